@@ -22,9 +22,14 @@ a few per cent of the episode mean.  When an episode ends inside the timed regio
          bench.py --gpus N --steps K --warmup W # the same under a launcher; a launcher whose world differs from --gpus is refused
                                                 # (env-batch split, no collective on the data path; `rccl_ranks` = the world RCCL reports)
 
-Rank 0 prints ONE JSON line.  `roofline` prices the step kernel against HBM (this path has no dense
-contraction, MFMA is irrelevant); `cpu_baseline` is the C oracle (oracle/, test infrastructure) timed on the
-host cores of the same box on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run measures the headline figure and nothing else: set-up, fast-forward, warm-up, the K
+timed steps (no per-launch events), the line.  Everything else the benchmark measures is behind --full: `roofline` prices the step
+kernel against HBM (this path has no dense contraction, MFMA is irrelevant) from per-launch HIP events of the timed steps;
+`all_outputs` times 20 untimed steps with every derived buffer written; `host.issue_us_per_step` times the issue of the first untimed
+steps; `cpu_baseline` is the C oracle (oracle/, test infrastructure) timed on the host cores of the same box on a bounded sample.
+
+  python bench.py --dump-outputs DIR            # after the timed steps: what the last timed step computed, DIR/<name>.npy
+                                                # (float32 / float64; rank 0's environments, a seeded sample of them above 64 MB)
 """
 import argparse
 import json
@@ -120,9 +125,11 @@ def window_start(steps, warmup):
     return max(warmup, min(EPISODE_MID - steps // 2, EPISODE_STEPS - steps))
 
 
-def run_timed(sims, steps, warmup, barrier, sync, reduce_max, all_outputs_steps=0):
+def run_timed(sims, steps, warmup, barrier, sync, reduce_max, all_outputs_steps=0, extras=True):
     """W untimed steps, then exactly K timed steps bracketed by barrier + device sync; max over ranks.  `sims`: the pipes of
-    this rank -- every step launches [agent, step] on each pipe's own stream, one host thread issuing them in turn."""
+    this rank -- every step launches [agent, step] on each pipe's own stream, one host thread issuing them in turn.
+    extras=False (a plain bench.py run): the K timed steps are the only measurement -- no host issue probe, no per-launch HIP events,
+    no statistics reads; kernel_ms, launches, st0, st1 and issue_s come back as 0.0, 0, None, None, None."""
     from resco_amd.sim import SimGroup
     # (tests/test_distributed_cpu.py drives this function with CPU stand-ins that have no C handle: per-pipe calls there)
     group = SimGroup(sims) if all(getattr(s, '_h', None) is not None for s in sims) else None
@@ -160,7 +167,7 @@ def run_timed(sims, steps, warmup, barrier, sync, reduce_max, all_outputs_steps=
     # for.  Under N ranks this is one rank's issue cost with the others competing for the cores: 1 / it is the step rate the host
     # side can sustain.  (The network is still empty then: these steps say nothing about the kernel.)
     n_plain = (ff - n_all_ff) + (0 if n_all_ff else warmup - n_all)
-    n_probe = min(48, n_plain)
+    n_probe = min(48, n_plain) if extras else 0
     issue_s = None
     if n_probe > 0:
         sync()
@@ -186,9 +193,10 @@ def run_timed(sims, steps, warmup, barrier, sync, reduce_max, all_outputs_steps=
     for _ in range(warmup if n_all_ff else 0):
         one()
     sync()
-    st0 = stats()
-    for sim in sims:
-        sim.timing(True)
+    st0 = stats() if extras else None
+    if extras:
+        for sim in sims:
+            sim.timing(True)
     barrier()
     sync()
     t0 = time.perf_counter()
@@ -198,12 +206,13 @@ def run_timed(sims, steps, warmup, barrier, sync, reduce_max, all_outputs_steps=
     barrier()
     t1 = time.perf_counter()
     kernel_ms, launches = 0.0, 0
-    for sim in sims:
-        ms, n = sim.timing_read()
-        kernel_ms += ms
-        launches += n
-        sim.timing(False)
-    st1 = stats()
+    if extras:
+        for sim in sims:
+            ms, n = sim.timing_read()
+            kernel_ms += ms
+            launches += n
+            sim.timing(False)
+    st1 = stats() if extras else None
     elapsed = reduce_max(t1 - t0)
     return elapsed, kernel_ms, launches, st0, st1, all_outputs_rate, n_all, t1 - t0, issue_s
 
@@ -227,6 +236,34 @@ def state_digest(sims, dist, rank, world):
         dist.all_gather_object(parts, per_env)
         per_env = [x for p in parts for x in p]
     return hashlib.sha1(''.join(per_env).encode()).hexdigest()
+
+
+# what a caller of the timed path receives after one step: the outputs the bench writes (OUTPUTS), the per-signal rewards and metrics
+# that are always written, and the actions the on-device policy chose for that step
+DUMP_BUFFERS = OUTPUTS + ('wait', 'wait_norm', 'pressure', 'phase', 'queue_sum', 'queue_max', 'arrivals', 'departures', 'actions')
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(sims, outdir, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy for every DUMP_BUFFERS entry, environments of this rank in global order (the pipes concatenated): float32
+    buffers as they are, integer buffers as float64 (exact).  Above `limit` bytes in all, a fixed seeded sample of the environments
+    (same for every run with the same arguments) is written, with its indices as env_index.npy.  Returns the names written."""
+    import numpy as np
+    arrays = {}
+    for name in DUMP_BUFFERS:
+        a = np.concatenate([np.ascontiguousarray(s.read(name)) for s in sims])
+        arrays[name] = a if a.dtype == np.float32 else a.astype(np.float64)
+    n_envs = len(arrays[DUMP_BUFFERS[0]])
+    per_env = sum(a.nbytes for a in arrays.values()) // max(1, n_envs)
+    if per_env * n_envs > limit:
+        keep = max(1, (limit - 8 * n_envs) // per_env)
+        idx = np.sort(np.random.default_rng(0).choice(n_envs, keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[idx]) for k, a in arrays.items()}
+        arrays['env_index'] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+    return sorted(arrays)
 
 
 def bind_to_gpu_numa_node(local_rank):
@@ -344,10 +381,18 @@ def main():
                          'documented setPhase); 0: it stays until the next action (round 5\'s default: a heavier network, 469 instead of 421 '
                          'vehicles per environment in the driver\'s window); the figure is reported for both (profiles/r06_bench_both_modes.txt)')
     ap.add_argument('--digest', action='store_true', help='add a digest of the final per-environment state (all ranks, global env order)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything else the benchmark measures next to the headline figure: roofline (per-launch HIP events), all-outputs '
+                         'steps, host issue time, mean active vehicles, CPU oracle baseline (unless --no-cpu-baseline) and SUMO baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
+                         'at most 64 MB: a seeded sample of the environments above that; rank 0\'s environments)')
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the contract's launch -- N ranks, one per GPU, through torch.distributed.run
         # (the reference's only parallelism is a process per trial, main.py:40-44; here a process per GPU)
@@ -413,28 +458,17 @@ def main():
         return float(t.item())
 
     elapsed, kernel_ms, launches, st0, st1, all_out_rate, n_all, elapsed_local, issue_s = run_timed(sims, args.steps, args.warmup, barrier, sync, reduce_max,
-                                                                                             all_outputs_steps=20)
-    ticks = (st1['ticks'] - st0['ticks']).astype('float64')
-    mean_active = float(((st1['active_ticks'] - st0['active_ticks']) / ticks.clip(min=1)).mean()) if ticks.min() > 0 \
-        else float(st1['active'].mean())
+                                                                                             all_outputs_steps=20 if args.full else 0,
+                                                                                             extras=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sims, args.dump_outputs)
     info = sim.info()
-    env_steps = world * n_local * args.steps
-    value = env_steps / elapsed
-    b_alg = algorithmic_bytes_per_env_step(sc, mean_active)
-    b_wide = designed_bytes_per_env_step(sc, mean_active)
-    k_avg_s = (kernel_ms / max(1, launches)) * 1e-3
-    # one step = `pipes` launches of n_local / pipes environments that overlap on their streams: the bytes of all of them over
-    # the average duration of one of them (= pipes x the per-launch figure)
-    achieved_per_launch = b_alg * per / k_avg_s / 1e9 if k_avg_s > 0 else 0.0
-    # `achieved`: the algorithmic bytes of everything this rank stepped over ITS wall clock of the timed region -- no assumption
-    # about how well the launches of the pipes overlap (pipes x the per-launch figure is the upper bound, reported next to it)
-    achieved = b_alg * n_local * args.steps / elapsed_local / 1e9
+    value = world * n_local * args.steps / elapsed
     w0 = window_start(args.steps, args.warmup)
-    traffic, traffic_note = pmc_traffic(args, n_local, world)
     out = {
         'metric': 'env-steps/sec', 'value': value, 'unit': 'env-steps/s', 'n_gpus': world, 'rccl_ranks': rccl_ranks, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
-        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'full': args.full,
         'config': {'workload': '%s x %d lock-step envs per GPU (BASELINE config 3), fixed demand from the map\'s '
                                'rou.xml, on-device seeded random policy, Krauss sigma 0.5 + speedFactor dev 0.1'
                                % (args.map, n_local),
@@ -444,37 +478,14 @@ def main():
                    'outputs_per_step': list(OUTPUTS) + ['wait', 'wait_norm', 'pressure', 'phase', 'queue_sum', 'queue_max', 'arrivals', 'departures'],
                    'parallelism': 'env-batch split x%d, no collective on the data path' % world,
                    'rank0_numa_node': numa},
-        'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                     'frac': achieved / HBM_PEAK_GBS,
-                     'traffic': traffic, 'traffic_note': traffic_note,
-                     'kernel': 'rs_step_kernel', 'kernel_avg_ms': k_avg_s * 1e3, 'launches': launches,
-                     'concurrent_launches': args.pipes, 'achieved_per_launch': achieved_per_launch,
-                     'achieved_upper_bound': args.pipes * achieved_per_launch,
-                     'achieved_note': 'a step is %d launches of %d environments each on %d HIP streams.  `achieved` = algorithmic bytes of the '
-                                      '%d env-steps of the timed region / its wall clock on this rank; `achieved_per_launch` = algorithmic bytes of '
-                                      'one launch / its average duration by HIP events on its own stream, `achieved_upper_bound` = %d x that (what '
-                                      'perfectly overlapping launches would give); `traffic` = %d x the per-launch counter figure'
-                                      % (args.pipes, per, args.pipes, n_local * args.steps, args.pipes, args.pipes),
-                     'algorithmic_bytes_per_env_step': b_alg, 'env_steps_per_launch': per,
-                     'formula': 'SURVEY 8(d): 60*V + 12*S + 20*SL + 8*S', 'designed_bytes_per_env_step': b_wide,
-                     'achieved_designed_bytes': b_wide * n_local * args.steps / elapsed_local / 1e9,
-                     'note': 'state is Infinity-Cache resident and the kernel is issue/latency bound: the HBM '
-                             'fraction is small by construction (SURVEY.md 8d)'},
-        'mean_active_vehicles_per_env': mean_active,
-        'host': {'issue_us_per_step': issue_s * 1e6 if issue_s else None, 'calls_per_step': 2 * args.pipes if PER_PIPE_CALLS else 1,
-                 'note': 'rank 0: wall time of the calls that hand ONE step (agent + step kernel of every pipe) to the runtime, measured on the first (up to) 48 untimed steps, '
-                         'issued back to back and not waited for until all are issued; %s'
-                         % ('two calls through ctypes per pipe (rs_act_random, rs_step)' if PER_PIPE_CALLS else 'one call through ctypes (rs_group_step)')},
-        'sim_ticks_per_s': value * 10, 'vehicle_ticks_per_s': value * 10 * mean_active,
-        'all_outputs': {'value': world * n_local * all_out_rate if all_out_rate else None, 'unit': 'env-steps/s', 'steps': n_all,
-                        'episode_window': [max(0, w0 - args.warmup - n_all), max(0, w0 - args.warmup - n_all) + n_all] if w0 - args.warmup >= n_all else [w0 - n_all, w0],
-                        'note': 'rank 0, the last untimed steps before the warm-up (the network is nearly as loaded as in the timed window) '
-                                'with EVERY derived buffer written (lane_agg, drq_norm, wave, mplight, mplight_full, '
-                                'drq_norm_f16, lane_arrivals): rounds 1-2 measured this workload, rounds 3-4 write what config 3 consumes'},
+        'sim_ticks_per_s': value * 10,
     }
+    if args.full:
+        out.update(full_figures(args, sc, world, n_local, per, elapsed, kernel_ms, launches, st0, st1, all_out_rate, n_all, elapsed_local,
+                                issue_s, w0))
     if args.digest:
         out['state_digest'] = state_digest(sims, dist, rank, world)
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_cpu_baseline:
             try:
                 out['cpu_baseline'] = cpu_baseline(sc, args.seed)
@@ -499,6 +510,52 @@ def main():
             pass
         print(json.dumps(out), flush=True)
 
+
+def full_figures(args, sc, world, n_local, per, elapsed, kernel_ms, launches, st0, st1, all_out_rate, n_all, elapsed_local, issue_s, w0):
+    """the figures of a --full run next to the headline: roofline, host issue time, all-outputs rate, mean active vehicles"""
+    ticks = (st1['ticks'] - st0['ticks']).astype('float64')
+    mean_active = float(((st1['active_ticks'] - st0['active_ticks']) / ticks.clip(min=1)).mean()) if ticks.min() > 0 \
+        else float(st1['active'].mean())
+    value = world * n_local * args.steps / elapsed
+    b_alg = algorithmic_bytes_per_env_step(sc, mean_active)
+    b_wide = designed_bytes_per_env_step(sc, mean_active)
+    k_avg_s = (kernel_ms / max(1, launches)) * 1e-3
+    # one step = `pipes` launches of n_local / pipes environments that overlap on their streams: the bytes of all of them over
+    # the average duration of one of them (= pipes x the per-launch figure)
+    achieved_per_launch = b_alg * per / k_avg_s / 1e9 if k_avg_s > 0 else 0.0
+    # `achieved`: the algorithmic bytes of everything this rank stepped over ITS wall clock of the timed region -- no assumption
+    # about how well the launches of the pipes overlap (pipes x the per-launch figure is the upper bound, reported next to it)
+    achieved = b_alg * n_local * args.steps / elapsed_local / 1e9
+    traffic, traffic_note = pmc_traffic(args, n_local, world)
+    return {
+        'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                     'frac': achieved / HBM_PEAK_GBS,
+                     'traffic': traffic, 'traffic_note': traffic_note,
+                     'kernel': 'rs_step_kernel', 'kernel_avg_ms': k_avg_s * 1e3, 'launches': launches,
+                     'concurrent_launches': args.pipes, 'achieved_per_launch': achieved_per_launch,
+                     'achieved_upper_bound': args.pipes * achieved_per_launch,
+                     'achieved_note': 'a step is %d launches of %d environments each on %d HIP streams.  `achieved` = algorithmic bytes of the '
+                                      '%d env-steps of the timed region / its wall clock on this rank; `achieved_per_launch` = algorithmic bytes of '
+                                      'one launch / its average duration by HIP events on its own stream, `achieved_upper_bound` = %d x that (what '
+                                      'perfectly overlapping launches would give); `traffic` = %d x the per-launch counter figure'
+                                      % (args.pipes, per, args.pipes, n_local * args.steps, args.pipes, args.pipes),
+                     'algorithmic_bytes_per_env_step': b_alg, 'env_steps_per_launch': per,
+                     'formula': 'SURVEY 8(d): 60*V + 12*S + 20*SL + 8*S', 'designed_bytes_per_env_step': b_wide,
+                     'achieved_designed_bytes': b_wide * n_local * args.steps / elapsed_local / 1e9,
+                     'note': 'state is Infinity-Cache resident and the kernel is issue/latency bound: the HBM '
+                             'fraction is small by construction (SURVEY.md 8d)'},
+        'mean_active_vehicles_per_env': mean_active,
+        'host': {'issue_us_per_step': issue_s * 1e6 if issue_s else None, 'calls_per_step': 2 * args.pipes if PER_PIPE_CALLS else 1,
+                 'note': 'rank 0: wall time of the calls that hand ONE step (agent + step kernel of every pipe) to the runtime, measured on the first (up to) 48 untimed steps, '
+                         'issued back to back and not waited for until all are issued; %s'
+                         % ('two calls through ctypes per pipe (rs_act_random, rs_step)' if PER_PIPE_CALLS else 'one call through ctypes (rs_group_step)')},
+        'vehicle_ticks_per_s': value * 10 * mean_active,
+        'all_outputs': {'value': world * n_local * all_out_rate if all_out_rate else None, 'unit': 'env-steps/s', 'steps': n_all,
+                        'episode_window': [max(0, w0 - args.warmup - n_all), max(0, w0 - args.warmup - n_all) + n_all] if w0 - args.warmup >= n_all else [w0 - n_all, w0],
+                        'note': 'rank 0, the last untimed steps before the warm-up (the network is nearly as loaded as in the timed window) '
+                                'with EVERY derived buffer written (lane_agg, drq_norm, wave, mplight, mplight_full, '
+                                'drq_norm_f16, lane_arrivals): rounds 1-2 measured this workload, rounds 3-4 write what config 3 consumes'},
+    }
 
 if __name__ == '__main__':
     main()

@@ -1528,7 +1528,7 @@ def test_bench_runs_through_rccl_at_one_gpu():
     env = dict(os.environ, RESCO_BENCH_FORCE_DIST='1', MASTER_ADDR='127.0.0.1', MASTER_PORT='29533', RANK='0', WORLD_SIZE='1',
                LOCAL_RANK='0')
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '6', '--warmup', '2', '--envs', '256',
-                          '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=170)
+                          '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=170)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1 and out.stdout.strip().splitlines()[-1] == lines[0]          # one JSON line, and it is the last one
@@ -1538,6 +1538,43 @@ def test_bench_runs_through_rccl_at_one_gpu():
     assert line['all_outputs']['value'] > 0
     assert line['config']['episode_window'][1] - line['config']['episode_window'][0] == 6
 
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run prints the headline line only (no roofline, all-outputs, host or CPU figures: those are --full's), times
+    exactly --steps steps, and computes what a --full run computes: the same final state digest and the same --dump-outputs arrays
+    (float32 / float64, one per output of the timed path, every environment of the batch)"""
+    import json
+    import subprocess
+    import bench
+    common = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '6', '--warmup', '2', '--envs', '256', '--digest']
+    lines = {}
+    for mode in ('plain', 'full'):
+        extra = ['--full', '--no-cpu-baseline'] if mode == 'full' else []
+        r = subprocess.run(common + extra + ['--dump-outputs', str(tmp_path / mode)], capture_output=True, text=True, timeout=170)
+        assert r.returncode == 0, r.stderr[-2000:]
+        found = [l for l in r.stdout.strip().splitlines() if l.startswith('{"metric"')]
+        assert len(found) == 1 and r.stdout.strip().splitlines()[-1] == found[0]
+        lines[mode] = json.loads(found[0])
+    a, b = lines['plain'], lines['full']
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in a and key in b
+    assert a['metric'] == b['metric'] == 'env-steps/sec' and a['unit'] == 'env-steps/s' and a['dtype'] == 'f32' and a['higher_is_better']
+    assert a['full'] is False and b['full'] is True
+    assert not {'roofline', 'all_outputs', 'host', 'mean_active_vehicles_per_env', 'cpu_baseline'} & set(a)
+    assert {'roofline', 'all_outputs', 'host', 'mean_active_vehicles_per_env'} <= set(b)
+    assert b['roofline']['launches'] == 6 * 2                      # --steps timed steps of two pipes each
+    for line in (a, b):
+        assert line['steps'] == 6 and line['config']['episode_window'][1] - line['config']['episode_window'][0] == 6
+        assert abs(line['value'] * line['ms_per_step'] * 1e-3 - 256) < 1e-6 * 256      # env-steps of one step / its duration
+    assert a['state_digest'] == b['state_digest']
+    names = sorted(f[:-4] for f in os.listdir(str(tmp_path / 'plain')))
+    assert names == sorted(bench.DUMP_BUFFERS) == sorted(f[:-4] for f in os.listdir(str(tmp_path / 'full')))
+    for name in names:
+        x, y = np.load(str(tmp_path / 'plain' / (name + '.npy'))), np.load(str(tmp_path / 'full' / (name + '.npy')))
+        assert x.dtype in (np.float32, np.float64) and x.shape[0] == 256
+        np.testing.assert_array_equal(x, y, err_msg=name)
+    assert np.load(str(tmp_path / 'plain' / 'drq_norm.npy')).any()
 
 def test_two_ranks_through_bench_on_one_gpu():
     """The N > 1 launch of the contract (`python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2`) end to end

@@ -356,18 +356,23 @@ def test_out_of_range_actions_keep_the_current_phase():
     sim.close()
 
 
-REF_ENV = '/root/reference/resco_benchmark/environments'
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_ENV), reason='needs the reference net / route files (build container only)')
 def test_route_kwarg_one_route_file_per_run(tmp_path, monkeypatch):
     """MultiSignal(route=prefix): the demand of episode k comes from `<prefix>_<k>.rou.xml` over the net file, SUMO begins at 0
     (multi_signal.py:33-38, 123-124 -- how the reference runs the two grid maps).  Two route files cut from cologne1's demand (even /
-    odd trips, departures shifted to begin 0); the host emulation stands in for the HIP library."""
+    odd trips, departures shifted to begin 0); the host emulation stands in for the HIP library.  The map's net and route files are
+    stored gzip-compressed and unchanged in tests/golden/cologne1.{net,rou}.xml.gz."""
+    import gzip
+    import shutil
     import xml.etree.ElementTree as ET
     import resco_amd.multi_signal as ms
     from resco_amd import rewards, states
-    root = ET.parse(os.path.join(REF_ENV, 'cologne1', 'cologne1.rou.xml')).getroot()
+    from conftest import GOLDEN
+    net = tmp_path / 'cologne1' / 'cologne1.net.xml'
+    net.parent.mkdir()
+    with gzip.open(os.path.join(GOLDEN, 'cologne1.net.xml.gz'), 'rb') as src, open(str(net), 'wb') as dst:
+        shutil.copyfileobj(src, dst)
+    with gzip.open(os.path.join(GOLDEN, 'cologne1.rou.xml.gz'), 'rb') as src:
+        root = ET.parse(src).getroot()
     vtypes = [el for el in root if el.tag == 'vType']
     trips = [el for el in root if el.tag == 'trip']
     for run, part in ((1, trips[0::2]), (2, trips[1::2])):
@@ -379,7 +384,7 @@ def test_route_kwarg_one_route_file_per_run(tmp_path, monkeypatch):
             t.set('depart', '%.2f' % (float(el.get('depart')) - 25200.0))
         ET.ElementTree(r).write(str(tmp_path / ('demand_%d.rou.xml' % run)))
     monkeypatch.setattr(ms, 'BatchedSim', lambda sc, n, **kw: EmuSim(sc, n, **{k: v for k, v in kw.items() if k != 'device'}))
-    env = ms.MultiSignal('t', 'cologne1', os.path.join(REF_ENV, 'cologne1', 'cologne1.net.xml'), states.mplight, rewards.wait,
+    env = ms.MultiSignal('t', 'cologne1', str(net), states.mplight, rewards.wait,
                          route=str(tmp_path / 'demand'), end_time=3600, yellow_length=3, log_dir=str(tmp_path) + os.sep, seed=3,
                          tripinfo=False)
     assert env.scenario.n_trips == len(trips[0::2]) and env.scenario.begin == 0

@@ -12,7 +12,7 @@ run() {  # label, ranks, map, envs per rank, pipes, extra env
   local label="$1" n="$2" map="$3" envs="$4" pipes="$5"; shift 5
   local line
   line=$(env "$@" python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 1000)) \
-         bench.py --gpus "$n" --steps 200 --warmup 20 --map "$map" --envs "$envs" --pipes "$pipes" --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1)
+         bench.py --gpus "$n" --steps 200 --warmup 20 --map "$map" --envs "$envs" --pipes "$pipes" --full --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1)
   python - "$label" "$n" "$envs" "$pipes" "$line" <<'PY'
 import json, sys
 label, n, envs, pipes, line = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]

@@ -8,13 +8,13 @@ TAG=${TAG:-final}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-python bench.py > $OUT/bench_default.log 2>/dev/null
+python bench.py --full > $OUT/bench_default.log 2>/dev/null
 tail -1 $OUT/bench_default.log > $OUT/bench_default.json
-python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_window.log 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_window.log 2>/dev/null
 tail -1 $OUT/bench_driver_window.log > $OUT/bench_driver_window.json
 # the other answer to what setPhase leaves behind (round 5's default): both windows
-python bench.py --tls-expiry 0 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_default_hold.json
-python bench.py --tls-expiry 0 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_driver_window_hold.json
+python bench.py --full --tls-expiry 0 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_default_hold.json
+python bench.py --full --tls-expiry 0 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_driver_window_hold.json
 python tools/phase_profile.py ingolstadt21 4096 0 > $OUT/phase_profile.txt 2>/dev/null
 python tools/phase_profile.py ingolstadt21 256 0 > $OUT/phase_profile_one_workgroup_per_cu.txt 2>/dev/null
 python tools/bench_configs.py > $OUT/bench_configs.jsonl 2>/dev/null
@@ -28,9 +28,9 @@ python tools/both_modes.py > $OUT/reference_bands_both_modes.txt 2>/dev/null
 [ "${HELDOUT:-1}" = 1 ] && python tools/heldout_both_modes.py > $OUT/heldout_both_modes.txt 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 # the SAME command as the contract line (default --steps / --warmup), CPU baseline off: per-kernel time by rocprofv3
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o $TAG -- python $R/bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o $TAG -- python $R/bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1
 grep '^{"metric"' $OUT/bench_under_rocprof.log > $OUT/bench_under_rocprof.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_dw -o ${TAG}_dw -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_dw_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_dw -o ${TAG}_dw -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_dw_under_rocprof.log 2>&1
 cd $R && bash tools/pmc_passes.sh $TAG/pmc_s300_w60 300 60 > $OUT/pmc_passes_s300_w60.log 2>&1
 bash tools/pmc_passes.sh $TAG/pmc_s20_w5 20 5 > $OUT/pmc_passes_s20_w5.log 2>&1
 [ "${DIAG:-1}" = 1 ] && bash tools/pmc_diag.sh $TAG/pmcdiag > $OUT/pmc_diag.log 2>&1
