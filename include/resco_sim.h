@@ -291,6 +291,33 @@ int rs_idqn_set_device_weights(rs_policy_handle p, const float *conv_w, const fl
 int rs_idqn_set_lanes(rs_policy_handle p, const int32_t *lanes_per_signal);
 void rs_idqn_destroy(rs_policy_handle p);
 
+/* ---- fused MPLight policy (the shared FRAP network, resco_amd/csrc/resco_frap.h) ---------------------------------
+ * Replaces MPLight's act() (resco_benchmark/agents/mplight.py:13-130, agents/pfrl_dqn.py:119-188 SharedDQN.batch_act +
+ * SharedEpsGreedy, agents/agent.py:57-79): ONE network shared by every signal of the map, P = len(phase_pairs) Q-values per
+ * (environment, signal) row, on the states.mplight rows (demand_shape 1: int32 RS_BUF_MPLIGHT [N][S][13]) or the
+ * states.mplight_full rows (demand_shape 4: f32 RS_BUF_MPLIGHT_FULL [N][S][49]).
+ * rs_mplight_create: pairs int32 [P][2] (movements 0..11), valid int32 [S][P] (local action of pair g for signal s, -1 = not
+ * valid), order int32 [S][P] (the valid pairs in the reference's valid_acts dict order, -1 terminated) -- the tables
+ * resco_amd/sim.py:maxwave_tables builds; a signal's local actions in dict order must be 0 .. n-1 (true on every shipped map),
+ * otherwise RS_EINVAL.  weights: host f32, FRAP's parameters in state_dict order, each row-major (1365 + 4 D floats):
+ *   p.weight [2][4], d.weight [4][D], d.bias [4], lane_embedding.weight [16][8], lane_embedding.bias [16],
+ *   lane_conv.weight [20][32], lane_conv.bias [20], relation_embedding.weight [2][4], relation_conv.weight [20][4],
+ *   relation_conv.bias [20], hidden_layer.weight [20][20], hidden_layer.bias [20], before_merge.weight [20], before_merge.bias [1]
+ * rs_mplight_act: obs, actions (int32 [N][S], the LOCAL action the simulator takes), pair_index (int32 [N][S], the global pair g the
+ * reference's replay stores; may be NULL) and q (f32 [N][S][16], -inf beyond P; may be NULL) are DEVICE pointers.  Greedy: the first
+ * maximum of Q over the signal's valid pairs in dict order (strict >); with probability epsilon the k-th valid pair, k uniform in
+ * [0, n_valid) -- the draws are the counter hash over (seed; env_base + env, signal, step_key).  Only the Q of the valid pairs of the
+ * rows that do not explore are computed unless q is requested.  dyn: NULL or a device {float epsilon; uint32 step_key} (as
+ * rs_idqn_act).  An IDQN handle passed here, or an MPLight handle passed to rs_idqn_*, is refused with RS_EINVAL.
+ * rs_mplight_set_device_weights: point the policy at a caller-owned DEVICE copy of the packed weights (borrowed, read in stream
+ * order by later launches). */
+int rs_mplight_create(int32_t device_id, int32_t demand_shape, int32_t n_pairs, const int32_t *pairs, int32_t n_signals,
+                      const int32_t *valid, const int32_t *order, const float *weights, rs_policy_handle *out);
+int rs_mplight_act(rs_policy_handle p, const void *obs, int32_t n_envs, int32_t env_base, float epsilon, uint32_t seed, uint32_t step_key,
+                   const void *dyn, int32_t *actions, int32_t *pair_index, float *q, void *stream);
+int rs_mplight_set_device_weights(rs_policy_handle p, const float *weights);
+void rs_mplight_destroy(rs_policy_handle p);
+
 /* ---- a whole group of handles stepped by ONE call --------------------------------------------------------------
  * The environments of one GPU are split over several handles ("pipes") whose kernels overlap on their own
  * streams; driven from Python that costs two calls through ctypes per pipe and step (agent + rs_step, ~37 us each), which is the
@@ -304,13 +331,16 @@ void rs_idqn_destroy(rs_policy_handle p);
  *   RS_AGENT_IDQN         rs_idqn_act(policy, h's RS_BUF_DRQ_NORM_F16, mode, epsilon + k * epsilon_step (>= 0), seed, step_key + k);
  *                         the epsilon-greedy draws are keyed by the GLOBAL environment index (env_base + e), so that a batch
  *                         split over pipes or GPUs draws what the single batch draws
+ *   RS_AGENT_MPLIGHT      rs_mplight_act(policy, h's RS_BUF_MPLIGHT (demand_shape 1) or RS_BUF_MPLIGHT_FULL (4), epsilon + k * epsilon_step
+ *                         (>= 0), seed, step_key + k), keyed by the global environment index as IDQN; mode must be 0, and the buffer the
+ *                         policy reads must not be switched off (rs_set_outputs)
  * Returns the first error (codes as everywhere; rs_last_error of the handle it occurred on). */
-enum rs_agent { RS_AGENT_NONE = 0, RS_AGENT_RANDOM = 1, RS_AGENT_MAXWAVE = 2, RS_AGENT_MAXPRESSURE = 3, RS_AGENT_IDQN = 4 };
+enum rs_agent { RS_AGENT_NONE = 0, RS_AGENT_RANDOM = 1, RS_AGENT_MAXWAVE = 2, RS_AGENT_MAXPRESSURE = 3, RS_AGENT_IDQN = 4, RS_AGENT_MPLIGHT = 5 };
 typedef struct rs_group_agent {
     int32_t kind;               /* enum rs_agent */
-    uint32_t step_key;          /* RANDOM, IDQN: key of the call's first step */
-    rs_policy_handle policy;    /* IDQN */
-    int32_t mode;               /* IDQN: 0 epsilon-greedy, 1 softmax sampling (rs_idqn_act) */
+    uint32_t step_key;          /* RANDOM, IDQN, MPLIGHT: key of the call's first step */
+    rs_policy_handle policy;    /* IDQN, MPLIGHT */
+    int32_t mode;               /* IDQN: 0 epsilon-greedy, 1 softmax sampling (rs_idqn_act); MPLIGHT: 0 */
     float epsilon, epsilon_step;
     uint32_t seed;
 } rs_group_agent;

@@ -107,6 +107,7 @@ __device__ unsigned long long *g_sec_prof;
 #endif
 #include "resco_step.h"
 #include "resco_policy.h"
+#include "resco_frap.h"
 
 // ------------------------------------------------------------------------------------------------ kernels
 // The tables / state / output descriptors live in ONE constant block in device memory (StepArgs): passed by value they
@@ -912,9 +913,12 @@ extern "C" int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int
 
 
 // ------------------------------------------------------------------------------------------------ fused IDQN policy
+enum { POLICY_IDQN = 0, POLICY_MPLIGHT = 1 };
 struct rs_policy {
     int device = 0;
-    PolicyTab W{};
+    int kind = POLICY_IDQN;     // which rs_*_create made it: the entry points of the other kind refuse it
+    PolicyTab W{};              // IDQN
+    FrapTab F{};                // MPLight
     std::vector<void *> allocs;
 };
 
@@ -962,11 +966,90 @@ extern "C" int rs_idqn_create(int32_t device_id, int32_t n_signals, int32_t lmax
 
 extern "C" int rs_idqn_act(rs_policy_handle p, const void *obs, int32_t n_envs, int32_t env_base, int32_t mode, float epsilon, uint32_t seed, uint32_t step_key,
                            const void *dyn, int32_t *actions, float *q, void *stream) {
-    if (!p || !obs || !actions || n_envs <= 0 || mode < 0 || mode > 1) return RS_EINVAL;
+    if (!p || p->kind != POLICY_IDQN || !obs || !actions || n_envs <= 0 || mode < 0 || mode > 1) return RS_EINVAL;
     if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
     hipLaunchKernelGGL(rs_idqn_forward_kernel, dim3((n_envs + POL_TM - 1) / POL_TM, p->W.S), dim3(256), 0, (hipStream_t)stream,
                        p->W, (const __half *)obs, (int)n_envs, (int)env_base, (int)mode, epsilon, seed, step_key, (const uint32_t *)dyn, actions, q);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+// ------------------------------------------------------------------------------------------------ fused MPLight (FRAP) policy
+static void mplight_launch(const FrapTab &F, const void *obs, int n_envs, int env_base, float eps, uint32_t seed, uint32_t step_key,
+                           const void *dyn, int32_t *actions, int32_t *pair_out, float *q, hipStream_t st) {
+    const int G = F.P <= 4 ? 4 : (F.P <= 8 ? 8 : 16), rows = 256 / G;
+    hipLaunchKernelGGL(rs_mplight_act_kernel, dim3((n_envs + rows - 1) / rows, F.S), dim3(256), 0, st, F, obs, n_envs, env_base, eps, seed,
+                       step_key, (const uint32_t *)dyn, actions, pair_out, q);
+}
+
+extern "C" int rs_mplight_create(int32_t device_id, int32_t demand_shape, int32_t n_pairs, const int32_t *pairs, int32_t n_signals,
+                                 const int32_t *valid, const int32_t *order, const float *weights, rs_policy_handle *out) {
+    if (!out) return RS_EINVAL;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_err = "no HIP device visible (this library has no CPU fallback)"; return RS_EHIP; }
+    if (device_id < 0 || device_id >= ndev || (demand_shape != 1 && demand_shape != 4) || n_pairs < 2 || n_pairs > FRAP_PMAX || n_signals <= 0 ||
+        !pairs || !valid || !order || !weights) {
+        g_create_err = "rs_mplight_create: bad argument (demand_shape 1 or 4, 2 <= n_pairs <= 16, 1 <= n_signals, tables and weights required)";
+        return RS_EINVAL;
+    }
+    const int P = n_pairs, S = n_signals;
+    for (int i = 0; i < 2 * P; ++i)
+        if (pairs[i] < 0 || pairs[i] >= FRAP_MV) { g_create_err = "rs_mplight_create: a phase pair names a movement outside 0..11"; return RS_EINVAL; }
+    // the exploration draw takes the k-th valid pair of the dict order; the reference takes reverse_valid[k]: the same pair only while
+    // the local actions of the valid pairs, in dict order, are 0, 1, .., n - 1
+    std::vector<int32_t> nv((size_t)S, 0);
+    for (int s = 0; s < S; ++s) {
+        int n = 0;
+        while (n < P && order[s * P + n] >= 0) ++n;
+        int n_valid = 0;
+        for (int g = 0; g < P; ++g) n_valid += valid[s * P + g] >= 0;
+        if (n == 0 || n != n_valid) { g_create_err = "rs_mplight_create: order[s] must list exactly the valid pairs of signal s (at least one)"; return RS_EINVAL; }
+        for (int k = 0; k < n; ++k) {
+            const int g = order[s * P + k];
+            if (g >= P || valid[s * P + g] != k) {
+                g_create_err = "rs_mplight_create: the local actions of a signal's valid pairs, in dict order, must be 0 .. n-1"; return RS_EINVAL; }
+        }
+        nv[(size_t)s] = n;
+    }
+    if (hipSetDevice(device_id) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RS_EHIP; }
+    rs_policy *p = new (std::nothrow) rs_policy();
+    if (!p) return RS_ENOMEM;
+    p->device = device_id;
+    p->kind = POLICY_MPLIGHT;
+    p->F.P = P; p->F.S = S; p->F.D = demand_shape;
+    const size_t nw = (size_t)FrapOff(demand_shape).n;
+    int rc;
+    if ((rc = pol_upload<float>(p, &p->F.w, weights, nw)) || (rc = pol_upload<int32_t>(p, &p->F.pairs, pairs, (size_t)P * 2)) ||
+        (rc = pol_upload<int32_t>(p, &p->F.valid, valid, (size_t)S * P)) || (rc = pol_upload<int32_t>(p, &p->F.order, order, (size_t)S * P)) ||
+        (rc = pol_upload<int32_t>(p, &p->F.nvalid, nv.data(), (size_t)S))) {
+        g_create_err = "rs_mplight_create: device allocation / upload failed";
+        rs_mplight_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return RS_OK;
+}
+
+extern "C" int rs_mplight_act(rs_policy_handle p, const void *obs, int32_t n_envs, int32_t env_base, float epsilon, uint32_t seed, uint32_t step_key,
+                              const void *dyn, int32_t *actions, int32_t *pair_index, float *q, void *stream) {
+    if (!p || p->kind != POLICY_MPLIGHT || !obs || !actions || n_envs <= 0) return RS_EINVAL;
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    mplight_launch(p->F, obs, n_envs, env_base, epsilon, seed, step_key, dyn, actions, pair_index, q, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_mplight_set_device_weights(rs_policy_handle p, const float *weights) {
+    if (!p || p->kind != POLICY_MPLIGHT || !weights) return RS_EINVAL;
+    p->F.w = weights;
+    return RS_OK;
+}
+
+extern "C" void rs_mplight_destroy(rs_policy_handle p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    (void)hipDeviceSynchronize();
+    for (void *d : p->allocs) (void)hipFree(d);
+    delete p;
 }
 
 // ---- one env-step (or n of them) of a whole group of handles in ONE call (include/resco_sim.h: rs_group_step)
@@ -980,10 +1063,20 @@ extern "C" int rs_group_step(const rs_handle *hs, int32_t n_handles, const rs_gr
             if (!h->pairs) { h->err = "rs_group_step: the MAXWAVE / MAXPRESSURE tables are installed by a first rs_act_maxwave call"; return RS_EINVAL; }
             if (!(h->out_mask & (kind == RS_AGENT_MAXPRESSURE ? OUT_MPLIGHT : OUT_WAVE))) { h->err = "rs_group_step: the agent's input buffer is switched off (rs_set_outputs)"; return RS_EINVAL; }
         } else if (kind == RS_AGENT_IDQN) {
-            if (!agent->policy || agent->mode < 0 || agent->mode > 1 || agent->policy->W.S != h->K.n_signals || agent->policy->W.lmax != h->K.lmax) {
+            if (!agent->policy || agent->policy->kind != POLICY_IDQN || agent->mode < 0 || agent->mode > 1 || agent->policy->W.S != h->K.n_signals || agent->policy->W.lmax != h->K.lmax) {
                 h->err = "rs_group_step: RS_AGENT_IDQN needs a policy built for this scenario (n_signals, lmax)"; return RS_EINVAL; }
             if (agent->policy->device != h->device) { h->err = "rs_group_step: the policy's weights live on another device than this handle"; return RS_EINVAL; }
             if (!(h->out_mask & OUT_DRQ_F16)) { h->err = "rs_group_step: RS_AGENT_IDQN reads RS_BUF_DRQ_NORM_F16, which rs_set_outputs has switched off"; return RS_EINVAL; }
+        } else if (kind == RS_AGENT_MPLIGHT) {
+            if (!agent->policy || agent->policy->kind != POLICY_MPLIGHT || agent->policy->F.S != h->K.n_signals) {
+                h->err = "rs_group_step: RS_AGENT_MPLIGHT needs an rs_mplight_create policy built for this scenario (n_signals)"; return RS_EINVAL; }
+            if (agent->mode != 0) { h->err = "rs_group_step: RS_AGENT_MPLIGHT has only mode 0 (epsilon-greedy)"; return RS_EINVAL; }
+            if (agent->policy->device != h->device) { h->err = "rs_group_step: the policy's weights live on another device than this handle"; return RS_EINVAL; }
+            if (!(h->out_mask & (agent->policy->F.D == 1 ? OUT_MPLIGHT : OUT_MPLIGHT_FULL))) {
+                h->err = agent->policy->F.D == 1 ? "rs_group_step: RS_AGENT_MPLIGHT reads RS_BUF_MPLIGHT, which rs_set_outputs has switched off"
+                                                 : "rs_group_step: RS_AGENT_MPLIGHT reads RS_BUF_MPLIGHT_FULL, which rs_set_outputs has switched off";
+                return RS_EINVAL;
+            }
         } else if (kind != RS_AGENT_NONE && kind != RS_AGENT_RANDOM) { h->err = "rs_group_step: unknown agent kind"; return RS_EINVAL; }
     }
     for (int k = 0; k < n_steps; ++k)
@@ -1005,6 +1098,13 @@ extern "C" int rs_group_step(const rs_handle *hs, int32_t n_handles, const rs_gr
                 hipLaunchKernelGGL(rs_idqn_forward_kernel, dim3((h->n_envs + POL_TM - 1) / POL_TM, h->K.n_signals), dim3(256), 0, st,
                                    agent->policy->W, (const __half *)h->O.drq_f16(), (int)h->n_envs, (int)h->P.env_base, (int)agent->mode, eps,
                                    agent->seed, agent->step_key + (uint32_t)k, (const uint32_t *)nullptr, h->actions, (float *)nullptr);
+            } else if (kind == RS_AGENT_MPLIGHT) {
+                float eps = agent->epsilon + (float)k * agent->epsilon_step;
+                if (eps < 0.0f) eps = 0.0f;
+                const FrapTab &F = agent->policy->F;
+                const void *obs = F.D == 1 ? (const void *)h->O.mplight() : (const void *)h->O.mplight_full();
+                mplight_launch(F, obs, h->n_envs, h->P.env_base, eps, agent->seed, agent->step_key + (uint32_t)k, nullptr, h->actions, nullptr,
+                               nullptr, st);
             }
             if (kind != RS_AGENT_NONE) HIPCHK(h, hipGetLastError());
             const int rc = launch_step(h, st, h->K.step_length * h->ratio, 1);
@@ -1015,7 +1115,7 @@ extern "C" int rs_group_step(const rs_handle *hs, int32_t n_handles, const rs_gr
 
 extern "C" int rs_idqn_set_device_weights(rs_policy_handle p, const float *conv_w, const float *conv_b, const uint16_t *w1, const float *b1,
                                           const uint16_t *w2, const float *b2, const uint16_t *w3, const float *b3) {
-    if (!p) return RS_EINVAL;
+    if (!p || p->kind != POLICY_IDQN) return RS_EINVAL;
     if (conv_w) p->W.conv_w = conv_w;
     if (conv_b) p->W.conv_b = conv_b;
     if (w1) p->W.w1 = (const h4_t *)w1;
@@ -1030,7 +1130,7 @@ extern "C" int rs_idqn_set_device_weights(rs_policy_handle p, const float *conv_
 // The networks' own input sizes: signal s observes lanes[s] lanes, so the fc1 rows of its padded lanes (beyond (lanes[s] - 1) * 4
 // per conv channel) are zero and the kernel may skip their k-steps -- results are unchanged, the work follows the real head sizes.
 extern "C" int rs_idqn_set_lanes(rs_policy_handle p, const int32_t *lanes_per_signal) {
-    if (!p || !lanes_per_signal) return RS_EINVAL;
+    if (!p || p->kind != POLICY_IDQN || !lanes_per_signal) return RS_EINVAL;
     if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
     std::vector<int32_t> hp((size_t)p->W.S);
     for (int s = 0; s < p->W.S; ++s) {

@@ -32,7 +32,7 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_act_maxwave', 'rs_get_buffer', 'rs_read_buffer', 'rs_stats', 'rs_snapshot', 'rs_restore',
                'rs_snapshot_free', 'rs_timing', 'rs_timing_read', 'rs_set_seed', 'rs_phase_profile', 'rs_info',
                'rs_idqn_create', 'rs_idqn_act', 'rs_idqn_set_device_weights', 'rs_idqn_set_lanes', 'rs_idqn_destroy', 'rs_group_step',
-               'rs_default_block']
+               'rs_default_block', 'rs_mplight_create', 'rs_mplight_act', 'rs_mplight_set_device_weights', 'rs_mplight_destroy']
 
 _lib = None
 
@@ -93,7 +93,7 @@ def load_library():
     return _lib
 
 
-AGENT = {'none': 0, 'random': 1, 'maxwave': 2, 'maxpressure': 3, 'idqn': 4}      # enum rs_agent
+AGENT = {'none': 0, 'random': 1, 'maxwave': 2, 'maxpressure': 3, 'idqn': 4, 'mplight': 5}      # enum rs_agent
 
 
 class GroupAgent(C.Structure):
@@ -105,7 +105,7 @@ class GroupAgent(C.Structure):
 class SimGroup:
     """The handles ("pipes") of one GPU stepped together by ONE call through the C ABI per env-step (rs_group_step): for every
     pipe the agent's kernel and the step kernel on the pipe's own stream.  agent: 'none' | 'random' | 'maxwave' | 'maxpressure' |
-    'idqn' (policy = an rs_policy_handle, e.g. FusedIDQN.handle)."""
+    'idqn' | 'mplight' (policy = an rs_policy_handle: FusedIDQN.handle, FusedMPLight.handle)."""
 
     def __init__(self, sims):
         self.sims = list(sims)
