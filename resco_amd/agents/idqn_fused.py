@@ -40,6 +40,15 @@ def _fragment_index(K, N, n_ksteps, n_tiles, zero_index):
     return np.where((kk < K) & (nn < N), kk * N + nn, zero_index).astype(np.int64)
 
 
+def repack_index(lmax, amax):
+    """Flat gather indices of FusedIDQN.refresh_on_device: per signal, w1 / w2 / w3 of pack_idqn_weights (flattened) =
+    fc*_w[s].reshape(-1)[index], -1 where the fragment is zero padding."""
+    H, hp = lmax - 1, lmax // 2
+    base = _fragment_index(H * 4, 64, hp, 2, -1)             # [hp, 2, 64, 4] into one channel's [H*4, 64] block
+    i1 = np.stack([np.where(base >= 0, c * H * 4 * 64 + base, -1) for c in range(64)]).reshape(-1)
+    return {'w1': i1, 'w2': _fragment_index(64, 64, 8, 2, -1).reshape(-1), 'w3': _fragment_index(64, amax, 8, 1, -1).reshape(-1)}
+
+
 def pack_idqn_weights(net):
     """numpy arrays in the order rs_idqn_create takes them."""
     S, lmax = len(net.lanes), net.lmax
@@ -113,14 +122,10 @@ class FusedIDQN:
         (index_select + mask + casting copy each)."""
         net, S = self.net, self.S
         dev = net.fc1_w.device
-        H, hp, A = self.lmax - 1, self.lmax // 2, net.amax
+        A = net.amax
         if not hasattr(self, '_idx'):
-            base = _fragment_index(H * 4, 64, hp, 2, -1)             # [hp, 2, 64, 4] into one channel's [H*4, 64] block
-            i1 = np.stack([np.where(base >= 0, c * H * 4 * 64 + base, -1) for c in range(64)]).reshape(-1)
-            i2 = _fragment_index(64, 64, 8, 2, -1).reshape(-1)
-            i3 = _fragment_index(64, A, 8, 1, -1).reshape(-1)
             self._idx, self._mask, self._dev = {}, {}, {}
-            for k, i in (('w1', i1), ('w2', i2), ('w3', i3)):
+            for k, i in repack_index(self.lmax, A).items():
                 self._idx[k] = torch.as_tensor(np.maximum(i, 0), device=dev)
                 self._mask[k] = torch.as_tensor((i >= 0).astype(np.float32), device=dev)
                 # + 2 KB: the kernel's copy passes of the last conv channel may read up to 1 KB past the fc1 fragments

@@ -815,6 +815,15 @@ def test_fused_idqn_policy_matches_torch_reference(map_name, n):
         A = net.actions[s_]
         np.testing.assert_allclose(q[:, s_, :A].cpu().numpy(), ref[:, s_, :A].detach().cpu().numpy(), atol=3e-2, rtol=0)
         assert torch.isinf(q[:, s_, A:]).all()
+    # the rounding-faithful reference of the kernel's own arithmetic (tests/idqn_kernel_ref.py), element-wise within its bound
+    from idqn_kernel_ref import idqn_kernel_ref
+    from resco_amd.agents.idqn_fused import pack_idqn_weights
+    q_k, bound = idqn_kernel_ref(pack_idqn_weights(net), net.lanes, obs.cpu().numpy(), n)
+    valid = np.isfinite(q_k)
+    assert np.array_equal(valid, np.isfinite(q.cpu().numpy()))
+    ratio = np.abs(q.cpu().numpy()[valid] - q_k[valid]) / bound[valid]
+    print('%s: max |q - ref| / bound = %.3f' % (map_name, ratio.max()))
+    assert ratio.max() <= 1.0
     top2 = ref.masked_fill(~net.action_mask, float('-inf')).topk(2, dim=-1).values
     clear = (top2[..., 0] - top2[..., 1]) > 6e-2
     assert clear.float().mean() > 0.3
