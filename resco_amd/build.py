@@ -15,13 +15,13 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 #   v_cndmask pairs (and the s_nop the pair needs on gfx950): +0.6-0.9 % (profiles/r06_ab_linkrec_nnan.txt); results bit-identical
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fno-honor-nans', '-mllvm', '-disable-machine-licm', '-fPIC', '-shared',
          '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(HERE, 'csrc')]
+_DEPS = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('resco_host.h', 'resco_step.h', 'resco_tables.h', 'resco_policy.h', 'resco_frap.h')] + \
+        [os.path.join(ROOT, 'include', f) for f in ('resco_sim.h', 'resco_model.h')]
 
 
 def build_library(force=False, verbose=False):
-    deps = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('resco_step.h', 'resco_tables.h', 'resco_policy.h', 'resco_frap.h')] + \
-           [os.path.join(ROOT, 'include', f) for f in ('resco_sim.h', 'resco_model.h')]
     force = force or os.environ.get('GRAFT_FORCE_BUILD') == '1'
-    if not force and os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in deps):
+    if not force and os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in _DEPS):
         return LIB
     cmd = [HIPCC] + FLAGS + [SRC, '-o', LIB]
     if verbose:
@@ -37,10 +37,8 @@ def build_check_library(force=False):
     """The CHECKING build: the step kernel's classification invariants (RS_ASSERT) counted on the device instead of compiled out
     (rs_stats()[11]); one capacity (256 slots: cologne8, ingolstadt7, cologne3) so that it compiles in seconds.  Test infrastructure
     of tests/test_gpu_parity.py::test_device_invariant_counter -- never loaded by the package."""
-    deps = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('resco_step.h', 'resco_tables.h', 'resco_policy.h', 'resco_frap.h')] + \
-           [os.path.join(ROOT, 'include', f) for f in ('resco_sim.h', 'resco_model.h')]
     force = force or os.environ.get('GRAFT_FORCE_BUILD') == '1'
-    if not force and os.path.exists(CHECK_LIB) and all(os.path.getmtime(CHECK_LIB) >= os.path.getmtime(d) for d in deps):
+    if not force and os.path.exists(CHECK_LIB) and all(os.path.getmtime(CHECK_LIB) >= os.path.getmtime(d) for d in _DEPS):
         return CHECK_LIB
     subprocess.check_call([HIPCC] + FLAGS + ['-DRS_DEVICE_ASSERT', '-DRS_ONE_CAP=256', SRC, '-o', CHECK_LIB])
     return CHECK_LIB

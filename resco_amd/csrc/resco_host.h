@@ -1,0 +1,201 @@
+// resco_host.h -- what surrounds the step body and is the same for the HIP library (resco_sim.hip) and for the host emulation of
+// the CPU tests (tests/hostemu/rs_emu.cpp): the per-element bodies of reset, re-init and the static agents, the buffer-mask ->
+// OUT_* mapping, the table of the RS_BUF_* buffers, and scenario -> KTab / KParams.  Written like resco_step.h: the includer
+// supplies the qualifier macros, nothing here calls HIP.  The library wraps the bodies in kernels and uploads the tables; the
+// emulation calls the bodies in loops and keeps the tables in host memory.
+#pragma once
+#include "resco_step.h"
+
+// ------------------------------------------------------------------------------------------------ reset / re-init (device or host)
+// Each body does the share of "thread" `first` of `stride` for ONE environment: the kernels pass (threadIdx.x, blockDim.x), the
+// emulation (0, 1).
+// reset an environment: no vehicles, every backlog at its first trip, TLS programs freshly installed
+// (Signal.__init__, traffic_signal.py:93-100)
+RS_DEV void rs_reset_env(const KTab &T, const State &G, const KParams &P, int env, int first, unsigned stride) {
+    const int C = T.capacity, S = T.n_signals;
+    const size_t eo = (size_t)env * C;
+    for (int s = first; s < C; s += stride) {
+        G.lane()[eo + s] = LANE_NONE; G.trip()[eo + s] = TRIP_NONE; G.owner()[eo + s] = OWNER_NONE;
+        G.rwait()[eo + s] = 0; G.swait()[eo + s] = 0; G.cursor()[eo + s] = 0; G.depart()[eo + s] = 0; G.wtot()[eo + s] = 0;
+        G.pos()[eo + s] = 0.0f; G.speed()[eo + s] = 0.0f; G.accel()[eo + s] = 0.0f; G.tloss()[eo + s] = 0.0f; G.sf()[eo + s] = 1.0f;
+        G.coop(0)[eo + s] = COOP_NONE; G.coop(1)[eo + s] = COOP_NONE; G.cooplead(0)[eo + s] = COOP_NONE; G.cooplead(1)[eo + s] = COOP_NONE;
+    }
+    for (int s = first; s < S; s += stride) {
+        int ph, left;
+        if (P.fixed_program) { ph = T.cold.fix_init_phase[s]; left = T.cold.fix_init_left[s]; }
+        else { ph = T.cold.tls_init_phase[s]; left = T.cold.tls_dur[T.cold.tls_dur_off[s] + ph]; }
+        G.tls[(env * S + s) * TLS_W + 0] = ph; G.tls[(env * S + s) * TLS_W + 1] = left; G.tls[(env * S + s) * TLS_W + 2] = 0; G.tls[(env * S + s) * TLS_W + 3] = 0;
+    }
+    for (int d = first; d < T.n_dep; d += stride) G.dep_next[(size_t)env * T.n_dep + d] = T.cold.dep_first[d];
+    for (int i = first; i < (C + 31) / 32; i += stride) G.mail[(size_t)env * ((C + 31) / 32) + i] = 0u;
+    for (int i = first; i < 4; i += stride) G.env[env * 4 + i] = 0;
+    for (int i = first; i < ST_N; i += stride) G.stats[(size_t)env * ST_N + i] = 0;
+    if (G.trip_log)
+        for (int i = first; i < T.n_trips * 4; i += stride) G.trip_log[(size_t)env * T.n_trips * 4 + i] = 0;
+}
+// fresh Signal objects on the running simulation (rs_reinit_signals)
+RS_DEV void rs_reinit_env(const KTab &T, const State &G, const KParams &P, int env, int first, unsigned stride) {
+    const int C = T.capacity, S = T.n_signals;
+    const size_t eo = (size_t)env * C;
+    for (int s = first; s < C; s += stride) { G.owner()[eo + s] = OWNER_NONE; G.rwait()[eo + s] = 0; }
+    for (int s = first; s < S; s += stride) {
+        if (!P.fixed_program) G.tls[(env * S + s) * TLS_W + 1] = T.cold.tls_dur[T.cold.tls_dur_off[s] + G.tls[(env * S + s) * TLS_W + 0]];
+        G.tls[(env * S + s) * TLS_W + 2] = 0; G.tls[(env * S + s) * TLS_W + 3] = 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ static agents (device or host)
+// The action of flat index i = env * n_signals + signal, i < n_envs * n_signals.
+// STOCHASTIC (agents/stochastic.py:17-18): uniform green index per (env, signal, step)
+RS_DEV int32_t rs_random_action(const KTab &T, const KParams &P, uint32_t step_key, int i) {
+    const int S = T.n_signals;
+    const int env = i / S, s = i - env * S;
+    const uint32_t h = d_hash(P.seed ^ 0xA5A5A5A5u, (uint32_t)(P.env_base + env), (uint32_t)s, step_key, 7u);
+    return (int32_t)(h % (uint32_t)T.cold.tls_ngreen[s]);
+}
+// MAXWAVE / MAXPRESSURE (agents/maxwave.py:18-38, maxpressure.py:13-18): first maximum over the valid
+// phase pairs (in the reference's iteration order) of obs[pair0] + obs[pair1]
+RS_DEV int32_t rs_maxwave_action(const KTab &T, const int32_t *pairs, int n_pairs, const int32_t *valid, const int32_t *order, int use_pressure,
+                                 const int32_t *mplight, const int32_t *wave, int i) {
+    const int s = i % T.n_signals;
+    const int32_t *obs = use_pressure ? mplight + (size_t)i * 13 + 1 : wave + (size_t)i * 12;
+    bool have = false;
+    int best = 0, best_act = 0;
+    for (int j = 0; j < n_pairs; ++j) {
+        const int p = order[s * n_pairs + j];     // the reference walks valid_acts in dict order; ties keep the first
+        if (p < 0) break;
+        const int act = valid[s * n_pairs + p];
+        if (act < 0) continue;
+        const int press = obs[pairs[p * 2]] + obs[pairs[p * 2 + 1]];
+        if (!have || press > best) { have = true; best = press; best_act = act; }
+    }
+    return best_act;
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+// which output buffers an observe writes (rs_set_outputs: bit b = buffer id b) as the kernel's OUT_* groups
+static inline uint32_t rs_out_mask(uint64_t buffer_mask) {
+    uint32_t m = 0;
+    if (buffer_mask & (1ull << RS_BUF_LANE_AGG)) m |= OUT_LANE_AGG;
+    if (buffer_mask & (1ull << RS_BUF_DRQ_NORM)) m |= OUT_DRQ_NORM;
+    if (buffer_mask & (1ull << RS_BUF_DRQ_NORM_F16)) m |= OUT_DRQ_F16;
+    if (buffer_mask & (1ull << RS_BUF_LANE_ARRIVALS)) m |= OUT_LANE_ARR;
+    if (buffer_mask & (1ull << RS_BUF_MPLIGHT)) m |= OUT_MPLIGHT;
+    if (buffer_mask & (1ull << RS_BUF_WAVE)) m |= OUT_WAVE;
+    if (buffer_mask & (1ull << RS_BUF_MPLIGHT_FULL)) m |= OUT_MPLIGHT_FULL;
+    if (buffer_mask & (1ull << RS_BUF_VEH_ACCEL)) m |= OUT_VEH_ACCEL;
+    return m;
+}
+
+// ---- the RS_BUF_* buffers: X(id, pointer, dtype, ndim, shape[0..3]) over G (State), O (Out), `actions` and the dimensions of BufDims
+struct Buf { void *ptr; int64_t shape[4]; int ndim; int dtype; size_t bytes; };
+struct BufDims { int64_t n, c, s, o, lmax, n_dep, n_trips; };      // envs, capacity, signals, observed lanes, .., trips (0: no trip log)
+static const size_t kDtypeSize[] = {4, 4, 2, 1, 2, 8, 4};
+#define RS_BUF_TABLE(X)                                                                                                               \
+    X(LANE_AGG, O.lane_agg(), F32, 3, n, o, 5, 1)           X(DRQ_NORM, O.drq_norm(), F32, 3, n, o, 5, 1)                             \
+    X(PHASE, O.phase(), I32, 2, n, s, 1, 1)                 X(MPLIGHT, O.mplight(), I32, 3, n, s, 13, 1)                              \
+    X(WAVE, O.wave(), I32, 3, n, s, 12, 1)                  X(WAIT, O.wait(), F32, 2, n, s, 1, 1)                                     \
+    X(WAIT_NORM, O.wait_norm(), F32, 2, n, s, 1, 1)         X(PRESSURE, O.pressure(), I32, 2, n, s, 1, 1)                             \
+    X(QUEUE_SUM, O.queue_sum(), I32, 2, n, s, 1, 1)         X(QUEUE_MAX, O.queue_max(), I32, 2, n, s, 1, 1)                           \
+    X(ACTIONS, actions, I32, 2, n, s, 1, 1)                 X(ENV, G.env, I32, 2, n, 4, 1, 1)                                         \
+    X(TLS, G.tls, I32, 3, n, s, TLS_W, 1)                                                                                             \
+    X(VEH_POS, G.pos(), F32, 2, n, c, 1, 1)                 X(VEH_SPEED, G.speed(), F32, 2, n, c, 1, 1)                               \
+    X(VEH_ACCEL, G.accel(), F32, 2, n, c, 1, 1)             X(VEH_TLOSS, G.tloss(), F32, 2, n, c, 1, 1)                               \
+    X(VEH_LANE, G.lane(), U16, 2, n, c, 1, 1)               X(VEH_TRIP, G.trip(), U16, 2, n, c, 1, 1)                                 \
+    X(VEH_CURSOR, G.cursor(), U16, 2, n, c, 1, 1)           X(VEH_SWAIT, G.swait(), U16, 2, n, c, 1, 1)                               \
+    X(VEH_RWAIT, G.rwait(), U16, 2, n, c, 1, 1)             X(VEH_DEPART, G.depart(), U16, 2, n, c, 1, 1)                             \
+    X(VEH_OWNER, G.owner(), U8, 2, n, c, 1, 1)              X(STATS, G.stats, I64, 2, n, ST_N, 1, 1)                                  \
+    X(DRQ_NORM_F16, O.drq_f16(), F16, 4, n, s, lmax, 5)     X(VEH_SF, G.sf(), F32, 2, n, c, 1, 1)                                     \
+    X(VEH_WTOT, G.wtot(), U16, 2, n, c, 1, 1)               X(TRIP_LOG, G.trip_log, I32, 3, n, n_trips, 4, 1)                         \
+    X(DEP_NEXT, G.dep_next, U16, 2, n, n_dep, 1, 1)                                                                                   \
+    X(VEH_COOP, G.coop(0), U32, 2, n, c, 1, 1)              X(VEH_COOPLEAD, G.cooplead(0), U32, 2, n, c, 1, 1)                        \
+    X(ARRIVALS, O.arrivals(), I32, 2, n, s, 1, 1)           X(DEPARTURES, O.departures(), I32, 2, n, s, 1, 1)                         \
+    X(MPLIGHT_FULL, O.mplight_full(), F32, 3, n, s, 49, 1)  X(LANE_ARRIVALS, O.lane_arr(), I32, 2, n, o, 1, 1)                        \
+    X(VEH_COOP_ODD, G.coop(1), U32, 2, n, c, 1, 1)          X(VEH_COOPLEAD_ODD, G.cooplead(1), U32, 2, n, c, 1, 1)                    \
+    X(VEH_MAIL, G.mail, U32, 2, n, (c + 31) / 32, 1, 1)
+#define RS_BUF_BIT(id, ptr, dt, nd, a, b, c_, d) | (1ull << RS_BUF_##id)
+static_assert((0ull RS_BUF_TABLE(RS_BUF_BIT)) == (1ull << RS_BUF_COUNT) - 1, "RS_BUF_TABLE must describe every buffer id below RS_BUF_COUNT");
+#undef RS_BUF_BIT
+#define RS_BUF_ONE(id, ptr, dt, nd, a, b, c_, d) + 1
+static_assert((0 RS_BUF_TABLE(RS_BUF_ONE)) == RS_BUF_COUNT, "RS_BUF_TABLE must describe every buffer id once");
+#undef RS_BUF_ONE
+static inline void rs_fill_bufs(Buf *bufs, const State &G, const Out &O, int32_t *actions, const BufDims &D) {
+    const int64_t n = D.n, c = D.c, s = D.s, o = D.o, lmax = D.lmax, n_dep = D.n_dep, n_trips = D.n_trips;
+#define RS_BUF_SET(id, ptr_, dt, nd, a, b, c_, d)                                                                  \
+    { Buf &B = bufs[RS_BUF_##id];                                                                                  \
+      B.ptr = (void *)(ptr_); B.dtype = RS_##dt; B.ndim = nd;                                                      \
+      B.shape[0] = (a); B.shape[1] = (b); B.shape[2] = (c_); B.shape[3] = (d);                                     \
+      B.bytes = (size_t)(B.shape[0] * B.shape[1] * B.shape[2] * B.shape[3]) * kDtypeSize[RS_##dt]; }
+    RS_BUF_TABLE(RS_BUF_SET)
+#undef RS_BUF_SET
+}
+// the bodies of rs_get_buffer and of rs_info behind the argument checks
+static inline void rs_buf_describe(const Buf &B, void **ptr, int64_t shape[4], int32_t *ndim, int32_t *dtype) {
+    if (ptr) *ptr = B.ptr;
+    if (shape) for (int i = 0; i < 4; ++i) shape[i] = B.shape[i];
+    if (ndim) *ndim = B.ndim;
+    if (dtype) *dtype = B.dtype;
+}
+static inline void rs_info_describe(int n_envs_, int block_, size_t lds_, int lmax_, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes,
+                                    int32_t *max_lanes_per_signal) {
+    if (n_envs) *n_envs = n_envs_;
+    if (block_threads) *block_threads = block_;
+    if (lds_bytes) *lds_bytes = (int32_t)lds_;
+    if (max_lanes_per_signal) *max_lanes_per_signal = lmax_;
+}
+
+// ---- scenario -> tables
+// The packed tables with the grid cell length of this scenario: build once to learn the sizes that do not depend on it, choose, build
+// for good.  Returns the error text, or NULL.
+static inline const char *rs_pack_tables(PackedTables &PT, const rs_scenario *sc) {
+    PackedTables probe;
+    if (!probe.build(sc)) { PT.err = probe.err; return PT.err.c_str(); }
+    if (!PT.build(sc, pick_cell_len(sc, probe.n_arr, probe.n_dep, probe.tls_maxl))) return PT.err.c_str();
+    return nullptr;
+}
+// the table members of KTab K: X(member, element type, source on the host, element count) -- the library uploads each, the
+// emulation keeps a host copy
+#define RS_KTAB_TABLES(X, K, PT, sc)                                                                                                  \
+    X(K.lanes_, LaneRec, PT.lanes.data(), PT.lanes.size()) X(K.links_, LinkRec, PT.links.data(), PT.links.size())                     \
+    X(K.foes_, FoeRec, PT.foes.data(), PT.foes.size()) X(K.rsteps_, RStep, PT.rsteps.data(), PT.rsteps.size())                        \
+    X(K.routes_, RouteRec, PT.routes.data(), PT.routes.size()) X(K.next_link_, uint16_t, PT.next_link.data(), PT.next_link.size())    \
+    X(K.trip_route_, uint16_t, PT.trip_route.data(), PT.trip_route.size()) X(K.trip_vtype_, uint8_t, PT.trip_vtype.data(), PT.trip_vtype.size()) \
+    X(K.route_cont_, float, PT.route_cont.data(), PT.route_cont.size()) X(K.notbest_, uint16_t, PT.notbest.data(), PT.notbest.size()) \
+    X(K.cold.trip_depart, int32_t, sc->trip_depart, sc->n_trips) X(K.cold.trip_next, uint16_t, PT.trip_next.data(), PT.trip_next.size()) \
+    X(K.cold.dep_lane, uint16_t, PT.dep_lane.data(), PT.dep_lane.size()) X(K.cold.dep_info, DepInfo, PT.dep_info.data(), PT.dep_info.size()) \
+    X(K.cold.dep_first, uint16_t, PT.dep_first.data(), PT.dep_first.size())                                                           \
+    X(K.cold.vtype_params, float, sc->vtype_params, sc->n_vtypes * VT_COLS)                                                           \
+    X(K.cold.tls8, uint8_t, PT.tls8.data(), PT.tls8.size()) X(K.cold.fix8, uint8_t, PT.fix8.data(), PT.fix8.size())                   \
+    X(K.cold.tls_nphase, int32_t, sc->tls_nphase, sc->n_signals) X(K.cold.tls_ngreen, int32_t, sc->tls_ngreen, sc->n_signals)         \
+    X(K.cold.tls_nlinks, int32_t, sc->tls_nlinks, sc->n_signals) X(K.cold.tls_state_off, int32_t, PT.tls_off_p.data(), sc->n_signals) \
+    X(K.cold.tls_dur_off, int32_t, sc->tls_dur_off, sc->n_signals) X(K.cold.tls_yel_off, int32_t, sc->tls_yel_off, sc->n_signals)     \
+    X(K.cold.tls_dur, int32_t, sc->tls_dur, sc->n_tls_dur) X(K.cold.tls_yellow, int32_t, sc->tls_yellow, sc->n_tls_yellow)            \
+    X(K.cold.tls_init_phase, int32_t, sc->tls_init_phase, sc->n_signals)                                                              \
+    X(K.cold.fix_nphase, int32_t, sc->fix_nphase, sc->n_signals) X(K.cold.fix_state_off, int32_t, PT.fix_off_p.data(), sc->n_signals) \
+    X(K.cold.fix_dur_off, int32_t, sc->fix_dur_off, sc->n_signals) X(K.cold.fix_dur, int32_t, sc->fix_dur, sc->n_fix_dur)             \
+    X(K.cold.fix_init_phase, int32_t, sc->fix_init_phase, sc->n_signals) X(K.cold.fix_init_left, int32_t, sc->fix_init_left, sc->n_signals) \
+    X(K.cold.lane_obs, int16_t, PT.lane_obs16.data(), PT.lane_obs16.size()) X(K.cold.obs_sig, int32_t, PT.obs_sig.data(), PT.obs_sig.size()) \
+    X(K.cold.sig_obs_start, int32_t, sc->sig_obs_start, sc->n_signals + 1)                                                            \
+    X(K.cold.mv_in_start, int32_t, sc->mv_in_start, sc->n_signals * 12 + 1) X(K.cold.mv_in_idx, int32_t, sc->mv_in_idx, sc->n_mv_in)  \
+    X(K.cold.mv_out_start, int32_t, sc->mv_out_start, sc->n_signals * 12 + 1) X(K.cold.mv_out_idx, int32_t, sc->mv_out_idx, sc->n_mv_out) \
+    X(K.cold.pr_out_start, int32_t, sc->pr_out_start, sc->n_signals + 1) X(K.cold.pr_out_idx, int32_t, sc->pr_out_idx, sc->n_pr_out)  \
+    X(K.cold.trips_cum, int32_t, sc->trips_cum, sc->horizon + 2)
+// rs_params.step_ratio: simulation ticks per step_sim() call
+static inline int rs_step_ratio(const rs_params *p) { return p->step_ratio > 1 ? p->step_ratio : 1; }
+// the scalar members of KTab
+static inline void rs_ktab_scalars(KTab &K, const PackedTables &PT, const rs_scenario *sc, int ratio) {
+    K.maxlen = PT.maxlen; K.occ_unit = PT.occ_unit;
+    K.n_trips = sc->n_trips; K.tls_maxl = PT.tls_maxl; K.kmax = sc->kmax;
+    K.n_lanes = sc->n_lanes; K.n_cells = PT.n_cells; K.n_signals = sc->n_signals; K.n_obs = sc->n_obs; K.n_vtypes = sc->n_vtypes;
+    // the kernel counts ticks: Signal.set_phase comes after yellow_length x step_ratio of them (multi_signal.py:102-105, 175-180);
+    // step_length stays what Signal.observe adds to a waiting time (traffic_signal.py:196)
+    K.horizon = sc->horizon; K.capacity = sc->capacity; K.step_length = sc->step_length; K.yellow_length = sc->yellow_length * ratio; K.lmax = PT.lmax;
+    K.n_arr = PT.n_arr; K.n_dep = PT.n_dep;
+}
+// the parameters of a handle that every launch starts from (launch_step / run_step fill in the per-launch members)
+static inline KParams rs_kparams(const rs_params *p, int32_t env_base, int32_t n_envs) {
+    KParams P{};
+    P.seed = p->seed; P.env_base = env_base; P.max_distance = p->max_distance; P.sigma = p->sigma;
+    P.speed_dev = p->speed_dev; P.fixed_program = p->fixed_program; P.tls_expiry = p->tls_hold == 0; P.n_envs = n_envs;
+    return P;
+}

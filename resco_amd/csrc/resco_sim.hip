@@ -105,7 +105,7 @@ __device__ unsigned long long *g_sec_prof;
 // (-ffp-contract=off): the one place where a compiler upgrade could silently skip a stop line.
 #define RS_ASSERT(c) if (!(c)) rs_atomic_add(&L.sc[SC_STATS + ST_INVARIANT], 1);     // (`L`: the working memory, in scope at every site)
 #endif
-#include "resco_step.h"
+#include "resco_host.h"
 #include "resco_policy.h"
 #include "resco_frap.h"
 
@@ -118,65 +118,13 @@ struct StepArgs { KTab T; State G; Out O; Lds L; };
 // global ones (global_load instead of flat_load, which would also tie up the LDS wait counter)
 typedef const __attribute__((address_space(4))) StepArgs *StepArgsPtr;
 
-// ---- the long code paths of a tick as FUNCTIONS: measured in round 6 and NOT adopted (build with -DRS_CALL_LONG to get it).  Inlined
-// into the tick loop, the walk over the links, the lane-change searches and the hand-over keep ~190 scalars alive at once -- table
-// bases, layout offsets, parameters -- and the 64-VGPR build (80 SGPRs: eight waves per SIMD) spills ~110 of them into VGPR lanes, a
-// v_readlane in front of every use.  A called function has a register allocation of its own (41 / 59 / 41 VGPRs, 70-78 SGPRs, no
-// SGPR spills inside) and loads what it needs from the constant block when it is entered; its arguments arrive in VGPRs (the calling
-// convention knows nothing about uniform values) and are made scalars again with v_readfirstlane.  Bit-exact, but 1-2 % SLOWER
-// (profiles/r06_ab_call.txt: ingolstadt21 x 4096 3.105 against 3.137 M env-steps/s, cologne1 x 1024 5.70 / 5.77, cologne8 x 2048 7.37 /
-// 7.51): the kernel itself still spills 102 scalars (the short paths, C and the observe phases hold as many), the calls add 48 bytes
-// of scratch per lane for the callee-saved registers, and a v_readlane is cheap next to what a spill costs elsewhere.
-__device__ __forceinline__ int rs_uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ uint32_t rs_uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ float rs_uni(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
-__device__ __forceinline__ StepArgsPtr rs_uni(StepArgsPtr p) {
-    const unsigned long long v = (unsigned long long)p;
-    return (StepArgsPtr)(((unsigned long long)rs_uni((uint32_t)(v >> 32)) << 32) | rs_uni((uint32_t)v));
-}
-// f(T, L, G) with the views a kernel of capacity CAP works with
-template <int CAP, class F> __device__ __forceinline__ void rs_with_tables(StepArgsPtr Ac, F f) {
-    const StepArgs *A = (const StepArgs *)Ac;
-    if constexpr (CAP != 0) { const LdsFix<CAP> Lf(A->L); f(A->T, Lf, A->G); }
-    else f(A->T, A->L, A->G);
-}
-// REGS only separates the instantiations by the register budget of the kernel that calls them (64 / 80 / 128 VGPRs)
-template <int CAP, int REGS> __device__ __attribute__((noinline)) void rs_fn_plan_long(StepArgsPtr Ac, uint32_t seed, float sigma, int genv, int env, int t, uint32_t tag, int s) {
-    Ac = rs_uni(Ac); seed = rs_uni(seed); sigma = rs_uni(sigma); genv = rs_uni(genv); env = rs_uni(env); t = rs_uni(t); tag = rs_uni(tag);
-    rs_with_tables<CAP>(Ac, [&](const KTab &T, const auto &L, const State &G) {
-        KParams P{};
-        P.seed = seed; P.sigma = sigma;
-        const int C = CAP ? CAP : T.capacity;
-        phase_plan<true>(T, L, Grid{(uint16_t *)L.grid, tag}, G, (size_t)env * C, P, genv, t, s);
-    });
-}
-template <int CAP, int REGS> __device__ __attribute__((noinline)) void rs_fn_lc_decide(StepArgsPtr Ac, int env, int t, uint32_t tag, int s) {
-    Ac = rs_uni(Ac); env = rs_uni(env); t = rs_uni(t); tag = rs_uni(tag);
-    rs_with_tables<CAP>(Ac, [&](const KTab &T, const auto &L, const State &G) {
-        const int C = CAP ? CAP : T.capacity;
-        lc_decide_and_flag(T, L, Grid{(uint16_t *)L.grid, tag}, G, (size_t)env * C, t, s);
-    });
-}
-template <int CAP, int REGS> __device__ __attribute__((noinline)) uint32_t rs_fn_move_long(StepArgsPtr Ac, uint32_t out_mask, int env, int t, uint32_t tag, int flags, int s) {
-    Ac = rs_uni(Ac); out_mask = rs_uni(out_mask); env = rs_uni(env); t = rs_uni(t); tag = rs_uni(tag); flags = rs_uni(flags);
-    int active = 0, halted = 0, top = 0;
-    rs_with_tables<CAP>(Ac, [&](const KTab &T, const auto &L, const State &G) {
-        KParams P{};
-        P.out_mask = out_mask;
-        const int C = CAP ? CAP : T.capacity;
-        phase_move<true>(T, L, Grid{(uint16_t *)L.grid, tag}, G, P, env, (size_t)env * C, t, (flags & 1) != 0, (flags & 2) != 0, s, active, halted, top);
-    });
-    return (uint32_t)active | ((uint32_t)halted << 1) | ((uint32_t)top << 2);
-}
-
 // grid = n_envs workgroups (one environment each); blockDim.x = 64 * waves (<= 1024), normally one thread per slot.
 // PROF: the build with the in-kernel timers (rs_phase_profile); the production kernels carry none of that code
-template <bool PROF, int CAP, int REGS> struct DevExec {
+template <bool PROF> struct DevExec {
     int B;
     int wave;                       // threadIdx.x / 64, wave-uniform: lives in a scalar register
     unsigned long long *prof;       // optional per-phase timers (rs_phase_profile)
     unsigned long long t0;
-    StepArgsPtr Ac;
     template <class F> __device__ __forceinline__ void phase(int id, F f) {
         // The thread index is RECOMPUTED per phase from the wave's index (a scalar) and the lane's position in the wave (two VALU
         // instructions): kept in a register across the kernel it costs a VGPR the 64-VGPR build does not have (it lived in scratch
@@ -212,123 +160,47 @@ template <bool PROF, int CAP, int REGS> struct DevExec {
 #endif
         if (PROF && prof && (threadIdx.x & 63) == 0 && (blockIdx.x & 15) == 0) atomicAdd(&prof[id], (wall_clock64() - start) + (1ull << 40));   // (every 16th environment: the sum stays below 2^40)
     }
-    // the long code paths: called (production kernels) or inlined (the profiling kernel, whose section timers live inside them)
-    template <class LT> __device__ __forceinline__ void plan_long(const KTab &T, const LT &L, const Grid &grid, const State &G, size_t eo, const KParams &P, int genv, int env, int t, int s) const {
-#ifdef RS_CALL_LONG
-        if constexpr (!PROF) { rs_fn_plan_long<CAP, REGS>(Ac, P.seed, P.sigma, genv, env, t, grid.tag, s); return; }
-#endif
-        phase_plan<true>(T, L, grid, G, eo, P, genv, t, s);
-    }
-    template <class LT> __device__ __forceinline__ void lc_decide(const KTab &T, const LT &L, const Grid &grid, const State &G, size_t eo, int env, int t, int s) const {
-#ifdef RS_CALL_LONG
-        if constexpr (!PROF) { rs_fn_lc_decide<CAP, REGS>(Ac, env, t, grid.tag, s); return; }
-#endif
-        lc_decide_and_flag(T, L, grid, G, eo, t, s);
-    }
-    template <class LT> __device__ __forceinline__ void move_long(const KTab &T, const LT &L, const Grid &gnew, const State &G, const KParams &P, int env, size_t eo, int t, bool last_tick,
-                                                                  bool more, int s, int &active, int &halted, int &top) const {
-#ifdef RS_CALL_LONG
-        if constexpr (!PROF) { move_unpack(rs_fn_move_long<CAP, REGS>(Ac, P.out_mask, env, t, gnew.tag, (last_tick ? 1 : 0) | (more ? 2 : 0), s), active, halted, top); return; }
-#endif
-        phase_move<true>(T, L, gnew, G, P, env, eo, t, last_tick, more, s, active, halted, top);
-    }
 };
 // Register budgets: 64 VGPRs (eight waves per SIMD: FOUR 512-thread workgroups per CU -- the default where the working memory of an
 // environment fits four times, round 6) and 80 VGPRs (three 512-thread workgroups per CU; `_v128` is the same code under a third
 // launch bound); CAP = the slot capacity as a compile-time constant (0: any).
-template <int CAP, bool PROF, int REGS> __device__ __forceinline__ void rs_step_kernel_body(StepArgsPtr Ac, const KParams &P, const int32_t *__restrict__ actions) {
+template <int CAP, bool PROF> __device__ __forceinline__ void rs_step_kernel_body(StepArgsPtr Ac, const KParams &P, const int32_t *__restrict__ actions) {
     if ((int)blockIdx.x >= P.n_envs) return;
     const StepArgs *A = (const StepArgs *)Ac;
 #ifdef RS_STUDY_SECTIONS
     if (threadIdx.x == 0) g_sec_prof = P.prof;
 #endif
-    DevExec<PROF, CAP, REGS> ex{(int)blockDim.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), PROF ? P.prof : nullptr, (PROF && P.prof) ? wall_clock64() : 0ull, Ac};
+    DevExec<PROF> ex{(int)blockDim.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), PROF ? P.prof : nullptr, (PROF && P.prof) ? wall_clock64() : 0ull};
     rs_step_body<CAP>(ex, A->L, A->T, A->G, A->O, P, actions, (int)blockIdx.x);
 }
 template <int CAP>
 __global__ void __launch_bounds__(1024, 8)
-rs_step_kernel_v64(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false, 64>(Ac, P, actions); }
+rs_step_kernel_v64(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false>(Ac, P, actions); }
 template <int CAP>
 __global__ void __launch_bounds__(768, 6)
-rs_step_kernel_v80(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false, 80>(Ac, P, actions); }
+rs_step_kernel_v80(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false>(Ac, P, actions); }
 template <int CAP>
 __global__ void __launch_bounds__(512, 4)
-rs_step_kernel_v128(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false, 128>(Ac, P, actions); }
+rs_step_kernel_v128(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false>(Ac, P, actions); }
 // the profiling build (rs_phase_profile / RS_STUDY_SECTIONS): any capacity, 80 VGPRs
 __global__ void __launch_bounds__(768, 6)
-rs_step_kernel_prof(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<0, true, 80>(Ac, P, actions); }
+rs_step_kernel_prof(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<0, true>(Ac, P, actions); }
 
-// reset every environment: no vehicles, every backlog at its first trip, TLS programs freshly installed
-// (Signal.__init__, traffic_signal.py:93-100)
-__global__ void rs_reset_kernel(KTab T, State G, KParams P) {
-    const int env = blockIdx.x;
-    const int C = T.capacity, S = T.n_signals;
-    const size_t eo = (size_t)env * C;
-    for (int s = threadIdx.x; s < C; s += blockDim.x) {
-        G.lane()[eo + s] = LANE_NONE; G.trip()[eo + s] = TRIP_NONE; G.owner()[eo + s] = OWNER_NONE;
-        G.rwait()[eo + s] = 0; G.swait()[eo + s] = 0; G.cursor()[eo + s] = 0; G.depart()[eo + s] = 0; G.wtot()[eo + s] = 0;
-        G.pos()[eo + s] = 0.0f; G.speed()[eo + s] = 0.0f; G.accel()[eo + s] = 0.0f; G.tloss()[eo + s] = 0.0f; G.sf()[eo + s] = 1.0f;
-        G.coop(0)[eo + s] = COOP_NONE; G.coop(1)[eo + s] = COOP_NONE; G.cooplead(0)[eo + s] = COOP_NONE; G.cooplead(1)[eo + s] = COOP_NONE;
-    }
-    for (int s = threadIdx.x; s < S; s += blockDim.x) {
-        int ph, left;
-        if (P.fixed_program) { ph = T.cold.fix_init_phase[s]; left = T.cold.fix_init_left[s]; }
-        else { ph = T.cold.tls_init_phase[s]; left = T.cold.tls_dur[T.cold.tls_dur_off[s] + ph]; }
-        G.tls[(env * S + s) * TLS_W + 0] = ph; G.tls[(env * S + s) * TLS_W + 1] = left; G.tls[(env * S + s) * TLS_W + 2] = 0; G.tls[(env * S + s) * TLS_W + 3] = 0;
-    }
-    for (int d = threadIdx.x; d < T.n_dep; d += blockDim.x) G.dep_next[(size_t)env * T.n_dep + d] = T.cold.dep_first[d];
-    for (int i = threadIdx.x; i < (C + 31) / 32; i += blockDim.x) G.mail[(size_t)env * ((C + 31) / 32) + i] = 0u;
-    if (threadIdx.x < 4) G.env[env * 4 + threadIdx.x] = 0;
-    if (threadIdx.x < ST_N) G.stats[(size_t)env * ST_N + threadIdx.x] = 0;
-    if (G.trip_log)
-        for (int i = threadIdx.x; i < T.n_trips * 4; i += blockDim.x) G.trip_log[(size_t)env * T.n_trips * 4 + i] = 0;
-}
-
-// fresh Signal objects on the running simulation (rs_reinit_signals)
-__global__ void rs_reinit_kernel(KTab T, State G, KParams P) {
-    const int env = blockIdx.x;
-    const int C = T.capacity, S = T.n_signals;
-    const size_t eo = (size_t)env * C;
-    for (int s = threadIdx.x; s < C; s += blockDim.x) { G.owner()[eo + s] = OWNER_NONE; G.rwait()[eo + s] = 0; }
-    for (int s = threadIdx.x; s < S; s += blockDim.x) {
-        if (!P.fixed_program) G.tls[(env * S + s) * TLS_W + 1] = T.cold.tls_dur[T.cold.tls_dur_off[s] + G.tls[(env * S + s) * TLS_W + 0]];
-        G.tls[(env * S + s) * TLS_W + 2] = 0; G.tls[(env * S + s) * TLS_W + 3] = 0;
-    }
-}
-
-// ---- static agents
-// STOCHASTIC (agents/stochastic.py:17-18): uniform green index per (env, signal, step)
+// reset / fresh Signal objects / the static agents: the bodies are in resco_host.h (shared with the host emulation)
+__global__ void rs_reset_kernel(KTab T, State G, KParams P) { rs_reset_env(T, G, P, (int)blockIdx.x, (int)threadIdx.x, blockDim.x); }
+__global__ void rs_reinit_kernel(KTab T, State G, KParams P) { rs_reinit_env(T, G, P, (int)blockIdx.x, (int)threadIdx.x, blockDim.x); }
 __global__ void rs_act_random_kernel(KTab T, KParams P, uint32_t step_key, int32_t *actions) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int S = T.n_signals;
-    if (i >= P.n_envs * S) return;
-    const int env = i / S, s = i - env * S;
-    const uint32_t h = d_hash(P.seed ^ 0xA5A5A5A5u, (uint32_t)(P.env_base + env), (uint32_t)s, step_key, 7u);
-    actions[i] = (int32_t)(h % (uint32_t)T.cold.tls_ngreen[s]);
+    if (i < P.n_envs * T.n_signals) actions[i] = rs_random_action(T, P, step_key, i);
 }
-// MAXWAVE / MAXPRESSURE (agents/maxwave.py:18-38, maxpressure.py:13-18): first maximum over the valid
-// phase pairs (in the reference's iteration order) of obs[pair0] + obs[pair1]
 __global__ void rs_act_maxwave_kernel(KTab T, KParams P, const int32_t *pairs, int n_pairs, const int32_t *valid, const int32_t *order,
                                       int use_pressure, const int32_t *mplight, const int32_t *wave, int32_t *actions) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int S = T.n_signals;
-    if (i >= P.n_envs * S) return;
-    const int s = i % S;
-    const int32_t *obs = use_pressure ? mplight + (size_t)i * 13 + 1 : wave + (size_t)i * 12;
-    bool have = false;
-    int best = 0, best_act = 0;
-    for (int j = 0; j < n_pairs; ++j) {
-        const int p = order[s * n_pairs + j];     // the reference walks valid_acts in dict order; ties keep the first
-        if (p < 0) break;
-        const int act = valid[s * n_pairs + p];
-        if (act < 0) continue;
-        const int press = obs[pairs[p * 2]] + obs[pairs[p * 2 + 1]];
-        if (!have || press > best) { have = true; best = press; best_act = act; }
-    }
-    actions[i] = best_act;
+    if (i < P.n_envs * T.n_signals) actions[i] = rs_maxwave_action(T, pairs, n_pairs, valid, order, use_pressure, mplight, wave, i);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+enum RegBudget { V64 = 0, V128 = 1, V80 = 2 };      // VGPRs of the step kernel a handle launches (the index step_kernel_for takes)
 struct rs_sim {
     int device = 0;
     int n_envs = 0, env_base = 0, block = 256;
@@ -336,7 +208,7 @@ struct rs_sim {
     size_t lds = 0;
     KTab K{};
     StepArgs *args = nullptr;      // device copy of {K, G, O}
-    int use_v128 = 0;
+    RegBudget budget = V64;
     State G{};
     Out O{};
     KParams P{};
@@ -348,8 +220,6 @@ struct rs_sim {
     hipStream_t stream = nullptr;
     hipStream_t last = nullptr;         // stream of the most recent launch: what the synchronous calls wait for
     std::vector<void *> allocs;
-    std::vector<int32_t> tls_ngreen;
-    struct Buf { void *ptr; int64_t shape[4]; int ndim; int dtype; size_t bytes; };
     Buf bufs[RS_BUF_COUNT]{};
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -390,22 +260,14 @@ static int dev_upload(rs_sim *h, const Tp **dst, const Tp *src, size_t count) {
     return RS_OK;
 }
 
-static const size_t kDtypeSize[] = {4, 4, 2, 1, 2, 8, 4};
-static void set_buf(rs_sim *h, int which, void *ptr, int dtype, int ndim, int64_t a, int64_t b = 1, int64_t c = 1, int64_t d = 1) {
-    auto &B = h->bufs[which];
-    B.ptr = ptr; B.dtype = dtype; B.ndim = ndim;
-    B.shape[0] = a; B.shape[1] = b; B.shape[2] = c; B.shape[3] = d;
-    B.bytes = (size_t)(a * b * c * d) * kDtypeSize[dtype];
-}
-
 typedef void (*step_kernel_fn)(StepArgsPtr, KParams, const int32_t *);
 static const int kStepCaps[] = {0, 128, 256, 512, 768, 896, 1024};
-// regs: 0 = 64 VGPRs (blocks up to 1024 threads), 1 = 128 VGPRs, 2 = 80 VGPRs (blocks up to 512 threads)
-#define RS_PICK(cap_) (regs == 1 ? rs_step_kernel_v128<cap_> : (regs == 2 ? rs_step_kernel_v80<cap_> : rs_step_kernel_v64<cap_>))
+// regs (a RegBudget): 64 VGPRs (blocks up to 1024 threads), 128 VGPRs (up to 512), 80 VGPRs (up to 768)
+#define RS_PICK(cap_) (regs == V128 ? rs_step_kernel_v128<cap_> : (regs == V80 ? rs_step_kernel_v80<cap_> : rs_step_kernel_v64<cap_>))
 static step_kernel_fn step_kernel_for(int regs, int capacity) {
 #ifdef RS_ONE_CAP       // study builds (seconds instead of minutes to compile): one capacity, the 64- and the 80-VGPR kernel only
     (void)capacity;
-    return regs == 0 ? rs_step_kernel_v64<RS_ONE_CAP> : rs_step_kernel_v80<RS_ONE_CAP>;
+    return regs == V64 ? rs_step_kernel_v64<RS_ONE_CAP> : rs_step_kernel_v80<RS_ONE_CAP>;
 #else
     switch (capacity) {
         case 128: return RS_PICK(128);
@@ -452,6 +314,24 @@ extern "C" int32_t rs_default_block(int32_t capacity, int32_t n_envs_on_device, 
     return -(20000 + 64 * waves);
 }
 
+// The block_threads argument of rs_create (include/resco_sim.h) as a register budget and a thread count; false: not a valid shape.
+// A positive value is that many threads (at most 1024) of the 64-VGPR build; a negative value selects the 128-VGPR build with |value|
+// threads (<= 512), -(10000 + threads) the 80-VGPR build (<= 768) -- tuning knobs; -(20000 + threads) is what
+// rs_default_block proposes.
+static bool decode_block(int block_threads, size_t lds, RegBudget *budget, int *threads) {
+    int t = block_threads;
+    RegBudget b = V64;
+    if (t <= -20000) {
+        // the shape rs_default_block proposes: the register budget follows from what fits a CU.  Where the working memory lets FOUR
+        // 512-thread workgroups share a CU they need eight waves per SIMD, i.e. the 64-VGPR build (ingolstadt21 with 896 slots:
+        // 40 768 B; +14 % env-steps/s over three workgroups of the 80-VGPR build, profiles/r06_ab_occupancy.txt); else 80 VGPRs
+        t = -t - 20000;
+        b = (t == 512 && lds <= RS_LDS_4WG_LIMIT) ? V64 : V80;
+    } else if (t < 0) { b = V128; t = -t; if (t >= 10000) { b = V80; t -= 10000; } }
+    *budget = b; *threads = t;
+    return t % 64 == 0 && t >= 64 && t <= (b == V128 ? 512 : (b == V80 ? 768 : 1024));
+}
+
 extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_envs, int32_t env_base, int32_t device_id,
                          int32_t block_threads, rs_handle *out) {
     if (!sc || !p || !out || n_envs <= 0) { g_create_err = "rs_create: bad argument"; return RS_EINVAL; }
@@ -470,56 +350,16 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
     if (C < 64 || (C % 64) || C > 1984) { h->err = "capacity must be a multiple of 64 in [64, 1984]"; return fail(RS_ELIMIT); }
     if (sc->kmax < 1 || sc->kmax > 16) { h->err = "kmax (lanes per edge) must be in [1, 16]"; return fail(RS_ELIMIT); }
     PackedTables PT;
-    {   // grid cell length: build once to learn the sizes that do not depend on it, choose, build for good
-        PackedTables probe;
-        if (!probe.build(sc)) { h->err = probe.err; return fail(RS_ELIMIT); }
-        if (!PT.build(sc, pick_cell_len(sc, probe.n_arr, probe.n_dep, probe.tls_maxl))) { h->err = PT.err; return fail(RS_ELIMIT); }
-    }
-    h->tls_ngreen.assign(sc->tls_ngreen, sc->tls_ngreen + sc->n_signals);
+    if (const char *msg = rs_pack_tables(PT, sc)) { h->err = msg; return fail(RS_ELIMIT); }
     int rc;
-    KTab &K = h->K;
-    {
-        KCold &cold = K.cold;
 #define UP(dst, type, src, count) if ((rc = dev_upload<type>(h, &dst, src, (size_t)(count)))) return fail(rc);
-        UP(K.lanes_, LaneRec, PT.lanes.data(), PT.lanes.size()) UP(K.links_, LinkRec, PT.links.data(), PT.links.size())
-        UP(K.foes_, FoeRec, PT.foes.data(), PT.foes.size()) UP(K.rsteps_, RStep, PT.rsteps.data(), PT.rsteps.size())
-        UP(K.routes_, RouteRec, PT.routes.data(), PT.routes.size()) UP(K.next_link_, uint16_t, PT.next_link.data(), PT.next_link.size())
-        UP(K.trip_route_, uint16_t, PT.trip_route.data(), PT.trip_route.size()) UP(K.trip_vtype_, uint8_t, PT.trip_vtype.data(), PT.trip_vtype.size())
-        UP(K.route_cont_, float, PT.route_cont.data(), PT.route_cont.size()) UP(K.notbest_, uint16_t, PT.notbest.data(), PT.notbest.size())
-        UP(cold.trip_depart, int32_t, sc->trip_depart, sc->n_trips) UP(cold.trip_next, uint16_t, PT.trip_next.data(), PT.trip_next.size())
-        UP(cold.dep_lane, uint16_t, PT.dep_lane.data(), PT.dep_lane.size()) UP(cold.dep_info, DepInfo, PT.dep_info.data(), PT.dep_info.size()) UP(cold.dep_first, uint16_t, PT.dep_first.data(), PT.dep_first.size())
-        UP(cold.vtype_params, float, sc->vtype_params, sc->n_vtypes * VT_COLS)
-        UP(cold.tls8, uint8_t, PT.tls8.data(), PT.tls8.size()) UP(cold.fix8, uint8_t, PT.fix8.data(), PT.fix8.size())
-        UP(cold.tls_nphase, int32_t, sc->tls_nphase, sc->n_signals) UP(cold.tls_ngreen, int32_t, sc->tls_ngreen, sc->n_signals)
-        UP(cold.tls_nlinks, int32_t, sc->tls_nlinks, sc->n_signals) UP(cold.tls_state_off, int32_t, PT.tls_off_p.data(), sc->n_signals)
-        UP(cold.tls_dur_off, int32_t, sc->tls_dur_off, sc->n_signals) UP(cold.tls_yel_off, int32_t, sc->tls_yel_off, sc->n_signals)
-        UP(cold.tls_dur, int32_t, sc->tls_dur, sc->n_tls_dur) UP(cold.tls_yellow, int32_t, sc->tls_yellow, sc->n_tls_yellow)
-        UP(cold.tls_init_phase, int32_t, sc->tls_init_phase, sc->n_signals)
-        UP(cold.fix_nphase, int32_t, sc->fix_nphase, sc->n_signals) UP(cold.fix_state_off, int32_t, PT.fix_off_p.data(), sc->n_signals)
-        UP(cold.fix_dur_off, int32_t, sc->fix_dur_off, sc->n_signals) UP(cold.fix_dur, int32_t, sc->fix_dur, sc->n_fix_dur)
-        UP(cold.fix_init_phase, int32_t, sc->fix_init_phase, sc->n_signals) UP(cold.fix_init_left, int32_t, sc->fix_init_left, sc->n_signals)
-        UP(cold.lane_obs, int16_t, PT.lane_obs16.data(), PT.lane_obs16.size()) UP(cold.obs_sig, int32_t, PT.obs_sig.data(), PT.obs_sig.size())
-        UP(cold.sig_obs_start, int32_t, sc->sig_obs_start, sc->n_signals + 1)
-        UP(cold.mv_in_start, int32_t, sc->mv_in_start, sc->n_signals * 12 + 1) UP(cold.mv_in_idx, int32_t, sc->mv_in_idx, sc->n_mv_in)
-        UP(cold.mv_out_start, int32_t, sc->mv_out_start, sc->n_signals * 12 + 1) UP(cold.mv_out_idx, int32_t, sc->mv_out_idx, sc->n_mv_out)
-        UP(cold.pr_out_start, int32_t, sc->pr_out_start, sc->n_signals + 1) UP(cold.pr_out_idx, int32_t, sc->pr_out_idx, sc->n_pr_out)
-        UP(cold.trips_cum, int32_t, sc->trips_cum, sc->horizon + 2)
+    RS_KTAB_TABLES(UP, h->K, PT, sc)
 #undef UP
-        K.maxlen = PT.maxlen; K.occ_unit = PT.occ_unit;
-        K.n_trips = sc->n_trips; K.tls_maxl = PT.tls_maxl; K.kmax = sc->kmax;
-        K.n_lanes = sc->n_lanes; K.n_cells = PT.n_cells; K.n_signals = sc->n_signals; K.n_obs = sc->n_obs; K.n_vtypes = sc->n_vtypes;
-        h->ratio = p->step_ratio > 1 ? p->step_ratio : 1;
-        // the kernel counts ticks: Signal.set_phase comes after yellow_length x step_ratio of them (multi_signal.py:102-105, 175-180);
-        // step_length stays what Signal.observe adds to a waiting time (traffic_signal.py:196)
-        K.horizon = sc->horizon; K.capacity = C; K.step_length = sc->step_length; K.yellow_length = sc->yellow_length * h->ratio; K.lmax = PT.lmax;
-        K.n_arr = PT.n_arr; K.n_dep = PT.n_dep;
-    }
+    h->ratio = rs_step_ratio(p);
+    rs_ktab_scalars(h->K, PT, sc, h->ratio);
     const int lmax = PT.lmax;
-
-    h->P.seed = p->seed; h->P.env_base = env_base; h->P.max_distance = p->max_distance; h->P.sigma = p->sigma;
-    h->P.speed_dev = p->speed_dev; h->P.fixed_program = p->fixed_program; h->P.tls_expiry = p->tls_hold == 0; h->P.n_envs = n_envs;
-
-    const size_t N = (size_t)n_envs, NC = N * C, S = (size_t)sc->n_signals, NO = (size_t)sc->n_obs;
+    h->P = rs_kparams(p, env_base, n_envs);
+    const size_t N = (size_t)n_envs, NC = N * C, S = (size_t)sc->n_signals;
     State &G = h->G;
     Out &O = h->O;
     {
@@ -532,64 +372,16 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
             (rc = dev_alloc(h, &h->actions, N * S)))
             return fail(rc);
         G.base = slab; O.base = outb;
-        (void)NO;
     }
-    const int64_t n = n_envs, c = C, s = sc->n_signals, o = sc->n_obs;
-    set_buf(h, RS_BUF_LANE_AGG, O.lane_agg(), RS_F32, 3, n, o, 5);
-    set_buf(h, RS_BUF_DRQ_NORM, O.drq_norm(), RS_F32, 3, n, o, 5);
-    set_buf(h, RS_BUF_PHASE, O.phase(), RS_I32, 2, n, s);
-    set_buf(h, RS_BUF_MPLIGHT, O.mplight(), RS_I32, 3, n, s, 13);
-    set_buf(h, RS_BUF_WAVE, O.wave(), RS_I32, 3, n, s, 12);
-    set_buf(h, RS_BUF_WAIT, O.wait(), RS_F32, 2, n, s);
-    set_buf(h, RS_BUF_WAIT_NORM, O.wait_norm(), RS_F32, 2, n, s);
-    set_buf(h, RS_BUF_PRESSURE, O.pressure(), RS_I32, 2, n, s);
-    set_buf(h, RS_BUF_QUEUE_SUM, O.queue_sum(), RS_I32, 2, n, s);
-    set_buf(h, RS_BUF_QUEUE_MAX, O.queue_max(), RS_I32, 2, n, s);
-    set_buf(h, RS_BUF_ACTIONS, h->actions, RS_I32, 2, n, s);
-    set_buf(h, RS_BUF_ENV, G.env, RS_I32, 2, n, 4);
-    set_buf(h, RS_BUF_TLS, G.tls, RS_I32, 3, n, s, TLS_W);
-    set_buf(h, RS_BUF_VEH_POS, G.pos(), RS_F32, 2, n, c);
-    set_buf(h, RS_BUF_VEH_SPEED, G.speed(), RS_F32, 2, n, c);
-    set_buf(h, RS_BUF_VEH_ACCEL, G.accel(), RS_F32, 2, n, c);
-    set_buf(h, RS_BUF_VEH_TLOSS, G.tloss(), RS_F32, 2, n, c);
-    set_buf(h, RS_BUF_VEH_LANE, G.lane(), RS_U16, 2, n, c);
-    set_buf(h, RS_BUF_VEH_TRIP, G.trip(), RS_U16, 2, n, c);
-    set_buf(h, RS_BUF_VEH_CURSOR, G.cursor(), RS_U16, 2, n, c);
-    set_buf(h, RS_BUF_VEH_SWAIT, G.swait(), RS_U16, 2, n, c);
-    set_buf(h, RS_BUF_VEH_RWAIT, G.rwait(), RS_U16, 2, n, c);
-    set_buf(h, RS_BUF_VEH_DEPART, G.depart(), RS_U16, 2, n, c);
-    set_buf(h, RS_BUF_VEH_OWNER, G.owner(), RS_U8, 2, n, c);
-    set_buf(h, RS_BUF_STATS, G.stats, RS_I64, 2, n, ST_N);
-    set_buf(h, RS_BUF_DRQ_NORM_F16, O.drq_f16(), RS_F16, 4, n, s, lmax, 5);
-    set_buf(h, RS_BUF_VEH_SF, G.sf(), RS_F32, 2, n, c);
-    set_buf(h, RS_BUF_VEH_WTOT, G.wtot(), RS_U16, 2, n, c);
     G.trip_log = nullptr;
     if (p->trip_log && (rc = dev_alloc(h, &G.trip_log, N * (size_t)sc->n_trips * 4))) return fail(rc);
-    set_buf(h, RS_BUF_TRIP_LOG, G.trip_log, RS_I32, 3, n, p->trip_log ? sc->n_trips : 0, 4);
-    set_buf(h, RS_BUF_DEP_NEXT, G.dep_next, RS_U16, 2, n, h->K.n_dep);
-    set_buf(h, RS_BUF_VEH_COOP, G.coop(0), RS_U32, 2, n, c);
-    set_buf(h, RS_BUF_VEH_COOPLEAD, G.cooplead(0), RS_U32, 2, n, c);
-    set_buf(h, RS_BUF_ARRIVALS, O.arrivals(), RS_I32, 2, n, s);
-    set_buf(h, RS_BUF_DEPARTURES, O.departures(), RS_I32, 2, n, s);
-    set_buf(h, RS_BUF_MPLIGHT_FULL, O.mplight_full(), RS_F32, 3, n, s, 49);
-    set_buf(h, RS_BUF_LANE_ARRIVALS, O.lane_arr(), RS_I32, 2, n, sc->n_obs);
-    set_buf(h, RS_BUF_VEH_COOP_ODD, G.coop(1), RS_U32, 2, n, c); set_buf(h, RS_BUF_VEH_COOPLEAD_ODD, G.cooplead(1), RS_U32, 2, n, c);
-    set_buf(h, RS_BUF_VEH_MAIL, G.mail, RS_U32, 2, n, (C + 31) / 32);
+    rs_fill_bufs(h->bufs, G, O, h->actions, BufDims{n_envs, C, sc->n_signals, sc->n_obs, lmax, h->K.n_dep, p->trip_log ? sc->n_trips : 0});
 
     h->lds = lds_carve(nullptr, C, h->K.n_cells, h->K.n_arr, h->K.n_dep, sc->n_obs, sc->n_signals, sc->n_vtypes, h->K.tls_maxl);
     if (const char *pad = getenv("RESCO_STUDY_LDS_PAD")) h->lds += (size_t)atoi(pad);      // study knob: unused bytes, to hold the residency fixed in an A/B
     if (h->lds > 160 * 1024) { h->err = "scenario needs more than 160 KiB of LDS per environment"; return fail(RS_ELIMIT); }
-    // block_threads: 0 = one thread per slot (at most 1024); a negative value selects the 128-VGPR build with |value|
-    // threads (<= 512), -(10000 + threads) the 80-VGPR build -- tuning knobs, see DESIGN.md
     if (block_threads == 0) block_threads = rs_default_block(C, n_envs, device_id);
-    if (block_threads <= -20000) {
-        // the shape rs_default_block proposes: the register budget follows from what fits a CU.  Where the working memory lets FOUR
-        // 512-thread workgroups share a CU they need eight waves per SIMD, i.e. the 64-VGPR build (ingolstadt21 with 896 slots:
-        // 40 768 B; +14 % env-steps/s over three workgroups of the 80-VGPR build, profiles/r06_ab_occupancy.txt); else 80 VGPRs
-        block_threads = -block_threads - 20000;
-        h->use_v128 = (block_threads == 512 && h->lds <= RS_LDS_4WG_LIMIT) ? 0 : 2;
-    } else if (block_threads < 0) { h->use_v128 = 1; block_threads = -block_threads; if (block_threads >= 10000) { h->use_v128 = 2; block_threads -= 10000; } }
-    if (block_threads % 64 || block_threads > (h->use_v128 == 1 ? 512 : (h->use_v128 == 2 ? 768 : 1024)) || block_threads < 64) {
+    if (!decode_block(block_threads, h->lds, &h->budget, &block_threads)) {
         h->err = "block_threads must be a multiple of 64 in [64, 1024] ([64, 768] for the 80-VGPR build, [64, 512] for the 128-VGPR build)";
         return fail(RS_EINVAL);
     }
@@ -602,7 +394,7 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
         std::lock_guard<std::mutex> lock(mu);
         size_t &cur = max_lds[device_id & 63];
         if (h->lds > cur) {
-            for (int v = 0; v < 3; ++v)
+            for (int v = V64; v <= V80; ++v)
                 for (int cp : kStepCaps)        // every instantiation: the ceiling is per kernel function
                     if (hipFuncSetAttribute((const void *)step_kernel_for(v, cp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess) {
                         h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return fail(RS_EHIP);
@@ -667,46 +459,41 @@ static int launch_step(rs_sim *h, hipStream_t st, int n_ticks, int do_fsm, int d
         HIPCHK(h, hipEventRecord(e0, st));
     }
     // (the in-kernel timers live in a kernel of their own: any capacity, 80 VGPRs, at most 768 threads)
-    const step_kernel_fn fn = (h->prof && h->block <= 768) ? (step_kernel_fn)rs_step_kernel_prof : step_kernel_for(h->use_v128, h->K.capacity);
+    const step_kernel_fn fn = (h->prof && h->block <= 768) ? (step_kernel_fn)rs_step_kernel_prof : step_kernel_for(h->budget, h->K.capacity);
     hipLaunchKernelGGL(fn, dim3(h->n_envs), dim3(h->block), h->lds, st, (StepArgsPtr)h->args, P, (const int32_t *)h->actions);
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(e1, st));
     return RS_OK;
 }
 
-extern "C" int rs_reset(rs_handle h, void *stream) {
+// what every launching entry point begins with: the handle's device, and the stream of this launch (the caller's, or the handle's own)
+static int enter(rs_sim *h, void *stream, hipStream_t *st) {
     if (!h) return RS_EINVAL;
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    h->last = st;
-    hipLaunchKernelGGL(rs_reset_kernel, dim3(h->n_envs), dim3(256), 0, st, h->K, h->G, h->P);
-    HIPCHK(h, hipGetLastError());
-    bool tm = h->timing;
-    h->timing = false;
-    int rc = launch_step(h, st, 0, 0);
-    h->timing = tm;
-    return rc;
+    *st = stream ? (hipStream_t)stream : h->stream;
+    h->last = *st;
+    return RS_OK;
 }
 
-extern "C" int rs_reinit_signals(rs_handle h, void *stream) {
-    if (!h) return RS_EINVAL;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    h->last = st;
-    hipLaunchKernelGGL(rs_reinit_kernel, dim3(h->n_envs), dim3(256), 0, st, h->K, h->G, h->P);
+// rs_reset / rs_reinit_signals: the kernel over the environments, then an untimed observe (of the new Signal objects)
+static int launch_reset(rs_sim *h, void *stream, void (*kernel)(KTab, State, KParams)) {
+    hipStream_t st;
+    int rc = enter(h, stream, &st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, dim3(h->n_envs), dim3(256), 0, st, h->K, h->G, h->P);
     HIPCHK(h, hipGetLastError());
     bool tm = h->timing;
     h->timing = false;
-    int rc = launch_step(h, st, 0, 0);      // the first observe of the new Signal objects
+    rc = launch_step(h, st, 0, 0);
     h->timing = tm;
     return rc;
 }
+extern "C" int rs_reset(rs_handle h, void *stream) { return launch_reset(h, stream, rs_reset_kernel); }
+extern "C" int rs_reinit_signals(rs_handle h, void *stream) { return launch_reset(h, stream, rs_reinit_kernel); }
 
 extern "C" int rs_step(rs_handle h, const int32_t *actions, int32_t actions_on_device, void *stream) {
-    if (!h) return RS_EINVAL;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    h->last = st;
+    hipStream_t st;
+    if (int rc = enter(h, stream, &st)) return rc;
     if (actions) {
         size_t bytes = (size_t)h->n_envs * h->K.n_signals * sizeof(int32_t);
         HIPCHK(h, hipMemcpyAsync(h->actions, actions, bytes, actions_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
@@ -717,34 +504,23 @@ extern "C" int rs_step(rs_handle h, const int32_t *actions, int32_t actions_on_d
 }
 
 extern "C" int rs_ticks(rs_handle h, int32_t n_ticks, void *stream) {
-    if (!h || n_ticks < 0) return RS_EINVAL;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    h->last = st;
+    hipStream_t st;
+    if (n_ticks < 0) return RS_EINVAL;
+    if (int rc = enter(h, stream, &st)) return rc;
     return launch_step(h, st, n_ticks, 0);
 }
 
 extern "C" int rs_step_sim(rs_handle h, int32_t n_ticks, void *stream) {
-    if (!h || n_ticks < 0) return RS_EINVAL;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    h->last = st;
+    hipStream_t st;
+    if (n_ticks < 0) return RS_EINVAL;
+    if (int rc = enter(h, stream, &st)) return rc;
     return launch_step(h, st, n_ticks, 0, 0);
 }
 
 // which output buffers the observe of the following launches writes (bit b = buffer id b); the others keep their contents
 extern "C" int rs_set_outputs(rs_handle h, uint64_t buffer_mask) {
     if (!h) return RS_EINVAL;
-    uint32_t m = 0;
-    if (buffer_mask & (1ull << RS_BUF_LANE_AGG)) m |= OUT_LANE_AGG;
-    if (buffer_mask & (1ull << RS_BUF_DRQ_NORM)) m |= OUT_DRQ_NORM;
-    if (buffer_mask & (1ull << RS_BUF_DRQ_NORM_F16)) m |= OUT_DRQ_F16;
-    if (buffer_mask & (1ull << RS_BUF_LANE_ARRIVALS)) m |= OUT_LANE_ARR;
-    if (buffer_mask & (1ull << RS_BUF_MPLIGHT)) m |= OUT_MPLIGHT;
-    if (buffer_mask & (1ull << RS_BUF_WAVE)) m |= OUT_WAVE;
-    if (buffer_mask & (1ull << RS_BUF_MPLIGHT_FULL)) m |= OUT_MPLIGHT_FULL;
-    if (buffer_mask & (1ull << RS_BUF_VEH_ACCEL)) m |= OUT_VEH_ACCEL;
-    h->out_mask = m;
+    h->out_mask = rs_out_mask(buffer_mask);
     return RS_OK;
 }
 
@@ -755,13 +531,22 @@ extern "C" int rs_sync(rs_handle h) {
     return RS_OK;
 }
 
-extern "C" int rs_act_random(rs_handle h, uint32_t step_key, void *stream) {
-    if (!h) return RS_EINVAL;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    h->last = st;
-    int total = h->n_envs * h->K.n_signals;
+// ---- the agents' launches: one function each, for the single call and for rs_group_step (the caller checks hipGetLastError)
+static void launch_random(rs_sim *h, hipStream_t st, uint32_t step_key) {
+    const int total = h->n_envs * h->K.n_signals;
     hipLaunchKernelGGL(rs_act_random_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->K, h->P, step_key, h->actions);
+}
+static void launch_maxwave(rs_sim *h, hipStream_t st, int use_pressure) {
+    const int total = h->n_envs * h->K.n_signals;
+    hipLaunchKernelGGL(rs_act_maxwave_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->K, h->P, (const int32_t *)h->pairs,
+                       h->n_pairs, (const int32_t *)h->valid, (const int32_t *)h->order, use_pressure, (const int32_t *)h->O.mplight(),
+                       (const int32_t *)h->O.wave(), h->actions);
+}
+
+extern "C" int rs_act_random(rs_handle h, uint32_t step_key, void *stream) {
+    hipStream_t st;
+    if (int rc = enter(h, stream, &st)) return rc;
+    launch_random(h, st, step_key);
     HIPCHK(h, hipGetLastError());
     return RS_OK;
 }
@@ -776,9 +561,8 @@ extern "C" int rs_act_maxwave(rs_handle h, const int32_t *phase_pairs, int32_t n
                               : "rs_act_maxwave(use_pressure=0) reads RS_BUF_WAVE, which rs_set_outputs has switched off";
         return RS_EINVAL;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    h->last = st;
+    hipStream_t st;
+    if (int rc = enter(h, stream, &st)) return rc;
     if (!h->pairs) {
         if (!phase_pairs || !valid || !order) { h->err = "rs_act_maxwave: tables required on first use"; return RS_EINVAL; }
         int rc;
@@ -789,21 +573,14 @@ extern "C" int rs_act_maxwave(rs_handle h, const int32_t *phase_pairs, int32_t n
         HIPCHK(h, hipMemcpy(h->valid, valid, (size_t)h->K.n_signals * n_pairs * 4, hipMemcpyHostToDevice));
         h->n_pairs = n_pairs;
     }
-    int total = h->n_envs * h->K.n_signals;
-    hipLaunchKernelGGL(rs_act_maxwave_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->K, h->P, (const int32_t *)h->pairs,
-                       h->n_pairs, (const int32_t *)h->valid, (const int32_t *)h->order, (int)use_pressure, (const int32_t *)h->O.mplight(),
-                       (const int32_t *)h->O.wave(), h->actions);
+    launch_maxwave(h, st, (int)use_pressure);
     HIPCHK(h, hipGetLastError());
     return RS_OK;
 }
 
 extern "C" int rs_get_buffer(rs_handle h, int32_t which, void **dev_ptr, int64_t shape[4], int32_t *ndim, int32_t *dtype) {
     if (!h || which < 0 || which >= RS_BUF_COUNT) return RS_EINVAL;
-    auto &B = h->bufs[which];
-    if (dev_ptr) *dev_ptr = B.ptr;
-    if (shape) for (int i = 0; i < 4; ++i) shape[i] = B.shape[i];
-    if (ndim) *ndim = B.ndim;
-    if (dtype) *dtype = B.dtype;
+    rs_buf_describe(h->bufs[which], dev_ptr, shape, ndim, dtype);
     return RS_OK;
 }
 
@@ -904,10 +681,7 @@ extern "C" int rs_set_seed(rs_handle h, uint32_t seed) {
 
 extern "C" int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal) {
     if (!h) return RS_EINVAL;
-    if (n_envs) *n_envs = h->n_envs;
-    if (block_threads) *block_threads = h->block;
-    if (lds_bytes) *lds_bytes = (int32_t)h->lds;
-    if (max_lanes_per_signal) *max_lanes_per_signal = h->K.lmax;
+    rs_info_describe(h->n_envs, h->block, h->lds, h->K.lmax, n_envs, block_threads, lds_bytes, max_lanes_per_signal);
     return RS_OK;
 }
 
@@ -922,6 +696,31 @@ struct rs_policy {
     std::vector<void *> allocs;
 };
 
+// what the two rs_*_create functions begin with: the result cleared, the number of visible devices
+static int policy_devices(rs_policy_handle *out, int *ndev) {
+    if (!out) return RS_EINVAL;
+    *out = nullptr;
+    if (hipGetDeviceCount(ndev) != hipSuccess || *ndev <= 0) { g_create_err = "no HIP device visible (this library has no CPU fallback)"; return RS_EHIP; }
+    return RS_OK;
+}
+// ... and what they do once the arguments are checked: an empty policy of `kind` on the device, which is made current
+static int policy_new(int device_id, int kind, rs_policy **p) {
+    if (hipSetDevice(device_id) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RS_EHIP; }
+    *p = new (std::nothrow) rs_policy();
+    if (!*p) return RS_ENOMEM;
+    (*p)->device = device_id; (*p)->kind = kind;
+    return RS_OK;
+}
+static void policy_destroy(rs_policy *p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    (void)hipDeviceSynchronize();
+    for (void *d : p->allocs) (void)hipFree(d);
+    delete p;
+}
+extern "C" void rs_idqn_destroy(rs_policy_handle p) { policy_destroy(p); }
+extern "C" void rs_mplight_destroy(rs_policy_handle p) { policy_destroy(p); }
+
 template <class T> static int pol_upload(rs_policy *p, const T **dst, const void *src, size_t count) {
     void *d = nullptr;
     if (hipMalloc(&d, count * sizeof(T) + 2048) != hipSuccess) return RS_ENOMEM;     // the fc1 copy passes may read up to 1 KB past the end
@@ -934,22 +733,18 @@ template <class T> static int pol_upload(rs_policy *p, const T **dst, const void
 extern "C" int rs_idqn_create(int32_t device_id, int32_t n_signals, int32_t lmax, const int32_t *n_actions, const float *conv_w,
                               const float *conv_b, const uint16_t *w1, const float *b1, const uint16_t *w2, const float *b2,
                               const uint16_t *w3, const float *b3, rs_policy_handle *out) {
-    if (!out) return RS_EINVAL;
-    *out = nullptr;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_err = "no HIP device visible (this library has no CPU fallback)"; return RS_EHIP; }
+    if (int rc = policy_devices(out, &ndev)) return rc;
     if (device_id < 0 || device_id >= ndev || n_signals <= 0 || lmax < 2 || lmax > 17 || !n_actions || !conv_w || !conv_b || !w1 || !b1 || !w2 || !b2 || !w3 || !b3) {
         g_create_err = "rs_idqn_create: bad argument (1 <= signals, 2 <= lmax <= 17)"; return RS_EINVAL;
     }
     for (int s = 0; s < n_signals; ++s)
         if (n_actions[s] < 1 || n_actions[s] > POL_QMAX) { g_create_err = "rs_idqn_create: 1..8 actions per signal"; return RS_ELIMIT; }
-    if (hipSetDevice(device_id) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RS_EHIP; }
-    rs_policy *p = new (std::nothrow) rs_policy();
-    if (!p) return RS_ENOMEM;
-    p->device = device_id;
+    rs_policy *p = nullptr;
+    int rc = policy_new(device_id, POLICY_IDQN, &p);
+    if (rc) return rc;
     const size_t S = (size_t)n_signals, hp = (size_t)(lmax / 2);       // ceil((lmax - 1) / 2)
     p->W.S = n_signals; p->W.lmax = lmax; p->W.hp = (int32_t)hp;
-    int rc;
     if ((rc = pol_upload<float>(p, &p->W.conv_w, conv_w, S * 64 * 4)) || (rc = pol_upload<float>(p, &p->W.conv_b, conv_b, S * 64)) ||
         (rc = pol_upload<h4_t>(p, &p->W.w1, w1, S * 64 * hp * 2 * 64)) || (rc = pol_upload<float>(p, &p->W.b1, b1, S * 64)) ||
         (rc = pol_upload<h4_t>(p, &p->W.w2, w2, S * 8 * 2 * 64)) || (rc = pol_upload<float>(p, &p->W.b2, b2, S * 64)) ||
@@ -964,12 +759,17 @@ extern "C" int rs_idqn_create(int32_t device_id, int32_t n_signals, int32_t lmax
     return RS_OK;
 }
 
+static void idqn_launch(const PolicyTab &W, const void *obs, int n_envs, int env_base, int mode, float eps, uint32_t seed, uint32_t step_key,
+                        const void *dyn, int32_t *actions, float *q, hipStream_t st) {
+    hipLaunchKernelGGL(rs_idqn_forward_kernel, dim3((n_envs + POL_TM - 1) / POL_TM, W.S), dim3(256), 0, st, W, (const __half *)obs, n_envs, env_base,
+                       mode, eps, seed, step_key, (const uint32_t *)dyn, actions, q);
+}
+
 extern "C" int rs_idqn_act(rs_policy_handle p, const void *obs, int32_t n_envs, int32_t env_base, int32_t mode, float epsilon, uint32_t seed, uint32_t step_key,
                            const void *dyn, int32_t *actions, float *q, void *stream) {
     if (!p || p->kind != POLICY_IDQN || !obs || !actions || n_envs <= 0 || mode < 0 || mode > 1) return RS_EINVAL;
     if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    hipLaunchKernelGGL(rs_idqn_forward_kernel, dim3((n_envs + POL_TM - 1) / POL_TM, p->W.S), dim3(256), 0, (hipStream_t)stream,
-                       p->W, (const __half *)obs, (int)n_envs, (int)env_base, (int)mode, epsilon, seed, step_key, (const uint32_t *)dyn, actions, q);
+    idqn_launch(p->W, obs, n_envs, env_base, mode, epsilon, seed, step_key, dyn, actions, q, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
 }
 
@@ -983,10 +783,8 @@ static void mplight_launch(const FrapTab &F, const void *obs, int n_envs, int en
 
 extern "C" int rs_mplight_create(int32_t device_id, int32_t demand_shape, int32_t n_pairs, const int32_t *pairs, int32_t n_signals,
                                  const int32_t *valid, const int32_t *order, const float *weights, rs_policy_handle *out) {
-    if (!out) return RS_EINVAL;
-    *out = nullptr;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_err = "no HIP device visible (this library has no CPU fallback)"; return RS_EHIP; }
+    if (int rc = policy_devices(out, &ndev)) return rc;
     if (device_id < 0 || device_id >= ndev || (demand_shape != 1 && demand_shape != 4) || n_pairs < 2 || n_pairs > FRAP_PMAX || n_signals <= 0 ||
         !pairs || !valid || !order || !weights) {
         g_create_err = "rs_mplight_create: bad argument (demand_shape 1 or 4, 2 <= n_pairs <= 16, 1 <= n_signals, tables and weights required)";
@@ -1011,14 +809,11 @@ extern "C" int rs_mplight_create(int32_t device_id, int32_t demand_shape, int32_
         }
         nv[(size_t)s] = n;
     }
-    if (hipSetDevice(device_id) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RS_EHIP; }
-    rs_policy *p = new (std::nothrow) rs_policy();
-    if (!p) return RS_ENOMEM;
-    p->device = device_id;
-    p->kind = POLICY_MPLIGHT;
+    rs_policy *p = nullptr;
+    int rc = policy_new(device_id, POLICY_MPLIGHT, &p);
+    if (rc) return rc;
     p->F.P = P; p->F.S = S; p->F.D = demand_shape;
     const size_t nw = (size_t)FrapOff(demand_shape).n;
-    int rc;
     if ((rc = pol_upload<float>(p, &p->F.w, weights, nw)) || (rc = pol_upload<int32_t>(p, &p->F.pairs, pairs, (size_t)P * 2)) ||
         (rc = pol_upload<int32_t>(p, &p->F.valid, valid, (size_t)S * P)) || (rc = pol_upload<int32_t>(p, &p->F.order, order, (size_t)S * P)) ||
         (rc = pol_upload<int32_t>(p, &p->F.nvalid, nv.data(), (size_t)S))) {
@@ -1042,14 +837,6 @@ extern "C" int rs_mplight_set_device_weights(rs_policy_handle p, const float *we
     if (!p || p->kind != POLICY_MPLIGHT || !weights) return RS_EINVAL;
     p->F.w = weights;
     return RS_OK;
-}
-
-extern "C" void rs_mplight_destroy(rs_policy_handle p) {
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    (void)hipDeviceSynchronize();
-    for (void *d : p->allocs) (void)hipFree(d);
-    delete p;
 }
 
 // ---- one env-step (or n of them) of a whole group of handles in ONE call (include/resco_sim.h: rs_group_step)
@@ -1082,29 +869,19 @@ extern "C" int rs_group_step(const rs_handle *hs, int32_t n_handles, const rs_gr
     for (int k = 0; k < n_steps; ++k)
         for (int i = 0; i < n_handles; ++i) {
             rs_sim *h = hs[i];
-            HIPCHK(h, hipSetDevice(h->device));
-            hipStream_t st = h->stream;
-            h->last = st;
-            const int total = h->n_envs * h->K.n_signals;
-            if (kind == RS_AGENT_RANDOM)
-                hipLaunchKernelGGL(rs_act_random_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->K, h->P, agent->step_key + (uint32_t)k, h->actions);
-            else if (kind == RS_AGENT_MAXWAVE || kind == RS_AGENT_MAXPRESSURE)
-                hipLaunchKernelGGL(rs_act_maxwave_kernel, dim3((total + 255) / 256), dim3(256), 0, st, h->K, h->P, (const int32_t *)h->pairs,
-                                   h->n_pairs, (const int32_t *)h->valid, (const int32_t *)h->order, (int)(kind == RS_AGENT_MAXPRESSURE),
-                                   (const int32_t *)h->O.mplight(), (const int32_t *)h->O.wave(), h->actions);
-            else if (kind == RS_AGENT_IDQN) {
-                float eps = agent->epsilon + (float)k * agent->epsilon_step;
-                if (eps < 0.0f) eps = 0.0f;
-                hipLaunchKernelGGL(rs_idqn_forward_kernel, dim3((h->n_envs + POL_TM - 1) / POL_TM, h->K.n_signals), dim3(256), 0, st,
-                                   agent->policy->W, (const __half *)h->O.drq_f16(), (int)h->n_envs, (int)h->P.env_base, (int)agent->mode, eps,
-                                   agent->seed, agent->step_key + (uint32_t)k, (const uint32_t *)nullptr, h->actions, (float *)nullptr);
-            } else if (kind == RS_AGENT_MPLIGHT) {
-                float eps = agent->epsilon + (float)k * agent->epsilon_step;
-                if (eps < 0.0f) eps = 0.0f;
+            hipStream_t st;
+            if (int rc = enter(h, nullptr, &st)) return rc;
+            const uint32_t key = agent ? agent->step_key + (uint32_t)k : 0u;
+            float eps = agent ? agent->epsilon + (float)k * agent->epsilon_step : 0.0f;
+            if (eps < 0.0f) eps = 0.0f;
+            if (kind == RS_AGENT_RANDOM) launch_random(h, st, key);
+            else if (kind == RS_AGENT_MAXWAVE || kind == RS_AGENT_MAXPRESSURE) launch_maxwave(h, st, kind == RS_AGENT_MAXPRESSURE);
+            else if (kind == RS_AGENT_IDQN)
+                idqn_launch(agent->policy->W, h->O.drq_f16(), h->n_envs, h->P.env_base, agent->mode, eps, agent->seed, key, nullptr, h->actions, nullptr, st);
+            else if (kind == RS_AGENT_MPLIGHT) {
                 const FrapTab &F = agent->policy->F;
                 const void *obs = F.D == 1 ? (const void *)h->O.mplight() : (const void *)h->O.mplight_full();
-                mplight_launch(F, obs, h->n_envs, h->P.env_base, eps, agent->seed, agent->step_key + (uint32_t)k, nullptr, h->actions, nullptr,
-                               nullptr, st);
+                mplight_launch(F, obs, h->n_envs, h->P.env_base, eps, agent->seed, key, nullptr, h->actions, nullptr, nullptr, st);
             }
             if (kind != RS_AGENT_NONE) HIPCHK(h, hipGetLastError());
             const int rc = launch_step(h, st, h->K.step_length * h->ratio, 1);
@@ -1140,12 +917,4 @@ extern "C" int rs_idqn_set_lanes(rs_policy_handle p, const int32_t *lanes_per_si
     }
     if (hipDeviceSynchronize() != hipSuccess) return RS_EHIP;
     return hipMemcpy((void *)p->W.hp_sig, hp.data(), hp.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess ? RS_OK : RS_EHIP;
-}
-
-extern "C" void rs_idqn_destroy(rs_policy_handle p) {
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    (void)hipDeviceSynchronize();
-    for (void *d : p->allocs) (void)hipFree(d);
-    delete p;
 }

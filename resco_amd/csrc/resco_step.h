@@ -10,8 +10,6 @@
 //   ex.next_chunk(c, w, i, n)  the next work chunk of wave w (its i-th call in this phase, n waves): on the GPU ONE atomic on the LDS
 //                           counter c per wave (dynamic: whichever wave is free takes the next chunk), on the host i * n + w --
 //                           any assignment of chunks to waves gives the same result, a phase being order independent
-//   ex.plan_long / ex.lc_decide / ex.move_long   the long code paths of a tick for ONE slot (ExecInline below: inlined; -DRS_CALL_LONG: called as functions
-//                           with a register allocation of their own -- measured, not adopted)
 // On the GPU (resco_sim.hip) one workgroup = one environment; the state lives in LDS for the whole env-step and phase() is
 // `f(threadIdx.x); __syncthreads()`.  The CPU tests compile the very same source for the host (tests/hostemu), where
 // phase() calls f for tid = 0 .. B-1 in turn (in any order: a phase never reads what another thread writes in the same
@@ -1218,27 +1216,9 @@ template <class LT> RS_DEV void lc_decide_and_flag(const KTab &T, const LT &L, c
     const int code = phase_lc_decide(T, L, grid, G, eo, t, s, ax, L.node[s]);
     if (code) flag_mover(L, s, t, code);
 }
-// what phase_move adds to its thread's counters, as one word (a function that is CALLED returns it in a register): bit 0 the vehicle is
-// still on the network, bit 1 it stands, bits 2.. its slot + 1 (0: it has arrived)
-RS_DEV void move_unpack(uint32_t r, int &active, int &halted, int &top) {
-    active += (int)(r & 1u); halted += (int)((r >> 1) & 1u);
-    if ((int)(r >> 2) > top) top = (int)(r >> 2);
-}
-// The LONG code paths of a tick as the execution interface sees them (ex.plan_long / ex.lc_decide / ex.move_long): this default inlines
-// them where they are used; a build with -DRS_CALL_LONG calls them as functions with a register allocation of their own (resco_sim.hip:
-// measured in round 6, 1-2 % slower, not adopted).
-struct ExecInline {
-    template <class LT> RS_MEM static void plan_long(const KTab &T, const LT &L, const Grid &grid, const State &G, size_t eo, const KParams &P, int genv, int, int t, int s) {
-        phase_plan<true>(T, L, grid, G, eo, P, genv, t, s);
-    }
-    template <class LT> RS_MEM static void lc_decide(const KTab &T, const LT &L, const Grid &grid, const State &G, size_t eo, int, int t, int s) {
-        lc_decide_and_flag(T, L, grid, G, eo, t, s);
-    }
-    template <class LT> RS_MEM static void move_long(const KTab &T, const LT &L, const Grid &gnew, const State &G, const KParams &P, int env, size_t eo, int t, bool last_tick, bool more,
-                                                     int s, int &active, int &halted, int &top) {
-        phase_move<true>(T, L, gnew, G, P, env, eo, t, last_tick, more, s, active, halted, top);
-    }
-};
+// Optional empty base of an execution interface: the step below asks nothing of it (the long paths of a tick are called directly), and
+// an Exec that names it as its base (`struct HostExec : ExecInline`) compiles as it is.
+struct ExecInline {};
 
 // ------------------------------------------------------------------------------------------------ the step
 // CAP: the slot capacity as a compile-time constant (0: read it from the tables at run time)
@@ -1355,8 +1335,8 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
                 for (int pass = 0; pass < 2; ++pass)
                     for (int w = tid; w < hw; w += B) {
                         if (pass && !(L.node[w].fl & FL_LC)) continue;
-                        if (pass) ex.lc_decide(T, L, gold, G, eo, env, t, w);
-                        else ex.plan_long(T, L, gold, G, eo, P, genv, env, t, w);
+                        if (pass) lc_decide_and_flag(T, L, gold, G, eo, t, w);
+                        else phase_plan<true>(T, L, gold, G, eo, P, genv, t, w);
                     }
             } else {
                 // The work of the phase in chunks, longest code path first: the look-ahead list (RS_LIST_CHUNK entries per chunk), the
@@ -1370,11 +1350,11 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
                     if (c < hch) {                                  // plan of a vehicle that looks beyond its lane
                         role = 1;
                         const int w = c * RS_H_CHUNK + ln;
-                        if (ln < RS_H_CHUNK && w < nh) ex.plan_long(T, L, gold, G, eo, P, genv, env, t, L.ls_h[w]);
+                        if (ln < RS_H_CHUNK && w < nh) phase_plan<true>(T, L, gold, G, eo, P, genv, t, L.ls_h[w]);
                     } else if (c < hch + lch) {                     // lane-change decision
                         role = 2;
                         const int w = (c - hch) * RS_LIST_CHUNK + ln;
-                        if (ln < RS_LIST_CHUNK && w < nlc) ex.lc_decide(T, L, gold, G, eo, env, t, L.ls_lc[w]);
+                        if (ln < RS_LIST_CHUNK && w < nlc) lc_decide_and_flag(T, L, gold, G, eo, t, L.ls_lc[w]);
                     } else {                                        // plan on the short path
                         const int w = (c - hch - lch) * 64 + ln;
                         if (w < hw && !(L.node[w].fl & FL_H)) phase_plan<false>(T, L, gold, G, eo, P, genv, t, w);
@@ -1433,7 +1413,7 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
                 if (c < mch) {
                     list = true;
                     const int w = c * RS_LIST_CHUNK + ln;
-                    if (ln < RS_LIST_CHUNK && w < nmh) ex.move_long(T, L, gnew, G, P, env, eo, t, !more, more, L.ls_mh[w], active, halted, top);
+                    if (ln < RS_LIST_CHUNK && w < nmh) phase_move<true>(T, L, gnew, G, P, env, eo, t, !more, more, L.ls_mh[w], active, halted, top);
                 } else if (c < mch + ich) {
                     // the winners of the departure lanes take the slots that were free at the beginning of the tick, lower lane first
                     for (int d = 63 - ln; d < T.n_dep; d += 64) {
@@ -1477,7 +1457,7 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
                     const int w = (c - mch - ich) * 64 + ln;
                     // (the vehicles of the list have FL_MH of this tick's parity set: their chunk moves them)
                     if (w < hw && (L.alive0[w >> 5] & (1u << (w & 31)))) {
-                        if (all) ex.move_long(T, L, gnew, G, P, env, eo, t, !more, more, w, active, halted, top);
+                        if (all) phase_move<true>(T, L, gnew, G, P, env, eo, t, !more, more, w, active, halted, top);
                         else if (!(L.node[w].fl & fl_mh(t))) phase_move<false>(T, L, gnew, G, P, env, eo, t, !more, more, w, active, halted, top);
                     }
                 }

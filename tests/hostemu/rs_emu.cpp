@@ -1,6 +1,7 @@
 // rs_emu.cpp -- HOST EMULATION of the step kernel (TEST INFRASTRUCTURE, never shipped, never loaded by resco_amd/).
 //
-// Compiles resco_amd/csrc/resco_step.h -- the very source of the HIP kernel -- with g++ and runs the "threads" of a
+// Compiles resco_amd/csrc/resco_step.h -- the very source of the HIP kernel -- and resco_host.h -- reset, re-init, the static agents,
+// the buffer table and scenario -> tables as the library has them -- with g++ and runs the "threads" of a
 // workgroup one after the other, phase by phase (HostExec::phase), in a selectable order (ascending, descending,
 // shuffled).  The CPU tests compare it with the oracle bit for bit: that pins the kernel's LOGIC (and its independence
 // of the thread order inside a phase) without a GPU; the -m gpu tests then pin the real thing.  The library exports the
@@ -71,9 +72,9 @@ static int rs_dbg_slot = getenv("RS_DBG_SLOT") ? atoi(getenv("RS_DBG_SLOT")) : -
 static int rs_dbg_t = getenv("RS_DBG_T") ? atoi(getenv("RS_DBG_T")) : -1;
 static long rs_dbg_chain = 0;         // chain-walk steps of the current phase (reset by HostExec::phase)
 #endif
-#include "resco_step.h"
+#include "resco_host.h"
 
-struct HostExec : ExecInline {
+struct HostExec {
     unsigned long long role_begin() const { return 0ull; }
     void role_end(int, unsigned long long) const {}
     int wave_of(int tid) const { return tid >> 6; }
@@ -100,7 +101,6 @@ struct HostExec : ExecInline {
 };
 
 struct rs_sim {
-    PackedTables PT;
     KTab K{};
     State G{};
     Out O{};
@@ -114,24 +114,17 @@ struct rs_sim {
     std::vector<long long> stats;
     std::vector<uint16_t> dep_next;
     std::vector<uint32_t> mail;
-    std::vector<float> route_cont, vtype_params;
-    std::vector<std::vector<int32_t>> keep;
-    struct Buf { void *ptr; int64_t shape[4]; int ndim; int dtype; size_t bytes; };
+    // the tables of K: copies of the packed tables AND of the caller's arrays (which it may free).  Byte blocks: the 16-byte records rest
+    // on operator new's alignment, and an empty table is 16 zero bytes, not a null pointer (a read of one does not fault here)
+    std::vector<std::vector<char>> keep;
     Buf bufs[RS_BUF_COUNT]{};
     std::string err;
     int n_pairs = 0;
 };
 static std::string g_err;
-static const size_t kDtypeSize[] = {4, 4, 2, 1, 2, 8, 4};
-static void set_buf(rs_sim *h, int which, void *ptr, int dtype, int ndim, int64_t a, int64_t b = 1, int64_t c = 1, int64_t d = 1) {
-    auto &B = h->bufs[which];
-    B.ptr = ptr; B.dtype = dtype; B.ndim = ndim;
-    B.shape[0] = a; B.shape[1] = b; B.shape[2] = c; B.shape[3] = d;
-    B.bytes = (size_t)(a * b * c * d) * kDtypeSize[dtype];
-}
-static const int32_t *keep_i32(rs_sim *h, const int32_t *src, size_t n) {
-    h->keep.emplace_back(src, src + (n ? n : 0));
-    if (h->keep.back().empty()) h->keep.back().push_back(0);
+static const void *keep_copy(rs_sim *h, const void *src, size_t bytes) {
+    h->keep.emplace_back((const char *)src, (const char *)src + bytes);
+    if (h->keep.back().empty()) h->keep.back().resize(16, 0);
     return h->keep.back().data();
 }
 
@@ -158,44 +151,19 @@ extern "C" {
 // block_threads < 0 selects thread order: -1 descending, -2 shuffled (with one thread per slot); order > 0 as given
 int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_envs, int32_t env_base, int32_t device_id, int32_t block_threads, rs_handle *out) {
     rs_sim *h = new rs_sim();
-    {   // (the library's choice of the grid cell length, resco_sim.hip)
-        PackedTables probe;
-        if (!probe.build(sc)) { g_err = probe.err; delete h; return RS_ELIMIT; }
-        if (!h->PT.build(sc, pick_cell_len(sc, probe.n_arr, probe.n_dep, probe.tls_maxl))) { g_err = h->PT.err; delete h; return RS_ELIMIT; }
-    }
-    PackedTables &PT = h->PT;
+    PackedTables PT;
+    if (const char *msg = rs_pack_tables(PT, sc)) { g_err = msg; delete h; return RS_ELIMIT; }
     const int C = sc->capacity;
     h->order = device_id;           // the emulation has no device: the argument carries the thread order
     h->block = block_threads > 0 ? block_threads : (C > 1024 ? 1024 : C);
     h->n_envs = n_envs;
-    h->route_cont = PT.route_cont;
-    h->vtype_params.assign(sc->vtype_params, sc->vtype_params + (size_t)sc->n_vtypes * VT_COLS);
-    KTab &K = h->K; KCold &c = K.cold;
-    K.lanes_ = PT.lanes.data(); K.links_ = PT.links.data(); K.foes_ = PT.foes.data(); K.rsteps_ = PT.rsteps.data();
-    K.route_cont_ = h->route_cont.data(); K.next_link_ = PT.next_link.data(); K.notbest_ = PT.notbest.data(); K.routes_ = PT.routes.data();
-    K.trip_route_ = PT.trip_route.data(); K.trip_vtype_ = PT.trip_vtype.data();
-    c.trip_depart = keep_i32(h, sc->trip_depart, sc->n_trips); c.trip_next = PT.trip_next.data(); c.dep_lane = PT.dep_lane.data(); c.dep_info = PT.dep_info.data(); c.dep_first = PT.dep_first.data();
-    c.vtype_params = h->vtype_params.data(); c.tls8 = PT.tls8.data(); c.fix8 = PT.fix8.data();
-    c.tls_nphase = keep_i32(h, sc->tls_nphase, sc->n_signals); c.tls_ngreen = keep_i32(h, sc->tls_ngreen, sc->n_signals);
-    c.tls_nlinks = keep_i32(h, sc->tls_nlinks, sc->n_signals); c.tls_state_off = PT.tls_off_p.data();
-    c.tls_dur_off = keep_i32(h, sc->tls_dur_off, sc->n_signals); c.tls_yel_off = keep_i32(h, sc->tls_yel_off, sc->n_signals);
-    c.tls_dur = keep_i32(h, sc->tls_dur, sc->n_tls_dur); c.tls_yellow = keep_i32(h, sc->tls_yellow, sc->n_tls_yellow);
-    c.tls_init_phase = keep_i32(h, sc->tls_init_phase, sc->n_signals);
-    c.fix_nphase = keep_i32(h, sc->fix_nphase, sc->n_signals); c.fix_state_off = PT.fix_off_p.data();
-    c.fix_dur_off = keep_i32(h, sc->fix_dur_off, sc->n_signals); c.fix_dur = keep_i32(h, sc->fix_dur, sc->n_fix_dur);
-    c.fix_init_phase = keep_i32(h, sc->fix_init_phase, sc->n_signals); c.fix_init_left = keep_i32(h, sc->fix_init_left, sc->n_signals);
-    c.lane_obs = PT.lane_obs16.data(); c.obs_sig = PT.obs_sig.data(); c.sig_obs_start = keep_i32(h, sc->sig_obs_start, sc->n_signals + 1);
-    c.mv_in_start = keep_i32(h, sc->mv_in_start, sc->n_signals * 12 + 1); c.mv_in_idx = keep_i32(h, sc->mv_in_idx, sc->n_mv_in);
-    c.mv_out_start = keep_i32(h, sc->mv_out_start, sc->n_signals * 12 + 1); c.mv_out_idx = keep_i32(h, sc->mv_out_idx, sc->n_mv_out);
-    c.pr_out_start = keep_i32(h, sc->pr_out_start, sc->n_signals + 1); c.pr_out_idx = keep_i32(h, sc->pr_out_idx, sc->n_pr_out);
-    c.trips_cum = keep_i32(h, sc->trips_cum, sc->horizon + 2);
-    K.maxlen = PT.maxlen; K.occ_unit = PT.occ_unit; K.n_trips = sc->n_trips; K.tls_maxl = PT.tls_maxl; K.kmax = sc->kmax;
-    K.n_lanes = sc->n_lanes; K.n_cells = PT.n_cells; K.n_signals = sc->n_signals; K.n_obs = sc->n_obs; K.n_vtypes = sc->n_vtypes;
-    h->ratio = p->step_ratio > 1 ? p->step_ratio : 1;
-    K.horizon = sc->horizon; K.capacity = C; K.step_length = sc->step_length; K.yellow_length = sc->yellow_length * h->ratio; K.lmax = PT.lmax;
-    K.n_arr = PT.n_arr; K.n_dep = PT.n_dep;
-    h->P.seed = p->seed; h->P.env_base = env_base; h->P.max_distance = p->max_distance; h->P.sigma = p->sigma;
-    h->P.speed_dev = p->speed_dev; h->P.fixed_program = p->fixed_program; h->P.tls_expiry = p->tls_hold == 0; h->P.n_envs = n_envs;
+    KTab &K = h->K;
+#define KEEP(dst, type, src, count) dst = (const type *)keep_copy(h, src, (size_t)(count) * sizeof(type));
+    RS_KTAB_TABLES(KEEP, K, PT, sc)
+#undef KEEP
+    h->ratio = rs_step_ratio(p);
+    rs_ktab_scalars(K, PT, sc, h->ratio);
+    h->P = rs_kparams(p, env_base, n_envs);
     const size_t N = (size_t)n_envs, NC = N * C, S = (size_t)sc->n_signals;
     h->G.nc = NC; h->slab.assign(State::bytes(NC), 0); h->G.base = h->slab.data();
     h->O.n = n_envs; h->O.o = sc->n_obs; h->O.s = sc->n_signals; h->O.lm = PT.lmax;
@@ -208,61 +176,16 @@ int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_envs, int32_t
     if (p->trip_log) { h->trip_log.assign(N * (size_t)sc->n_trips * 4, 0); h->G.trip_log = h->trip_log.data(); }
     h->lds = lds_carve(&h->L, C, K.n_cells, K.n_arr, K.n_dep, sc->n_obs, sc->n_signals, sc->n_vtypes, K.tls_maxl);
     if (!lds_fix_matches(h->L, C)) { g_err = "the layout of the working memory does not match the kernel's literals (lds_carve / LdsFix)"; delete h; return RS_EINVAL; }
-    h->L.cell_inv = h->PT.cell_inv;
+    h->L.cell_inv = PT.cell_inv;
     h->smem.assign(h->lds + 64, 0);
-    State &G = h->G; Out &O = h->O;
-    const int64_t n = n_envs, cc = C, s = sc->n_signals, o = sc->n_obs, lmax = PT.lmax;
-    set_buf(h, RS_BUF_LANE_AGG, O.lane_agg(), RS_F32, 3, n, o, 5); set_buf(h, RS_BUF_DRQ_NORM, O.drq_norm(), RS_F32, 3, n, o, 5);
-    set_buf(h, RS_BUF_PHASE, O.phase(), RS_I32, 2, n, s); set_buf(h, RS_BUF_MPLIGHT, O.mplight(), RS_I32, 3, n, s, 13);
-    set_buf(h, RS_BUF_WAVE, O.wave(), RS_I32, 3, n, s, 12); set_buf(h, RS_BUF_WAIT, O.wait(), RS_F32, 2, n, s);
-    set_buf(h, RS_BUF_WAIT_NORM, O.wait_norm(), RS_F32, 2, n, s); set_buf(h, RS_BUF_PRESSURE, O.pressure(), RS_I32, 2, n, s);
-    set_buf(h, RS_BUF_QUEUE_SUM, O.queue_sum(), RS_I32, 2, n, s); set_buf(h, RS_BUF_QUEUE_MAX, O.queue_max(), RS_I32, 2, n, s);
-    set_buf(h, RS_BUF_ACTIONS, h->actions.data(), RS_I32, 2, n, s); set_buf(h, RS_BUF_ENV, G.env, RS_I32, 2, n, 4);
-    set_buf(h, RS_BUF_TLS, G.tls, RS_I32, 3, n, s, TLS_W);
-    set_buf(h, RS_BUF_VEH_POS, G.pos(), RS_F32, 2, n, cc); set_buf(h, RS_BUF_VEH_SPEED, G.speed(), RS_F32, 2, n, cc);
-    set_buf(h, RS_BUF_VEH_ACCEL, G.accel(), RS_F32, 2, n, cc); set_buf(h, RS_BUF_VEH_TLOSS, G.tloss(), RS_F32, 2, n, cc);
-    set_buf(h, RS_BUF_VEH_LANE, G.lane(), RS_U16, 2, n, cc); set_buf(h, RS_BUF_VEH_TRIP, G.trip(), RS_U16, 2, n, cc);
-    set_buf(h, RS_BUF_VEH_CURSOR, G.cursor(), RS_U16, 2, n, cc); set_buf(h, RS_BUF_VEH_SWAIT, G.swait(), RS_U16, 2, n, cc);
-    set_buf(h, RS_BUF_VEH_RWAIT, G.rwait(), RS_U16, 2, n, cc); set_buf(h, RS_BUF_VEH_DEPART, G.depart(), RS_U16, 2, n, cc);
-    set_buf(h, RS_BUF_VEH_OWNER, G.owner(), RS_U8, 2, n, cc); set_buf(h, RS_BUF_STATS, G.stats, RS_I64, 2, n, ST_N);
-    set_buf(h, RS_BUF_DRQ_NORM_F16, O.drq_f16(), RS_F16, 4, n, s, lmax, 5); set_buf(h, RS_BUF_VEH_SF, G.sf(), RS_F32, 2, n, cc);
-    set_buf(h, RS_BUF_VEH_WTOT, G.wtot(), RS_U16, 2, n, cc);
-    set_buf(h, RS_BUF_TRIP_LOG, G.trip_log, RS_I32, 3, n, p->trip_log ? sc->n_trips : 0, 4);
-    set_buf(h, RS_BUF_DEP_NEXT, G.dep_next, RS_U16, 2, n, K.n_dep);
-    set_buf(h, RS_BUF_VEH_COOP, G.coop(0), RS_U32, 2, n, cc); set_buf(h, RS_BUF_VEH_COOPLEAD, G.cooplead(0), RS_U32, 2, n, cc);
-    set_buf(h, RS_BUF_ARRIVALS, O.arrivals(), RS_I32, 2, n, s); set_buf(h, RS_BUF_DEPARTURES, O.departures(), RS_I32, 2, n, s);
-    set_buf(h, RS_BUF_MPLIGHT_FULL, O.mplight_full(), RS_F32, 3, n, s, 49);
-    set_buf(h, RS_BUF_LANE_ARRIVALS, O.lane_arr(), RS_I32, 2, n, sc->n_obs);
-    set_buf(h, RS_BUF_VEH_COOP_ODD, G.coop(1), RS_U32, 2, n, cc); set_buf(h, RS_BUF_VEH_COOPLEAD_ODD, G.cooplead(1), RS_U32, 2, n, cc);
-    set_buf(h, RS_BUF_VEH_MAIL, G.mail, RS_U32, 2, n, (cc + 31) / 32);
+    rs_fill_bufs(h->bufs, h->G, h->O, h->actions.data(), BufDims{n_envs, C, sc->n_signals, sc->n_obs, PT.lmax, K.n_dep, p->trip_log ? sc->n_trips : 0});
     *out = h;
     return rs_reset(h, nullptr);
 }
 void rs_destroy(rs_handle h) { delete h; }
 const char *rs_last_error(rs_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
 int rs_reset(rs_handle h, void *) {
-    const KTab &T = h->K; const State &G = h->G;
-    const int C = T.capacity, S = T.n_signals;
-    for (int env = 0; env < h->n_envs; ++env) {
-        const size_t eo = (size_t)env * C;
-        for (int s = 0; s < C; ++s) {
-            G.lane()[eo + s] = LANE_NONE; G.trip()[eo + s] = TRIP_NONE; G.owner()[eo + s] = OWNER_NONE;
-            G.rwait()[eo + s] = 0; G.swait()[eo + s] = 0; G.cursor()[eo + s] = 0; G.depart()[eo + s] = 0; G.wtot()[eo + s] = 0;
-            G.pos()[eo + s] = 0.0f; G.speed()[eo + s] = 0.0f; G.accel()[eo + s] = 0.0f; G.tloss()[eo + s] = 0.0f; G.sf()[eo + s] = 1.0f;
-            G.coop(0)[eo + s] = COOP_NONE; G.coop(1)[eo + s] = COOP_NONE; G.cooplead(0)[eo + s] = COOP_NONE; G.cooplead(1)[eo + s] = COOP_NONE;
-        }
-        for (int s = 0; s < S; ++s) {
-            int ph, left;
-            if (h->P.fixed_program) { ph = T.cold.fix_init_phase[s]; left = T.cold.fix_init_left[s]; }
-            else { ph = T.cold.tls_init_phase[s]; left = T.cold.tls_dur[T.cold.tls_dur_off[s] + ph]; }
-            G.tls[(env * S + s) * TLS_W + 0] = ph; G.tls[(env * S + s) * TLS_W + 1] = left; G.tls[(env * S + s) * TLS_W + 2] = 0; G.tls[(env * S + s) * TLS_W + 3] = 0;
-        }
-        for (int d = 0; d < T.n_dep; ++d) G.dep_next[(size_t)env * T.n_dep + d] = T.cold.dep_first[d];
-        for (int i = 0; i < (C + 31) / 32; ++i) G.mail[(size_t)env * ((C + 31) / 32) + i] = 0u;
-        for (int i = 0; i < 4; ++i) G.env[env * 4 + i] = 0;
-        for (int i = 0; i < ST_N; ++i) G.stats[(size_t)env * ST_N + i] = 0;
-        if (G.trip_log) for (int i = 0; i < T.n_trips * 4; ++i) G.trip_log[(size_t)env * T.n_trips * 4 + i] = 0;
-    }
+    for (int env = 0; env < h->n_envs; ++env) rs_reset_env(h->K, h->G, h->P, env, 0, 1);
     run_step(h, 0, 0);
     return RS_OK;
 }
@@ -274,40 +197,17 @@ int rs_step(rs_handle h, const int32_t *actions, int32_t, void *) {
 int rs_ticks(rs_handle h, int32_t n, void *) { run_step(h, n, 0); return RS_OK; }
 int rs_step_sim(rs_handle h, int32_t n, void *) { run_step(h, n, 0, 0); return RS_OK; }
 int rs_set_outputs(rs_handle h, uint64_t buffer_mask) {
-    uint32_t m = 0;
-    if (buffer_mask & (1ull << RS_BUF_LANE_AGG)) m |= OUT_LANE_AGG;
-    if (buffer_mask & (1ull << RS_BUF_DRQ_NORM)) m |= OUT_DRQ_NORM;
-    if (buffer_mask & (1ull << RS_BUF_DRQ_NORM_F16)) m |= OUT_DRQ_F16;
-    if (buffer_mask & (1ull << RS_BUF_LANE_ARRIVALS)) m |= OUT_LANE_ARR;
-    if (buffer_mask & (1ull << RS_BUF_MPLIGHT)) m |= OUT_MPLIGHT;
-    if (buffer_mask & (1ull << RS_BUF_WAVE)) m |= OUT_WAVE;
-    if (buffer_mask & (1ull << RS_BUF_MPLIGHT_FULL)) m |= OUT_MPLIGHT_FULL;
-    if (buffer_mask & (1ull << RS_BUF_VEH_ACCEL)) m |= OUT_VEH_ACCEL;
-    h->out_mask = m;
+    h->out_mask = rs_out_mask(buffer_mask);
     return RS_OK;
 }
 int rs_sync(rs_handle) { return RS_OK; }
 int rs_reinit_signals(rs_handle h, void *) {
-    const KTab &T = h->K; const State &G = h->G;
-    const int C = T.capacity, S = T.n_signals;
-    for (int env = 0; env < h->n_envs; ++env) {
-        const size_t eo = (size_t)env * C;
-        for (int s = 0; s < C; ++s) { G.owner()[eo + s] = OWNER_NONE; G.rwait()[eo + s] = 0; }
-        for (int s = 0; s < S; ++s) {
-            if (!h->P.fixed_program) G.tls[(env * S + s) * TLS_W + 1] = T.cold.tls_dur[T.cold.tls_dur_off[s] + G.tls[(env * S + s) * TLS_W + 0]];
-            G.tls[(env * S + s) * TLS_W + 2] = 0; G.tls[(env * S + s) * TLS_W + 3] = 0;
-        }
-    }
+    for (int env = 0; env < h->n_envs; ++env) rs_reinit_env(h->K, h->G, h->P, env, 0, 1);
     run_step(h, 0, 0);
     return RS_OK;
 }
 int rs_act_random(rs_handle h, uint32_t step_key, void *) {
-    const int S = h->K.n_signals;
-    for (int i = 0; i < h->n_envs * S; ++i) {
-        const int env = i / S, s = i - env * S;
-        const uint32_t hh = d_hash(h->P.seed ^ 0xA5A5A5A5u, (uint32_t)(h->P.env_base + env), (uint32_t)s, step_key, 7u);
-        h->actions[i] = (int32_t)(hh % (uint32_t)h->K.cold.tls_ngreen[s]);
-    }
+    for (int i = 0; i < h->n_envs * h->K.n_signals; ++i) h->actions[i] = rs_random_action(h->K, h->P, step_key, i);
     return RS_OK;
 }
 int rs_act_maxwave(rs_handle h, const int32_t *phase_pairs, int32_t n_pairs, const int32_t *valid, const int32_t *order, int32_t use_pressure, void *) {
@@ -317,20 +217,8 @@ int rs_act_maxwave(rs_handle h, const int32_t *phase_pairs, int32_t n_pairs, con
         h->pairs.assign(phase_pairs, phase_pairs + n_pairs * 2); h->valid.assign(valid, valid + S * n_pairs); h->ordr.assign(order, order + S * n_pairs);
         h->n_pairs = n_pairs;
     }
-    for (int i = 0; i < h->n_envs * S; ++i) {
-        const int s = i % S;
-        const int32_t *obs = use_pressure ? h->O.mplight() + (size_t)i * 13 + 1 : h->O.wave() + (size_t)i * 12;
-        bool have = false; int best = 0, best_act = 0;
-        for (int j = 0; j < h->n_pairs; ++j) {
-            const int p = h->ordr[s * h->n_pairs + j];
-            if (p < 0) break;
-            const int act = h->valid[s * h->n_pairs + p];
-            if (act < 0) continue;
-            const int press = obs[h->pairs[p * 2]] + obs[h->pairs[p * 2 + 1]];
-            if (!have || press > best) { have = true; best = press; best_act = act; }
-        }
-        h->actions[i] = best_act;
-    }
+    for (int i = 0; i < h->n_envs * S; ++i)
+        h->actions[i] = rs_maxwave_action(h->K, h->pairs.data(), h->n_pairs, h->valid.data(), h->ordr.data(), use_pressure, h->O.mplight(), h->O.wave(), i);
     return RS_OK;
 }
 // the static agents + the step of a group of handles in one call (include/resco_sim.h); the policy network is device code only
@@ -352,11 +240,7 @@ int rs_group_step(const rs_handle *hs, int32_t n, const rs_group_agent *agent, i
 }
 int rs_get_buffer(rs_handle h, int32_t which, void **dev_ptr, int64_t shape[4], int32_t *ndim, int32_t *dtype) {
     if (!h || which < 0 || which >= RS_BUF_COUNT) return RS_EINVAL;
-    auto &B = h->bufs[which];
-    if (dev_ptr) *dev_ptr = B.ptr;
-    if (shape) for (int i = 0; i < 4; ++i) shape[i] = B.shape[i];
-    if (ndim) *ndim = B.ndim;
-    if (dtype) *dtype = B.dtype;
+    rs_buf_describe(h->bufs[which], dev_ptr, shape, ndim, dtype);
     return RS_OK;
 }
 int rs_read_buffer(rs_handle h, int32_t which, void *host_dst, int64_t nbytes) {
@@ -385,7 +269,7 @@ int rs_timing(rs_handle, int32_t) { return RS_OK; }
 int rs_timing_read(rs_handle, float *ms, int32_t *n) { if (ms) *ms = 0.0f; if (n) *n = 0; return RS_OK; }
 int rs_phase_profile(rs_handle, int32_t, uint64_t *out) { if (out) memset(out, 0, 16 * 8); return RS_OK; }
 int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes) {
-    if (n_envs) *n_envs = h->n_envs; if (block_threads) *block_threads = h->block; if (lds_bytes) *lds_bytes = (int32_t)h->lds; if (max_lanes) *max_lanes = h->K.lmax;
+    rs_info_describe(h->n_envs, h->block, h->lds, h->K.lmax, n_envs, block_threads, lds_bytes, max_lanes);
     return RS_OK;
 }
 }
