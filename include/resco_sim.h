@@ -331,11 +331,12 @@ void rs_mplight_destroy(rs_policy_handle p);
  *   RS_AGENT_IDQN         rs_idqn_act(policy, h's RS_BUF_DRQ_NORM_F16, mode, epsilon + k * epsilon_step (>= 0), seed, step_key + k);
  *                         the epsilon-greedy draws are keyed by the GLOBAL environment index (env_base + e), so that a batch
  *                         split over pipes or GPUs draws what the single batch draws
+ *   RS_AGENT_IPPO         refused here (nothing records a trajectory in rs_group_step): the agent kind of rs_group_rollout below
  *   RS_AGENT_MPLIGHT      rs_mplight_act(policy, h's RS_BUF_MPLIGHT (demand_shape 1) or RS_BUF_MPLIGHT_FULL (4), epsilon + k * epsilon_step
  *                         (>= 0), seed, step_key + k), keyed by the global environment index as IDQN; mode must be 0, and the buffer the
  *                         policy reads must not be switched off (rs_set_outputs)
  * Returns the first error (codes as everywhere; rs_last_error of the handle it occurred on). */
-enum rs_agent { RS_AGENT_NONE = 0, RS_AGENT_RANDOM = 1, RS_AGENT_MAXWAVE = 2, RS_AGENT_MAXPRESSURE = 3, RS_AGENT_IDQN = 4, RS_AGENT_MPLIGHT = 5 };
+enum rs_agent { RS_AGENT_NONE = 0, RS_AGENT_RANDOM = 1, RS_AGENT_MAXWAVE = 2, RS_AGENT_MAXPRESSURE = 3, RS_AGENT_IDQN = 4, RS_AGENT_MPLIGHT = 5, RS_AGENT_IPPO = 6 };
 typedef struct rs_group_agent {
     int32_t kind;               /* enum rs_agent */
     uint32_t step_key;          /* RANDOM, IDQN, MPLIGHT: key of the call's first step */
@@ -345,6 +346,44 @@ typedef struct rs_group_agent {
     uint32_t seed;
 } rs_group_agent;
 int rs_group_step(const rs_handle *handles, int32_t n_handles, const rs_group_agent *agent, int32_t n_steps);
+
+/* ---- IPPO on the device: actor-critic launch, rollout recorder, fused GAE ------------------------------------------
+ * The reference's IPPO agent (resco_benchmark/agents/pfrl_ppo.py:38-75) is one pfrl PPO per signal on the IDQN trunk with two
+ * heads, SoftmaxCategoricalHead over Linear(64, A) and Linear(64, 1); its loop is main.py:104-108 (act, step, observe).
+ *
+ * rs_ippo_act: the actor-critic mode of the fused forward on an rs_idqn_create policy whose pack carries the value head as column 8
+ * of w3 and b3[s][8] (resco_amd/agents/ippo_fused.py: pack_ippo_weights; both are zero in an IDQN pack, whose value then is 0).
+ * For every (environment, signal): the action drawn from softmax(logits) exactly as rs_idqn_act mode 1 draws it (bit-identical for
+ * the same policy, obs, seed, step_key, env_base), logp = logit[a] - max - log(sum exp(logit - max)) over the signal's own actions,
+ * value = the value head on the same trunk.  All pointers are DEVICE pointers: actions int32 [N][S], logp / value float [N][S],
+ * logits float [N][S][8] (-inf beyond a signal's actions) or NULL.  actions and logp may BOTH be NULL: a value-only evaluation
+ * (the bootstrap value of the state after a segment; the same value bits as the full call).  dyn: NULL or a device
+ * {uint32 unused; uint32 step_key} (the layout of rs_idqn_act's).  An MPLight handle is refused with RS_EINVAL.
+ *
+ * rs_group_rollout: rs_group_step for agent->kind == RS_AGENT_IPPO (policy, seed, step_key are read; mode and epsilon are not)
+ * that also records the trajectory PPO learns from.  segs[i] describes caller-owned DEVICE buffers of handle i with T slots; per
+ * step k and handle, on the handle's own stream, asynchronously: RS_BUF_DRQ_NORM_F16 as the policy sees it -> obs[t0 + k], the
+ * actor-critic kernel (key step_key + k, draws keyed by env_base + e as for IDQN) -> RS_BUF_ACTIONS and act / logp / value[t0 + k],
+ * the step kernel, RS_BUF_WAIT_NORM after the step -> rew[t0 + k].  RS_EINVAL (rs_last_error of the handle): t0 + n_steps > T,
+ * a switched-off RS_BUF_DRQ_NORM_F16, a policy built for another scenario or device, another agent kind, a NULL buffer.
+ *
+ * rs_ppo_gae (resco_amd/csrc/resco_ppo.h): generalised advantage estimation over a recorded segment and the per-signal
+ * standardisation of the advantages, as resco_amd/agents/ippo.py gae() + make_dataset do them: no bootstrap across done[t],
+ * ret = adv_raw + value, adv = (adv_raw - mean_s) / (std_s + 1e-8) over the T * n_envs samples of signal s (std biased).  DEVICE
+ * pointers: rew, value, adv, ret float [T][n_envs][S]; last_value float [n_envs][S]; done uint8 [T]; scratch: n_envs * S floats.
+ * Fixed reduction order, no atomics: two runs give the same bits.  Launched on `stream`. */
+typedef struct rs_rollout {      /* caller-owned DEVICE buffers of ONE handle, T slots */
+    void *obs;                   /* f16 [T][n_envs][S][lmax][5]  RS_BUF_DRQ_NORM_F16 as the policy saw it */
+    int32_t *act; float *logp, *value, *rew;     /* [T][n_envs][S]; rew = RS_BUF_WAIT_NORM after the step */
+    int32_t T;
+} rs_rollout;
+int rs_ippo_act(rs_policy_handle p, const void *obs, int32_t n_envs, int32_t env_base, uint32_t seed, uint32_t step_key,
+                const void *dyn, int32_t *actions, float *logp, float *value, float *logits, void *stream);
+int rs_group_rollout(const rs_handle *handles, int32_t n_handles, const rs_group_agent *agent,
+                     const rs_rollout *segs /* [n_handles] */, int32_t t0, int32_t n_steps);
+int rs_ppo_gae(const float *rew, const float *value, const float *last_value, const uint8_t *done /* [T] */,
+               int32_t T, int32_t n_envs, int32_t n_signals, float gamma, float lambda,
+               float *adv /* standardised per signal */, float *ret, void *scratch, void *stream);
 
 /* static facts */
 int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal);

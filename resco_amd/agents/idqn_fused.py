@@ -83,9 +83,26 @@ class FusedIDQN:
         self._actions = {}
         self.refresh()
 
+    # what a subclass with more columns in the fc3 tile replaces (ippo_fused.FusedIPPO: the value head)
+    _pack = staticmethod(pack_idqn_weights)
+
+    def _repack_index(self):
+        return repack_index(self.lmax, self.net.amax)
+
+    def _fc3_source(self):
+        return self.net.fc3_w
+
+    def _fill_b3(self, b3):
+        b3[:, :self.net.amax] = self.net.fc3_b
+
+    @property
+    def handle(self):
+        """the rs_policy_handle (SimGroup.step('idqn', policy=...), SimGroup.rollout)"""
+        return self._h.value if self._h is not None else None
+
     def refresh(self):
         """(Re)pack the network's current weights, e.g. after learner updates."""
-        w = pack_idqn_weights(self.net)
+        w = self._pack(self.net)
         h = C.c_void_p()
         rc = self._lib.rs_idqn_create(self.device, self.S, self.lmax, *[w[k].ctypes.data for k in
                                       ('n_actions', 'conv_w', 'conv_b', 'w1', 'b1', 'w2', 'b2', 'w3', 'b3')], C.byref(h))
@@ -122,10 +139,9 @@ class FusedIDQN:
         (index_select + mask + casting copy each)."""
         net, S = self.net, self.S
         dev = net.fc1_w.device
-        A = net.amax
         if not hasattr(self, '_idx'):
             self._idx, self._mask, self._dev = {}, {}, {}
-            for k, i in repack_index(self.lmax, A).items():
+            for k, i in self._repack_index().items():
                 self._idx[k] = torch.as_tensor(np.maximum(i, 0), device=dev)
                 self._mask[k] = torch.as_tensor((i >= 0).astype(np.float32), device=dev)
                 # + 2 KB: the kernel's copy passes of the last conv channel may read up to 1 KB past the fc1 fragments
@@ -134,9 +150,9 @@ class FusedIDQN:
                 self._dev[k] = self._pad[k][:S * len(i)].view(S, len(i))
             self._dev['b3'] = torch.zeros(S, 32, device=dev, dtype=torch.float32)
         d = self._dev
-        for k, w in (('w1', net.fc1_w), ('w2', net.fc2_w), ('w3', net.fc3_w)):
+        for k, w in (('w1', net.fc1_w), ('w2', net.fc2_w), ('w3', self._fc3_source())):
             d[k].copy_(torch.index_select(w.reshape(S, -1).float(), 1, self._idx[k]).mul_(self._mask[k]))
-        d['b3'][:, :A] = net.fc3_b
+        self._fill_b3(d['b3'])
         in_place = net.conv_w.dtype == torch.float32
         for k, t in (('conv_w', net.conv_w), ('conv_b', net.conv_b), ('b1', net.fc1_b), ('b2', net.fc2_b)):
             d[k] = t.detach() if (in_place and t.is_contiguous()) else t.detach().float().contiguous()

@@ -16,7 +16,8 @@ What is different by design: the S agents are one set of stacked parameters unde
 parameters: equal to S optimisers); the loss is the sum of the per-signal losses; gradient clipping and advantage
 standardisation are done per signal as S separate agents would.  A rollout segment holds T env-steps of all N
 environments (T*N samples per signal per update instead of 1024 consecutive steps of one environment).
-Acting can go through the fused HIP kernel (`FusedIDQN(net).act(obs, sample=True)`: same trunk, softmax sampling).
+Acting can go through the fused HIP kernel (`FusedIDQN(net).act(obs, sample=True)`: same trunk, softmax sampling), or through its
+actor-critic mode, which also returns the log-probability and the value (ippo_fused.py: FusedIPPO; update_from_rollout below).
 """
 import math
 
@@ -206,7 +207,41 @@ class BatchedPPOLearner:
             g.mul_(scale.unsqueeze(1).to(g.dtype))
 
     def update(self, obs, act, rew, done, last_obs, generator=None):
-        ds = self.make_dataset(obs, act, rew, done, last_obs)
+        return self._fit(self.make_dataset(obs, act, rew, done, last_obs), generator)
+
+    @torch.no_grad()
+    def dataset_from_rollout(self, rollout, last_value, done):
+        """The dataset of make_dataset from a recorded segment (agents/ippo_fused.py: DeviceRollout, filled by rs_group_rollout)
+        WITHOUT a second forward: logp and value are the ones the actor-critic kernel wrote when it drew the actions, GAE and the
+        per-signal standardisation are ONE call of the fused kernels (rs_ppo_gae).  last_value float32 [N, S] = the value of the
+        state after the last step (FusedIPPO.value), done [T] bool / uint8."""
+        from ..sim import load_library, torch_stream
+        obs, act, logp, val, rew = (rollout.cat(k) for k in ('obs', 'act', 'logp', 'value', 'rew'))
+        for t in (obs, act, logp, val, rew, last_value, done):
+            if not t.is_cuda:
+                raise RuntimeError('update_from_rollout needs device tensors: rs_ppo_gae is a HIP kernel (there is no CPU fallback)')
+        T, N, S = act.shape
+        assert tuple(last_value.shape) == (N, S) and last_value.dtype == torch.float32 and tuple(done.shape) == (T,)
+        val, rew, last_value = val.contiguous(), rew.contiguous(), last_value.contiguous()
+        done8 = done.to(torch.uint8).contiguous()
+        adv, ret = torch.empty_like(val), torch.empty_like(val)
+        scratch = torch.empty(N, S, dtype=torch.float32, device=val.device)
+        rc = load_library().rs_ppo_gae(rew.data_ptr(), val.data_ptr(), last_value.data_ptr(), done8.data_ptr(), T, N, S, float(self.gamma),
+                                       float(self.lambd), adv.data_ptr(), ret.data_ptr(), scratch.data_ptr(), torch_stream(val.device.index))
+        if rc != 0:
+            raise RuntimeError('rs_ppo_gae failed (%d)' % rc)
+        return dict(obs=obs.reshape(T * N, *obs.shape[2:]), act=act.reshape(T * N, S).long(), logp=logp.reshape(T * N, S),
+                    adv=adv.reshape(T * N, S), ret=ret.reshape(T * N, S))
+
+    def update_from_rollout(self, rollout, last_value, done, generator=None):
+        """update() on a segment the device recorded: dataset_from_rollout, then the unchanged loss / clip_grad_per_signal / Adam
+        loop.  CPU tensors raise.  logp_old here is the BEHAVIOUR policy's own log-probability -- that of the fp16 kernel which drew
+        the action -- where make_dataset re-evaluates the fp32 network: the ratio of the first minibatch is
+        exp(logp_fp32 - logp_kernel) instead of exactly 1 (largest |difference| measured on a recorded segment: 1.4e-4 on cologne1,
+        5.4e-4 on ingolstadt21, profiles/r08_ippo_device_rollout.txt); likewise V in the advantages is the kernel's value."""
+        return self._fit(self.dataset_from_rollout(rollout, last_value, done), generator)
+
+    def _fit(self, ds, generator=None):
         n = ds['act'].shape[0]
         last = None
         for _ in range(self.epochs):

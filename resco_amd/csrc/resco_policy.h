@@ -72,6 +72,7 @@ struct PolicySmem {         // 18 KB: the observation tile is dead once the lane
             __attribute__((aligned(16))) _Float16 ys[2][32][POL_C + 8];    // per row half: activations for the next layer's A fragments
             float qs[2][32][POL_QMAX];
             h2_t cwp[POL_C][8];         // the signal's conv weights as packed pairs: w00 w00 | w01 w01 | w10 w10 | w11 w11 | b b | - - -
+            float vs[2][32];            // actor-critic variant: the value head's output per row (column POL_QMAX of the fc3 tile)
         };
     };
 };
@@ -80,10 +81,20 @@ struct PolicySmem {         // 18 KB: the observation tile is dead once the lane
 // straight-line code, so the LDS fragment reads of later steps are issued ahead of the MFMAs of earlier ones.  The packed fc1
 // fragments keep the layout of the widest signal (W.hp k-steps per channel); a narrower signal reads the first HP of them -- the
 // others belong to padded lanes, whose fc1 rows are zero: skipping them changes no result.
-template <int HP>
+//
+// AC = the actor-critic variant (rs_ippo_forward_kernel): the trunk is the same code; the value head Linear(64, 1) rides as column
+// POL_QMAX of the fc3 tile (24 of its 32 columns are padding in every pack), and the epilogue keeps what PPO needs of the row the
+// action was drawn from.  `if constexpr` throughout: the Q / mode-1 kernel compiles to what it was without the variant.
+struct PolicyAC {           // outputs of the actor-critic epilogue, all [N][S] DEVICE pointers
+    int32_t *act2;          // a second copy of the actions (the rollout segment's slot next to RS_BUF_ACTIONS) or NULL
+    float *logp;            // log pi(a | s) of the drawn action, or NULL together with `actions`: value-only evaluation
+    float *value;
+};
+
+template <int HP, bool AC = false>
 __device__ __forceinline__ void
 idqn_forward_body(PolicySmem &sm, const PolicyTab &W, const __half *__restrict__ obs, int n_envs, int env_base, int mode, float eps, uint32_t seed,
-                  uint32_t step_key, int32_t *__restrict__ actions, float *__restrict__ q_out) {
+                  uint32_t step_key, int32_t *__restrict__ actions, float *__restrict__ q_out, const PolicyAC ac = PolicyAC{}) {
     auto &xs = sm.xs; auto &ys = sm.ys; auto &qs = sm.qs; auto &cwp = sm.cwp;
     const int s = blockIdx.y;
     const int m0 = blockIdx.x * POL_TM;
@@ -230,8 +241,44 @@ idqn_forward_body(PolicySmem &sm, const PolicyTab &W, const __half *__restrict__
 #pragma unroll
             for (int r = 0; r < 16; ++r) qs[mh][(r & 3) + 8 * (r >> 2) + 4 * g][i] = d0[r] + b3v;
         }
+        if constexpr (AC) {
+            if (i == POL_QMAX) {                // the value head's column: V = y2 . v_w + v_b, fp32 out of the same accumulator tile
+                const float b3v = W.b3[(size_t)s * 32 + POL_QMAX];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sm.vs[mh][(r & 3) + 8 * (r >> 2) + 4 * g] = d0[r] + b3v;
+            }
+        }
     }
     __syncthreads();
+    if constexpr (AC) {
+        // ---- per environment: a ~ softmax(logits) drawn EXACTLY as mode 1 below draws it (same hash words, same cumulative walk,
+        //      same order of the float additions: the actions are bit-identical to rs_idqn_act mode 1), its log-probability over the
+        //      signal's own actions, and the value.  actions == NULL: value only (the bootstrap value after a segment).
+        if (nh == 0 && lane < 32) {
+            const int m = m0 + mh * 32 + lane;
+            if (m < n_envs) {
+                const size_t o = (size_t)m * W.S + s;
+                const int na = W.n_actions[s];
+                ac.value[o] = sm.vs[mh][lane];
+                if (actions) {
+                    float bq = qs[mh][lane][0];
+                    for (int a = 1; a < na; ++a) { const float v = qs[mh][lane][a]; if (v > bq) bq = v; }
+                    float z = 0.0f;
+                    for (int a = 0; a < na; ++a) z += __expf(qs[mh][lane][a] - bq);
+                    const float u = d_u01(pol_hash(seed ^ 0x1D0A17u, (uint32_t)(env_base + m), (uint32_t)s, step_key, 2u)) * z;
+                    float cum = 0.0f;
+                    int act = na - 1;
+                    for (int a = 0; a < na; ++a) { cum += __expf(qs[mh][lane][a] - bq); if (u < cum) { act = a; break; } }
+                    actions[o] = act;
+                    if (ac.act2) ac.act2[o] = act;
+                    ac.logp[o] = qs[mh][lane][act] - bq - logf(z);
+                }
+                if (q_out)
+                    for (int a = 0; a < POL_QMAX; ++a) q_out[o * POL_QMAX + a] = a < na ? qs[mh][lane][a] : -INFINITY;
+            }
+        }
+        return;
+    }
     // ---- per environment: greedy action over the signal's actions, epsilon-greedy draw
     if (nh == 0 && lane < 32) {
         const int m = m0 + mh * 32 + lane;
@@ -281,5 +328,24 @@ rs_idqn_forward_kernel(PolicyTab W, const __half *__restrict__ obs, int n_envs, 
         case 6: idqn_forward_body<6>(sm, W, obs, n_envs, env_base, mode, eps, seed, step_key, actions, q_out); break;
         case 7: idqn_forward_body<7>(sm, W, obs, n_envs, env_base, mode, eps, seed, step_key, actions, q_out); break;
         default: idqn_forward_body<8>(sm, W, obs, n_envs, env_base, mode, eps, seed, step_key, actions, q_out); break;
+    }
+}
+
+// The actor-critic launch of the same trunk (rs_ippo_act, rs_group_rollout): a kernel of its own, so that the Q / mode-1 kernel above
+// keeps its code and its registers.  dyn != NULL: the step key comes from device memory (word 1, as above; word 0 is unused).
+__global__ void __launch_bounds__(256, POL_MINBLOCKS)
+rs_ippo_forward_kernel(PolicyTab W, const __half *__restrict__ obs, int n_envs, int env_base, uint32_t seed, uint32_t step_key,
+                       const uint32_t *__restrict__ dyn, int32_t *__restrict__ actions, float *__restrict__ logits, PolicyAC ac) {
+    if (dyn) step_key = dyn[1];
+    __shared__ PolicySmem sm;
+    switch (__builtin_amdgcn_readfirstlane(W.hp_sig[blockIdx.y])) {
+        case 1: idqn_forward_body<1, true>(sm, W, obs, n_envs, env_base, 1, 0.0f, seed, step_key, actions, logits, ac); break;
+        case 2: idqn_forward_body<2, true>(sm, W, obs, n_envs, env_base, 1, 0.0f, seed, step_key, actions, logits, ac); break;
+        case 3: idqn_forward_body<3, true>(sm, W, obs, n_envs, env_base, 1, 0.0f, seed, step_key, actions, logits, ac); break;
+        case 4: idqn_forward_body<4, true>(sm, W, obs, n_envs, env_base, 1, 0.0f, seed, step_key, actions, logits, ac); break;
+        case 5: idqn_forward_body<5, true>(sm, W, obs, n_envs, env_base, 1, 0.0f, seed, step_key, actions, logits, ac); break;
+        case 6: idqn_forward_body<6, true>(sm, W, obs, n_envs, env_base, 1, 0.0f, seed, step_key, actions, logits, ac); break;
+        case 7: idqn_forward_body<7, true>(sm, W, obs, n_envs, env_base, 1, 0.0f, seed, step_key, actions, logits, ac); break;
+        default: idqn_forward_body<8, true>(sm, W, obs, n_envs, env_base, 1, 0.0f, seed, step_key, actions, logits, ac); break;
     }
 }

@@ -579,6 +579,12 @@ class VecMultiSignal:
         obs, rew = self._pack()
         return obs, rew, self.steps >= self.horizon_steps, {'steps': self.steps}
 
+    def advance(self, n_steps):
+        """n_steps env-steps were taken on the simulator behind this wrapper's back (SimGroup.step / SimGroup.rollout on self.sim):
+        keep the episode's step counter -- and with it `done` -- right.  Returns done."""
+        self.steps += int(n_steps)
+        return self.steps >= self.horizon_steps
+
     def sync(self):
         self.sim.sync()
 

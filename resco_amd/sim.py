@@ -32,7 +32,8 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_act_maxwave', 'rs_get_buffer', 'rs_read_buffer', 'rs_stats', 'rs_snapshot', 'rs_restore',
                'rs_snapshot_free', 'rs_timing', 'rs_timing_read', 'rs_set_seed', 'rs_phase_profile', 'rs_info',
                'rs_idqn_create', 'rs_idqn_act', 'rs_idqn_set_device_weights', 'rs_idqn_set_lanes', 'rs_idqn_destroy', 'rs_group_step',
-               'rs_default_block', 'rs_mplight_create', 'rs_mplight_act', 'rs_mplight_set_device_weights', 'rs_mplight_destroy']
+               'rs_default_block', 'rs_mplight_create', 'rs_mplight_act', 'rs_mplight_set_device_weights', 'rs_mplight_destroy',
+               'rs_ippo_act', 'rs_group_rollout', 'rs_ppo_gae']
 
 _lib = None
 
@@ -67,6 +68,11 @@ def bind(L):
     L.rs_phase_profile.argtypes = [vp, i32, vp]
     L.rs_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.rs_group_step.argtypes = [vp, i32, vp, i32]
+    if hasattr(L, 'rs_group_rollout'):
+        u32, f32 = C.c_uint32, C.c_float
+        L.rs_ippo_act.argtypes = [vp, vp, i32, i32, u32, u32, vp, vp, vp, vp, vp, vp]
+        L.rs_group_rollout.argtypes = [vp, i32, vp, vp, i32, i32]
+        L.rs_ppo_gae.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp]
     if hasattr(L, 'rs_default_block'):      # (the host emulation of the CPU tests exports only what it implements)
         L.rs_default_block.argtypes = [i32, i32, i32]
         L.rs_default_block.restype = i32
@@ -93,13 +99,18 @@ def load_library():
     return _lib
 
 
-AGENT = {'none': 0, 'random': 1, 'maxwave': 2, 'maxpressure': 3, 'idqn': 4, 'mplight': 5}      # enum rs_agent
+AGENT = {'none': 0, 'random': 1, 'maxwave': 2, 'maxpressure': 3, 'idqn': 4, 'mplight': 5, 'ippo': 6}      # enum rs_agent
 
 
 class GroupAgent(C.Structure):
     """ctypes mirror of rs_group_agent (include/resco_sim.h)"""
     _fields_ = [('kind', C.c_int32), ('step_key', C.c_uint32), ('policy', C.c_void_p), ('mode', C.c_int32),
                 ('epsilon', C.c_float), ('epsilon_step', C.c_float), ('seed', C.c_uint32)]
+
+
+class Rollout(C.Structure):
+    """ctypes mirror of rs_rollout (include/resco_sim.h): the device buffers of one handle's trajectory segment"""
+    _fields_ = [('obs', C.c_void_p), ('act', C.c_void_p), ('logp', C.c_void_p), ('value', C.c_void_p), ('rew', C.c_void_p), ('T', C.c_int32)]
 
 
 class SimGroup:
@@ -125,6 +136,19 @@ class SimGroup:
         if rc != 0:
             msgs = [m.decode() for m in (self._lib.rs_last_error(s._h) for s in self.sims) if m]
             raise RuntimeError('rs_group_step failed (%d): %s' % (rc, '; '.join(msgs)))
+
+    def rollout(self, rollout, policy, t0=0, n_steps=1, step_key=0, seed=0):
+        """rs_group_rollout: n_steps env-steps of every pipe under the IPPO actor-critic kernel (policy = FusedIPPO.handle), recorded
+        into slots t0 .. t0 + n_steps - 1 of `rollout` (agents/ippo_fused.py: DeviceRollout over these sims).  Asynchronous, on the
+        pipes' own streams: sync() before the segments are read."""
+        a = self._agent
+        a.kind, a.step_key, a.policy = AGENT['ippo'], int(step_key) & 0xFFFFFFFF, policy
+        a.mode, a.epsilon, a.epsilon_step, a.seed = 0, 0.0, 0.0, int(seed) & 0xFFFFFFFF
+        segs = rollout.segments(self.sims)
+        rc = self._lib.rs_group_rollout(self._hs, len(self.sims), C.byref(a), segs, int(t0), int(n_steps))
+        if rc != 0:
+            msgs = [m.decode() for m in (self._lib.rs_last_error(s._h) for s in self.sims) if m]
+            raise RuntimeError('rs_group_rollout failed (%d): %s' % (rc, '; '.join(msgs)))
 
     def sync(self):
         for s in self.sims:

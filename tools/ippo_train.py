@@ -2,7 +2,11 @@
 """IPPO training loop on the GPU: HIP simulator -> fp16 observations -> fused HIP policy kernel in sampling mode
 (rs_idqn_act, mode 1) -> rollout segment in HBM -> batched PPO update (PyTorch) -> weights re-packed on the device.
 
-    python tools/ippo_train.py [map] [n_envs] [episodes] [segment_steps] [minibatches_per_epoch]
+    python tools/ippo_train.py [--device-rollout] [map] [n_envs] [episodes] [segment_steps] [minibatches_per_epoch]
+
+--device-rollout: the segment is recorded on the device by the group path (rs_group_rollout: actor-critic kernel, step kernel and
+recorder, `segment_steps` env-steps per call through the ABI), the update takes logp / value from the recording and GAE from the
+fused kernel (BatchedPPOLearner.update_from_rollout) -- no Python work per env-step, no second forward over the segment.
 
 Prints one JSON line per episode (average trip delay as utils/readXML.py computes it, env-steps/s including
 learning).  The reference's IPPO learns far more slowly than its IDQN (1400 published episodes); this tool shows the
@@ -18,7 +22,51 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from resco_amd.agents.idqn_fused import FusedIDQN                   # noqa: E402
 from resco_amd.agents.ippo import BatchedIPPO, BatchedPPOLearner      # noqa: E402
+from resco_amd.agents.ippo_fused import DeviceRollout, FusedIPPO      # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                     # noqa: E402
+from resco_amd.sim import SimGroup                                    # noqa: E402
+
+
+def report(env, learner, ep, n, steps, dt):
+    print(json.dumps(dict(episode=ep, avg_delay_s=round(float(env.sim.trip_delay().mean()), 2),
+                          arrived_per_env=round(float(env.sim.stats()['arrived'].mean()), 1), adam_steps=learner.n_updates,
+                          env_steps_per_s=round(n * steps / dt), ms_per_step=round(dt / steps * 1e3, 3))), flush=True)
+
+
+def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
+    env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0)
+    steps = env.horizon_steps
+    net = BatchedIPPO.from_scenario(env.scenario, dtype=torch.float32, device='cuda')
+    net.init_like_reference(seed=0)
+    learner = BatchedPPOLearner(net, minibatch=max(256, seg * n // mbs))
+    policy = FusedIPPO(net, seed=3)
+    policy.refresh_on_device()
+    grp, rec = SimGroup([env.sim]), DeviceRollout(seg, [env.sim])
+    obs = env.tensor('drq_norm_f16')
+    done = [False] * seg
+    gen = torch.Generator(device='cuda').manual_seed(0)
+    t_global, i = 0, 0
+    for ep in range(episodes):
+        env.sim.set_seed(1000 + ep)
+        env.reset()
+        torch.cuda.synchronize()                # (the rollout runs on the handle's own stream, the reset ran on torch's)
+        t0 = time.perf_counter()
+        k = 0
+        while k < steps:
+            m = min(seg - i, steps - k)
+            grp.rollout(rec, policy.handle, t0=i, n_steps=m, step_key=t_global, seed=policy.seed)
+            k, i, t_global = k + m, i + m, t_global + m
+            done[i - 1] = env.advance(m)
+            if i == seg:
+                grp.sync()
+                learner.update_from_rollout(rec, policy.value(obs), torch.as_tensor(done, device='cuda'), generator=gen)
+                policy.refresh_on_device()
+                torch.cuda.current_stream().synchronize()       # the next rollout reads the re-packed weights on another stream
+                done, i = [False] * seg, 0
+        grp.sync()
+        torch.cuda.synchronize()
+        report(env, learner, ep, n, steps, time.perf_counter() - t0)
+    env.close()
 
 
 def main(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
@@ -56,14 +104,12 @@ def main(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
                 policy.refresh_on_device()
                 i = 0
         torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        print(json.dumps(dict(episode=ep, avg_delay_s=round(float(env.sim.trip_delay().mean()), 2),
-                              arrived_per_env=round(float(env.sim.stats()['arrived'].mean()), 1), adam_steps=learner.n_updates,
-                              env_steps_per_s=round(n * steps / dt), ms_per_step=round(dt / steps * 1e3, 3))), flush=True)
+        report(env, learner, ep, n, steps, time.perf_counter() - t0)
     env.close()
 
 
 if __name__ == '__main__':
-    a = sys.argv[1:]
-    main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 20,
-         int(a[3]) if len(a) > 3 else 30, int(a[4]) if len(a) > 4 else 4)
+    a = [x for x in sys.argv[1:] if x != '--device-rollout']
+    run = main_device_rollout if '--device-rollout' in sys.argv[1:] else main
+    run(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 20,
+        int(a[3]) if len(a) > 3 else 30, int(a[4]) if len(a) > 4 else 4)
