@@ -385,6 +385,48 @@ int rs_ppo_gae(const float *rew, const float *value, const float *last_value, co
                int32_t T, int32_t n_envs, int32_t n_signals, float gamma, float lambda,
                float *adv /* standardised per signal */, float *ret, void *scratch, void *stream);
 
+/* ---- IPPO: the PPO update on the device (resco_amd/csrc/resco_ppo_train.h) ------------------------------------------
+ * What resco_amd/agents/ippo.py BatchedPPOLearner._fit does per minibatch -- loss(), its backward through the S stacked
+ * actor-critics, clip_grad_per_signal, torch.optim.Adam(lr, eps) (bias-corrected, no weight decay) -- as five launches, all in
+ * fp32, every signal at its own lane and action count.  rs_ppo_tensors: ten DEVICE pointers in BatchedIPPO's own layouts (fp32,
+ * contiguous).  The four sets are caller-owned: params are the network's own storages and are updated in place; grads, m and v
+ * start as zeros; rows of fc1_w of padded lanes and columns of fc3_w / fc3_b of padded actions are never read or written.  The
+ * library owns the workspace (sized by max_minibatch) and the step counter t.
+ *
+ * rs_ppo_grad: the gradient of one minibatch into grads.  Row i of the minibatch is dataset row idx[i] (device int32 [B]); obs f16
+ * [n][S][lmax][5], act int32 / logp / adv / ret float [n][S]; the means are over B.  loss_out: NULL or device float [S][3] = the
+ * policy term, (value - ret)^2 and the entropy of every signal, un-weighted.
+ * rs_ppo_step: per signal min(1, max_grad_norm / (norm + 1e-6)), then Adam on what grads holds (grads itself stays un-scaled);
+ * advances t.  rs_ppo_steps: t.
+ * rs_ppo_fit: for e < epochs, for i = 0, minibatch, .. < n: rs_ppo_grad on perm[e][i : i + minibatch] (device int32 [epochs][n];
+ * the last minibatch may be short), then rs_ppo_step -- the same launches, enqueued by one call; loss_out holds the last one's.
+ * Fixed summation order, no atomics: the same state and data give the same bits.  Everything is launched on `stream`.
+ * NOT checked: the ABI carries no shapes of the data, so n, S and lmax of obs / act / logp / adv / ret are the caller's word (the
+ * Python wrapper checks them against the network); the values of idx and perm are trusted to lie in 0 .. n - 1 (an index outside
+ * reads outside the dataset); an action outside 0 .. A_s - 1 is clamped into it.  A step whose launch fails does not advance t.
+ * Workspace, allocated once by rs_ppo_create and padded to lmax for every signal: dz1 S * B' * 256 B, per-tile partials S * B' / 64 *
+ * 19 KB, per-chunk partials of fc1_w ceil(B' / 512) * S * (lmax - 1) * 64 KB (B' = max_minibatch rounded up to 64): 22 MB per chunk
+ * and 330 MB in all on ingolstadt21 (21 signals, lmax 17) at max_minibatch 7680.
+ * Refusals (RS_EINVAL, text in rs_last_error(NULL), nothing launched): a NULL handle or pointer, B or minibatch outside
+ * 1 .. max_minibatch, n < 1, epochs < 1; rs_ppo_create: lmax outside 2 .. 17, amax outside 1 .. 8, lanes / actions outside theirs. */
+typedef struct rs_ppo *rs_ppo_handle;
+typedef struct rs_ppo_tensors {
+    float *conv_w, *conv_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b, *fc3_w, *fc3_b, *v_w, *v_b;
+} rs_ppo_tensors;
+typedef struct rs_ppo_config {   /* doubles: torch forms lr / (1 - beta1^t), sqrt(1 - beta2^t), 1 - beta in double before it rounds */
+    double lr, adam_eps, beta1, beta2, clip_eps, entropy_coef, value_coef, max_grad_norm;
+} rs_ppo_config;
+int rs_ppo_create(int32_t device_id, int32_t n_signals, int32_t lmax, const int32_t *lanes, const int32_t *n_actions, int32_t amax,
+                  const rs_ppo_config *config, const rs_ppo_tensors *params, const rs_ppo_tensors *grads, const rs_ppo_tensors *m,
+                  const rs_ppo_tensors *v, int32_t max_minibatch, rs_ppo_handle *out);
+int rs_ppo_grad(rs_ppo_handle p, const void *obs, const int32_t *act, const float *logp, const float *adv, const float *ret,
+                const int32_t *idx, int32_t B, float *loss_out, void *stream);
+int rs_ppo_step(rs_ppo_handle p, void *stream);
+int rs_ppo_fit(rs_ppo_handle p, const void *obs, const int32_t *act, const float *logp, const float *adv, const float *ret, int32_t n,
+               const int32_t *perm, int32_t epochs, int32_t minibatch, float *loss_out, void *stream);
+int64_t rs_ppo_steps(rs_ppo_handle p);
+void rs_ppo_destroy(rs_ppo_handle p);
+
 /* static facts */
 int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal);
 

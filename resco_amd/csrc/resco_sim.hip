@@ -23,6 +23,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <math.h>
 #include <mutex>
 #include <new>
 #include <string>
@@ -109,6 +110,7 @@ __device__ unsigned long long *g_sec_prof;
 #include "resco_policy.h"
 #include "resco_frap.h"
 #include "resco_ppo.h"
+#include "resco_ppo_train.h"
 
 // ------------------------------------------------------------------------------------------------ kernels
 // The tables / state / output descriptors live in ONE constant block in device memory (StepArgs): passed by value they
@@ -800,6 +802,135 @@ extern "C" int rs_ppo_gae(const float *rew, const float *value, const float *las
     hipLaunchKernelGGL(rs_ppo_standardise_kernel, dim3(n_signals), dim3(PPO_B), 0, (hipStream_t)stream, A);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
 }
+
+// ---- PPO: the update itself (resco_ppo_train.h).  The four tensor sets are the caller's; the library owns the workspace and t.
+struct rs_ppo {
+    int device = 0;
+    PpoTrainTab T{};
+    rs_ppo_config cfg{};
+    int max_minibatch = 0;
+    long long t = 0;            // Adam steps taken
+    std::vector<void *> allocs;
+};
+
+extern "C" void rs_ppo_destroy(rs_ppo_handle p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    (void)hipDeviceSynchronize();
+    for (void *d : p->allocs) (void)hipFree(d);
+    delete p;
+}
+
+static bool ppo_tensors_complete(const rs_ppo_tensors *t) {
+    return t && t->conv_w && t->conv_b && t->fc1_w && t->fc1_b && t->fc2_w && t->fc2_b && t->fc3_w && t->fc3_b && t->v_w && t->v_b;
+}
+static PpoTensors ppo_tensors(const rs_ppo_tensors *t) {
+    return PpoTensors{{t->conv_w, t->conv_b, t->fc1_w, t->fc1_b, t->fc2_w, t->fc2_b, t->fc3_w, t->fc3_b, t->v_w, t->v_b}};
+}
+
+extern "C" int rs_ppo_create(int32_t device_id, int32_t n_signals, int32_t lmax, const int32_t *lanes, const int32_t *n_actions, int32_t amax,
+                             const rs_ppo_config *cfg, const rs_ppo_tensors *params, const rs_ppo_tensors *grads, const rs_ppo_tensors *m,
+                             const rs_ppo_tensors *v, int32_t max_minibatch, rs_ppo_handle *out) {
+    if (!out) return RS_EINVAL;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_err = "no HIP device visible (this library has no CPU fallback)"; return RS_EHIP; }
+    if (device_id < 0 || device_id >= ndev || n_signals <= 0 || lmax < 2 || lmax > 17 || amax < 1 || amax > PPT_AMAX || !lanes || !n_actions || !cfg ||
+        max_minibatch < 1) {
+        g_create_err = "rs_ppo_create: bad argument (1 <= signals, 2 <= lmax <= 17, 1 <= amax <= 8, 1 <= max_minibatch)"; return RS_EINVAL;
+    }
+    if (!ppo_tensors_complete(params) || !ppo_tensors_complete(grads) || !ppo_tensors_complete(m) || !ppo_tensors_complete(v)) {
+        g_create_err = "rs_ppo_create: a tensor pointer is NULL"; return RS_EINVAL;
+    }
+    for (int s = 0; s < n_signals; ++s)
+        if (lanes[s] < 2 || lanes[s] > lmax || n_actions[s] < 1 || n_actions[s] > amax) {
+            g_create_err = "rs_ppo_create: 2 <= lanes[s] <= lmax and 1 <= n_actions[s] <= amax"; return RS_EINVAL;
+        }
+    if (hipSetDevice(device_id) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RS_EHIP; }
+    rs_ppo *p = new (std::nothrow) rs_ppo();
+    if (!p) return RS_ENOMEM;
+    p->device = device_id; p->max_minibatch = max_minibatch;
+    PpoTrainTab &T = p->T;
+    T.S = n_signals; T.lmax = lmax; T.amax = amax; T.H = lmax - 1;
+    T.par = ppo_tensors(params); T.grad = ppo_tensors(grads); T.m = ppo_tensors(m); T.v = ppo_tensors(v);
+    p->cfg = *cfg;
+    T.hp = PpoHyper{(float)cfg->clip_eps, (float)cfg->entropy_coef, (float)cfg->value_coef};
+    T.tiles_max = (max_minibatch + PPT_TM - 1) / PPT_TM;
+    T.bpad_max = T.tiles_max * PPT_TM;
+    T.chunks_max = (T.bpad_max + PPT_CH - 1) / PPT_CH;
+    const size_t S = (size_t)n_signals, H = (size_t)T.H;
+    auto dev_alloc = [&](void **d, size_t bytes) {
+        if (hipMalloc(d, bytes) != hipSuccess) return false;
+        p->allocs.push_back(*d);
+        return true;
+    };
+    void *d_lanes = nullptr, *d_act = nullptr;
+    if (!dev_alloc(&d_lanes, S * 4) || !dev_alloc(&d_act, S * 4) || !dev_alloc((void **)&T.dz1, S * T.bpad_max * 64 * sizeof(float)) ||
+        !dev_alloc((void **)&T.part, S * T.tiles_max * PPT_P_SIZE * sizeof(float)) ||
+        !dev_alloc((void **)&T.pw1, (size_t)T.chunks_max * S * H * 256 * 64 * sizeof(float)) ||
+        !dev_alloc((void **)&T.pconv, (size_t)T.chunks_max * S * H * 64 * 5 * sizeof(float)) || !dev_alloc((void **)&T.sqpart, S * (H + 1) * 2 * sizeof(float)) ||
+        hipMemcpy(d_lanes, lanes, S * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_act, n_actions, S * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        g_create_err = "rs_ppo_create: device allocation / upload failed";
+        (void)hipGetLastError();
+        rs_ppo_destroy(p);
+        return RS_ENOMEM;
+    }
+    T.lanes = (const int32_t *)d_lanes; T.n_actions = (const int32_t *)d_act;
+    *out = p;
+    return RS_OK;
+}
+
+// the launches of one minibatch gradient; the arguments have been checked
+static void ppo_grad_launch(const rs_ppo *p, const PpoBatch &D, float *loss_out, hipStream_t st) {
+    const PpoTrainTab &T = p->T;
+    const int tiles = (D.B + PPT_TM - 1) / PPT_TM, chunks = (tiles * PPT_TM + PPT_CH - 1) / PPT_CH;
+    hipLaunchKernelGGL(ppo_fwd_bwd_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
+    hipLaunchKernelGGL(ppo_fc1_bwd_kernel, dim3(T.H * 2, chunks, T.S), dim3(PPT_T), 0, st, T, D);
+    hipLaunchKernelGGL(ppo_reduce_kernel, dim3(T.S, T.H + (PPT_N_SMALL + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, T, D.B, loss_out);
+}
+static void ppo_step_launch(rs_ppo *p, hipStream_t st) {
+    const PpoTrainTab &T = p->T;
+    const PpoStepConsts K = ppo_step_consts(p->cfg.lr, p->cfg.adam_eps, p->cfg.beta1, p->cfg.beta2, p->cfg.max_grad_norm, p->t + 1);
+    hipLaunchKernelGGL(ppo_norm_kernel, dim3(T.S, T.H + 1), dim3(PPT_T), 0, st, T);
+    hipLaunchKernelGGL(ppo_adam_kernel, dim3(T.S, T.H + 1), dim3(PPT_T), 0, st, T, K);
+    if (hipPeekAtLastError() == hipSuccess) p->t += 1;      // a step that could not be launched is not counted
+}
+
+extern "C" int rs_ppo_grad(rs_ppo_handle p, const void *obs, const int32_t *act, const float *logp, const float *adv, const float *ret,
+                           const int32_t *idx, int32_t B, float *loss_out, void *stream) {
+    if (!p) { g_create_err = "rs_ppo_grad: NULL handle"; return RS_EINVAL; }
+    if (!obs || !act || !logp || !adv || !ret || !idx) { g_create_err = "rs_ppo_grad: a data pointer is NULL"; return RS_EINVAL; }
+    if (B < 1 || B > p->max_minibatch) { g_create_err = "rs_ppo_grad: need 1 <= B <= max_minibatch of rs_ppo_create"; return RS_EINVAL; }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    ppo_grad_launch(p, PpoBatch{(const __half *)obs, act, logp, adv, ret, idx, B}, loss_out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_ppo_step(rs_ppo_handle p, void *stream) {
+    if (!p) { g_create_err = "rs_ppo_step: NULL handle"; return RS_EINVAL; }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    ppo_step_launch(p, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_ppo_fit(rs_ppo_handle p, const void *obs, const int32_t *act, const float *logp, const float *adv, const float *ret, int32_t n,
+                          const int32_t *perm, int32_t epochs, int32_t minibatch, float *loss_out, void *stream) {
+    if (!p) { g_create_err = "rs_ppo_fit: NULL handle"; return RS_EINVAL; }
+    if (!obs || !act || !logp || !adv || !ret || !perm) { g_create_err = "rs_ppo_fit: a data pointer is NULL"; return RS_EINVAL; }
+    if (n < 1 || epochs < 1 || minibatch < 1 || minibatch > p->max_minibatch) {
+        g_create_err = "rs_ppo_fit: need 1 <= n, 1 <= epochs, 1 <= minibatch <= max_minibatch of rs_ppo_create"; return RS_EINVAL;
+    }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    for (int e = 0; e < epochs; ++e)
+        for (int i = 0; i < n; i += minibatch) {
+            const int B = n - i < minibatch ? n - i : minibatch;
+            ppo_grad_launch(p, PpoBatch{(const __half *)obs, act, logp, adv, ret, perm + (size_t)e * n + i, B}, loss_out, (hipStream_t)stream);
+            ppo_step_launch(p, (hipStream_t)stream);
+        }
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int64_t rs_ppo_steps(rs_ppo_handle p) { return p ? (int64_t)p->t : -1; }
 
 // ------------------------------------------------------------------------------------------------ fused MPLight (FRAP) policy
 static void mplight_launch(const FrapTab &F, const void *obs, int n_envs, int env_base, float eps, uint32_t seed, uint32_t step_key,

@@ -33,7 +33,8 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_snapshot_free', 'rs_timing', 'rs_timing_read', 'rs_set_seed', 'rs_phase_profile', 'rs_info',
                'rs_idqn_create', 'rs_idqn_act', 'rs_idqn_set_device_weights', 'rs_idqn_set_lanes', 'rs_idqn_destroy', 'rs_group_step',
                'rs_default_block', 'rs_mplight_create', 'rs_mplight_act', 'rs_mplight_set_device_weights', 'rs_mplight_destroy',
-               'rs_ippo_act', 'rs_group_rollout', 'rs_ppo_gae']
+               'rs_ippo_act', 'rs_group_rollout', 'rs_ppo_gae',
+               'rs_ppo_create', 'rs_ppo_grad', 'rs_ppo_step', 'rs_ppo_fit', 'rs_ppo_steps', 'rs_ppo_destroy']
 
 _lib = None
 
@@ -73,6 +74,15 @@ def bind(L):
         L.rs_ippo_act.argtypes = [vp, vp, i32, i32, u32, u32, vp, vp, vp, vp, vp, vp]
         L.rs_group_rollout.argtypes = [vp, i32, vp, vp, i32, i32]
         L.rs_ppo_gae.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp]
+    if hasattr(L, 'rs_ppo_create'):
+        L.rs_ppo_create.argtypes = [i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, C.POINTER(vp)]
+        L.rs_ppo_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+        L.rs_ppo_step.argtypes = [vp, vp]
+        L.rs_ppo_fit.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp]
+        L.rs_ppo_steps.argtypes = [vp]
+        L.rs_ppo_steps.restype = C.c_int64
+        L.rs_ppo_destroy.argtypes = [vp]
+        L.rs_ppo_destroy.restype = None
     if hasattr(L, 'rs_default_block'):      # (the host emulation of the CPU tests exports only what it implements)
         L.rs_default_block.argtypes = [i32, i32, i32]
         L.rs_default_block.restype = i32
@@ -111,6 +121,19 @@ class GroupAgent(C.Structure):
 class Rollout(C.Structure):
     """ctypes mirror of rs_rollout (include/resco_sim.h): the device buffers of one handle's trajectory segment"""
     _fields_ = [('obs', C.c_void_p), ('act', C.c_void_p), ('logp', C.c_void_p), ('value', C.c_void_p), ('rew', C.c_void_p), ('T', C.c_int32)]
+
+
+PPO_TENSORS = ('conv_w', 'conv_b', 'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b', 'fc3_w', 'fc3_b', 'v_w', 'v_b')
+
+
+class PPOTensors(C.Structure):
+    """ctypes mirror of rs_ppo_tensors (include/resco_sim.h): ten device pointers in BatchedIPPO's layouts"""
+    _fields_ = [(k, C.c_void_p) for k in PPO_TENSORS]
+
+
+class PPOConfig(C.Structure):
+    """ctypes mirror of rs_ppo_config (include/resco_sim.h)"""
+    _fields_ = [(k, C.c_double) for k in ('lr', 'adam_eps', 'beta1', 'beta2', 'clip_eps', 'entropy_coef', 'value_coef', 'max_grad_norm')]
 
 
 class SimGroup:

@@ -6,7 +6,8 @@
         sim + actor-critic + recorder (rs_group_rollout), alternating, median and range over `reps` windows of `steps` steps.
         RESCO_SIM_LIB=variants/<name>.so measures another build of the library (tools/ab.py build), e.g. the recorder variants.
     python tools/ippo_rollout_bench.py update  [map] [envs] [segment_steps] [reps]
-        one BatchedPPOLearner.update against one update_from_rollout on the same recorded segment (median ms and range), and the
+        one BatchedPPOLearner.update against one update_from_rollout and one FusedPPOLearner.update_from_rollout (the update on the
+        device, rs_ppo_fit) on the same recorded segment (median ms and range), and the
         largest |logp_kernel - logp_fp32net| and |value_kernel - value_fp32net| of that segment.
     python tools/ippo_rollout_bench.py kernels [map] [envs ...]
         launches rs_idqn_act mode 1 and rs_ippo_act 50 times each per batch size: run it under
@@ -26,6 +27,7 @@ sys.path.insert(0, ROOT)
 from resco_amd.agents.idqn_fused import FusedIDQN                    # noqa: E402
 from resco_amd.agents.ippo import BatchedIPPO, BatchedPPOLearner      # noqa: E402
 from resco_amd.agents.ippo_fused import DeviceRollout, FusedIPPO      # noqa: E402
+from resco_amd.agents.ippo_learn_fused import FusedPPOLearner         # noqa: E402
 from resco_amd.multi_signal import load_scenario                      # noqa: E402
 from resco_amd.sim import BatchedSim, SimGroup                        # noqa: E402
 
@@ -98,10 +100,11 @@ def update(map_name='cologne1', n=256, seg=30, reps=5):
         gap_lp = (lp - p['logp']).abs().max().item()
         gap_v = (v.float().reshape(seg, n, -1) - p['value']).abs().max().item()
         vmax = p['value'].abs().max().item()
-    ms = {'update': [], 'update_from_rollout': []}
+    ms = {'update': [], 'update_from_rollout': [], 'fused update_from_rollout': []}
     for rep in range(reps + 1):
         for name in ms:
-            learner = BatchedPPOLearner(copy.deepcopy(net), minibatch=max(256, seg * n // 4))
+            cls = FusedPPOLearner if name.startswith('fused') else BatchedPPOLearner
+            learner = cls(copy.deepcopy(net), minibatch=max(256, seg * n // 4))
             gen = torch.Generator(device='cuda').manual_seed(0)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -112,6 +115,8 @@ def update(map_name='cologne1', n=256, seg=30, reps=5):
             torch.cuda.synchronize()
             if rep:
                 ms[name].append((time.perf_counter() - t0) * 1e3)
+            if name.startswith('fused'):
+                learner.close()
     # the dataset alone (what the two paths differ in; the Adam loop is the same code)
     learner = BatchedPPOLearner(copy.deepcopy(net))
     ds = {'make_dataset': [], 'dataset_from_rollout': []}

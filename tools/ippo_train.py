@@ -2,11 +2,15 @@
 """IPPO training loop on the GPU: HIP simulator -> fp16 observations -> fused HIP policy kernel in sampling mode
 (rs_idqn_act, mode 1) -> rollout segment in HBM -> batched PPO update (PyTorch) -> weights re-packed on the device.
 
-    python tools/ippo_train.py [--device-rollout] [map] [n_envs] [episodes] [segment_steps] [minibatches_per_epoch]
+    python tools/ippo_train.py [--device-rollout] [--device-update] [map] [n_envs] [episodes] [segment_steps] [minibatches_per_epoch]
 
 --device-rollout: the segment is recorded on the device by the group path (rs_group_rollout: actor-critic kernel, step kernel and
 recorder, `segment_steps` env-steps per call through the ABI), the update takes logp / value from the recording and GAE from the
 fused kernel (BatchedPPOLearner.update_from_rollout) -- no Python work per env-step, no second forward over the segment.
+
+--device-update (implies --device-rollout): the PPO update itself runs on the device too (FusedPPOLearner: loss, backward,
+per-signal clipping and Adam in HIP kernels, rs_ppo_fit -- one call through the ABI per update instead of ~200 launches per Adam
+step).
 
 Prints one JSON line per episode (average trip delay as utils/readXML.py computes it, env-steps/s including
 learning).  The reference's IPPO learns far more slowly than its IDQN (1400 published episodes); this tool shows the
@@ -23,6 +27,7 @@ sys.path.insert(0, ROOT)
 from resco_amd.agents.idqn_fused import FusedIDQN                   # noqa: E402
 from resco_amd.agents.ippo import BatchedIPPO, BatchedPPOLearner      # noqa: E402
 from resco_amd.agents.ippo_fused import DeviceRollout, FusedIPPO      # noqa: E402
+from resco_amd.agents.ippo_learn_fused import FusedPPOLearner         # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                     # noqa: E402
 from resco_amd.sim import SimGroup                                    # noqa: E402
 
@@ -33,12 +38,12 @@ def report(env, learner, ep, n, steps, dt):
                           env_steps_per_s=round(n * steps / dt), ms_per_step=round(dt / steps * 1e3, 3))), flush=True)
 
 
-def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
+def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, device_update=False):
     env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0)
     steps = env.horizon_steps
     net = BatchedIPPO.from_scenario(env.scenario, dtype=torch.float32, device='cuda')
     net.init_like_reference(seed=0)
-    learner = BatchedPPOLearner(net, minibatch=max(256, seg * n // mbs))
+    learner = (FusedPPOLearner if device_update else BatchedPPOLearner)(net, minibatch=max(256, seg * n // mbs))
     policy = FusedIPPO(net, seed=3)
     policy.refresh_on_device()
     grp, rec = SimGroup([env.sim]), DeviceRollout(seg, [env.sim])
@@ -109,7 +114,9 @@ def main(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
 
 
 if __name__ == '__main__':
-    a = [x for x in sys.argv[1:] if x != '--device-rollout']
-    run = main_device_rollout if '--device-rollout' in sys.argv[1:] else main
+    flags = ('--device-rollout', '--device-update')
+    a = [x for x in sys.argv[1:] if x not in flags]
+    run = main_device_rollout if any(f in sys.argv[1:] for f in flags) else main
+    kw = dict(device_update=True) if '--device-update' in sys.argv[1:] else {}
     run(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 20,
-        int(a[3]) if len(a) > 3 else 30, int(a[4]) if len(a) > 4 else 4)
+        int(a[3]) if len(a) > 3 else 30, int(a[4]) if len(a) > 4 else 4, **kw)
