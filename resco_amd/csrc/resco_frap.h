@@ -122,11 +122,13 @@ RS_HD inline float frap_lane_y(WP w, int D, const float Ai[FRAP_C], const float 
     return y;
 }
 
-// 1 when phase pairs i and j share exactly one movement (mplight.py:19-28)
+// 1 when phase pairs i and j name exactly three distinct movements (mplight.py:19-28: len(set(pair_a + pair_b)) == 3).  For pairs of
+// two distinct movements that is "they share one"; a pair that names one movement twice ([3, 3] against [4, 5]) counts as the
+// reference counts it
 RS_HD inline int frap_comp(const int32_t *pairs, int i, int j) {
     const int a0 = pairs[2 * i], a1 = pairs[2 * i + 1], b0 = pairs[2 * j], b1 = pairs[2 * j + 1];
-    const int shared = (a0 == b0 || a0 == b1) + (a1 == b0 || a1 == b1);
-    return shared == 1;
+    const int distinct = 1 + (a1 != a0) + (b0 != a0 && b0 != a1) + (b1 != a0 && b1 != a1 && b1 != b0);
+    return distinct == 3;
 }
 
 // the exploration draw of a row: returns -1 (greedy) or k in [0, n_valid): the k-th entry of the signal's valid list

@@ -1,7 +1,8 @@
 // frap_host.cpp -- the per-lane pieces of the fused MPLight kernel (resco_amd/csrc/resco_frap.h), compiled for the HOST (TEST
 // INFRASTRUCTURE, never shipped).  frap_rows runs the lanes of every row one after the other and glues them as the kernel's
 // frap_body does with shuffles: Q_i = sum over j != i of y_ij, the first maximum over the valid pairs in dict order, the
-// epsilon-greedy draw of the model's counter hash.  tests/test_mplight_cpu.py compares it with the reference's fixtures.
+// epsilon-greedy draw of the model's counter hash.  tests/test_mplight_cpu.py compares it with the reference's fixtures,
+// tests/test_frap_ref_cpu.py with the float64 reference (tests/frap_ref.py) on synthetic phase-pair sets.
 #include <stdio.h>
 #include <math.h>
 #include <stdint.h>
