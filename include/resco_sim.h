@@ -427,6 +427,57 @@ int rs_ppo_fit(rs_ppo_handle p, const void *obs, const int32_t *act, const float
 int64_t rs_ppo_steps(rs_ppo_handle p);
 void rs_ppo_destroy(rs_ppo_handle p);
 
+/* ---- IDQN: the DQN update on the device (resco_amd/csrc/resco_dqn_train.h) -------------------------------------------
+ * What resco_amd/agents/idqn_learn.py does per update -- DeviceReplay.sample, BatchedDQNLearner.loss, its backward through the S
+ * stacked Q-networks, torch.optim.Adam -- as HIP kernels, all in fp32, every signal at its own lane and action count, the replay
+ * ring read in place.  rs_dqn_tensors: eight DEVICE pointers in BatchedIDQN's own layouts (fp32, contiguous); params, target,
+ * grads, m and v are the caller's and borrowed for the life of the handle: params, m and v are updated in place, grads is written,
+ * target is only read (copying params into it every target_update agent steps stays with the caller: a device-to-device copy).
+ * rs_dqn_ring: the DEVICE arrays of a DeviceReplay -- obs f16 [capacity][n_envs][S][lmax][5], act int16 and rew f32
+ * [capacity][n_envs][S], done one byte per slot -- and its position, by value: head = the next slot to write, count = slots written.
+ * rs_dqn_sample: for draw i < batch of signal s, k = hash(seed, update_key, s, i, 0) % (count - 1), e = hash(seed, update_key, s, i,
+ * 1) % n_envs, t = (head - count + k) mod capacity, idx_out[i][s] = (t, e) (device int32 [batch][S][2]); hash = the simulator's
+ * counter hash.  Slot head - 1 (no successor yet) and unwritten slots are never drawn.  (The modulo's bias, below 2^-32 n per value,
+ * is accepted.)
+ * rs_dqn_grad: the gradient of the minibatch idx (rows (t, e) per signal; the library holds them inside the ring) into grads:
+ * tgt = rew[t][e][s] + gamma max_{a < A_s} Q_target(obs[(t + 1) mod capacity][e][s])[a], or rew alone where done[t] (the successor
+ * is then not read); loss = mean over the batch of Huber(Q(obs[t][e][s])[act] - tgt, delta 1); loss_out: device float [S] or NULL.
+ * rs_dqn_step: Adam (no gradient clipping, as PFRL's DQN) on what grads holds; advances the step count.  rs_dqn_steps: that count.
+ * rs_dqn_update: for j < n_updates: rs_dqn_sample with update_key = the step count so far into the handle's own index array,
+ * rs_dqn_grad, rs_dqn_step -- the same launches, all enqueued by one call without host synchronisation or copies.
+ * All calls are asynchronous on `stream`; every sum has one fixed order (no float atomics): the same state gives the same bits.
+ * Workspace, allocated once by rs_dqn_create for max_batch rows and padded to lmax for every signal.
+ * Refusals (RS_EINVAL, text in rs_last_error(NULL), nothing launched): a NULL handle or pointer, batch outside 1 .. max_batch,
+ * count < 2, capacity < 2, n_envs < 1, head or count outside the ring, n_updates < 1, a ring array (obs, act, rew, done) or an index
+ * array that the runtime does not know as memory of the handle's device (asked once per set of ring pointers, every call for idx);
+ * rs_dqn_update stops enqueueing at the first launch that fails (RS_EHIP; rs_dqn_steps counts the steps that were launched);
+ * rs_dqn_create: a device that is not there, lmax outside 2 .. 17, amax outside 1 .. 8, lanes / actions outside theirs. */
+typedef struct rs_dqn *rs_dqn_handle;
+typedef struct rs_dqn_tensors {
+    float *conv_w, *conv_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b, *fc3_w, *fc3_b;
+} rs_dqn_tensors;
+typedef struct rs_dqn_config {   /* doubles, as rs_ppo_config's */
+    double lr, adam_eps, beta1, beta2, gamma;
+} rs_dqn_config;
+typedef struct rs_dqn_ring {
+    const void *obs;
+    const int16_t *act;
+    const float *rew;
+    const uint8_t *done;
+    int32_t capacity, n_envs, head, count;
+} rs_dqn_ring;
+int rs_dqn_create(int32_t device_id, int32_t n_signals, int32_t lmax, const int32_t *lanes, const int32_t *n_actions, int32_t amax,
+                  const rs_dqn_config *config, const rs_dqn_tensors *params, const rs_dqn_tensors *target, const rs_dqn_tensors *grads,
+                  const rs_dqn_tensors *m, const rs_dqn_tensors *v, int32_t max_batch, rs_dqn_handle *out);
+int rs_dqn_sample(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key, int32_t *idx_out,
+                  void *stream);
+int rs_dqn_grad(rs_dqn_handle p, const rs_dqn_ring *ring, const int32_t *idx, int32_t batch, float *loss_out, void *stream);
+int rs_dqn_step(rs_dqn_handle p, void *stream);
+int rs_dqn_update(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out,
+                  void *stream);
+int64_t rs_dqn_steps(rs_dqn_handle p);
+void rs_dqn_destroy(rs_dqn_handle p);
+
 /* static facts */
 int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal);
 

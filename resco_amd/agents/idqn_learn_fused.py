@@ -1,0 +1,144 @@
+"""The DQN update of a BatchedIDQN on the device (include/resco_sim.h: rs_dqn_create / rs_dqn_sample / rs_dqn_grad / rs_dqn_step /
+rs_dqn_update; resco_amd/csrc/resco_dqn_train.h).
+
+`FusedDQNLearner(net)` does what `BatchedDQNLearner` does per update -- DeviceReplay.sample, loss(), its backward through the S
+stacked Q-networks, torch.optim.Adam -- in HIP kernels, all in fp32, every signal at its own lane and action count, the replay ring
+read in place.  All updates of an agent step are ONE call through the ABI.  The network's own parameter storages are updated in
+place: `net` stays the source of truth, `FusedIDQN.refresh_on_device()` and `state_dict()` work unchanged.  Gradients, Adam moments
+and the target network are torch tensors this object owns (`.grads`, `.m`, `.v`: name -> tensor; `.target`: a BatchedIDQN); the
+library owns only its workspace and the step counter.  The minibatches come from the library's counter hash, not from a torch
+generator: the distribution is DeviceReplay.sample's, the draws are not.  There is no CPU fallback.
+"""
+import copy
+import ctypes as C
+
+import torch
+
+from ..sim import DQN_TENSORS, DQNConfig, DQNRing, DQNTensors, load_library, torch_stream
+from .idqn_rollout import BatchedIDQN
+
+
+class FusedDQNLearner:
+    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, seed=0):
+        assert isinstance(net, BatchedIDQN)
+        for k in DQN_TENSORS:
+            p = getattr(net, k)
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise RuntimeError('FusedDQNLearner needs contiguous float32 device parameters: the update is a HIP kernel (there is no CPU fallback)')
+        self.net = net
+        self.gamma, self.lr, self.adam_eps = float(gamma), float(lr), 1e-8
+        self.batch_size, self.target_update, self.seed = int(batch_size), int(target_update), int(seed) & 0xFFFFFFFF
+        self.t = 0              # agent steps seen (PFRL's self.t)
+        self._lib = load_library()
+        if not hasattr(self._lib, 'rs_dqn_create'):
+            raise RuntimeError('the loaded library has no rs_dqn_create: rebuild it (there is no CPU fallback)')
+        self.device = net.fc1_w.device
+        self.target = copy.deepcopy(net)
+        for p in self.target.parameters():
+            p.requires_grad_(False)
+        S = len(net.lanes)
+        zeros = lambda: {k: torch.zeros_like(getattr(net, k).detach()) for k in DQN_TENSORS}
+        self.grads, self.m, self.v = zeros(), zeros(), zeros()
+        self.loss_out = torch.zeros(S, dtype=torch.float32, device=self.device)
+        sets = [DQNTensors(*[getattr(n, k).data_ptr() for k in DQN_TENSORS]) for n in (net, self.target)]
+        sets += [DQNTensors(*[d[k].data_ptr() for k in DQN_TENSORS]) for d in (self.grads, self.m, self.v)]
+        cfg = DQNConfig(self.lr, self.adam_eps, 0.9, 0.999, self.gamma)
+        lanes, acts = (C.c_int32 * S)(*net.lanes), (C.c_int32 * S)(*net.actions)
+        h = C.c_void_p()
+        self._h, self._keep = None, None
+        torch.cuda.synchronize(self.device)
+        rc = self._lib.rs_dqn_create(self.device.index or 0, S, net.lmax, lanes, acts, net.amax, C.byref(cfg), *[C.byref(t) for t in sets],
+                                     self.batch_size, C.byref(h))
+        if rc != 0:
+            self._fail('rs_dqn_create', rc)
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            self._lib.rs_dqn_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def n_updates(self):
+        """Adam steps taken so far"""
+        return 0 if self._h is None else int(self._lib.rs_dqn_steps(self._h))
+
+    def _fail(self, name, rc):
+        raise RuntimeError('%s failed (%d): %s' % (name, rc, (self._lib.rs_last_error(None) or b'').decode()))
+
+    def _ring(self, replay):
+        """rs_dqn_ring over a DeviceReplay's own arrays (no copies) at its present position"""
+        S, lmax = len(self.net.lanes), self.net.lmax
+        for a in (replay.obs, replay.act, replay.rew, replay.done):
+            if not a.is_cuda:
+                raise RuntimeError('FusedDQNLearner needs the replay ring on the device: the update is a HIP kernel (there is no CPU fallback)')
+            assert a.is_contiguous()
+        assert replay.obs.dtype == torch.float16 and tuple(replay.obs.shape) == (replay.T, replay.N, S, lmax, 5), 'obs must be f16 [T, N, S, lmax, 5]'
+        assert replay.act.dtype == torch.int16 and replay.rew.dtype == torch.float32 and replay.done.dtype == torch.bool
+        ring = DQNRing(replay.obs.data_ptr(), replay.act.data_ptr(), replay.rew.data_ptr(), replay.done.data_ptr(), replay.T, replay.N,
+                       replay.head, replay.count)
+        self._keep = (replay, ring)
+        return ring
+
+    # ---- the pieces (what the tests compare one by one) and the update
+    def sample(self, replay, batch_size=None, update_key=None):
+        """The minibatch the next update would draw: int32 device tensor [B, S, 2] of (slot, environment) per signal.
+        update_key: the number of Adam steps taken so far unless given."""
+        B = self.batch_size if batch_size is None else int(batch_size)
+        idx = torch.empty(max(B, 0), len(self.net.lanes), 2, dtype=torch.int32, device=self.device)
+        key = self.n_updates if update_key is None else int(update_key)
+        rc = self._lib.rs_dqn_sample(self._h, C.byref(self._ring(replay)), B, self.seed, key & 0xFFFFFFFF, idx.data_ptr(), torch_stream(self.device.index))
+        if rc != 0:
+            self._fail('rs_dqn_sample', rc)
+        return idx
+
+    def grad(self, replay, idx):
+        """The gradient of the minibatch idx (integer device tensor [B, S, 2]: slot, environment) into .grads and the mean Huber loss
+        of every signal into .loss_out [S]."""
+        if not idx.is_cuda:
+            raise RuntimeError('FusedDQNLearner.grad needs a device index tensor (there is no CPU fallback)')
+        assert idx.dim() == 3 and idx.shape[1] == len(self.net.lanes) and idx.shape[2] == 2
+        idx32 = idx.to(torch.int32).contiguous()
+        ring = self._ring(replay)
+        self._keep += (idx32,)
+        rc = self._lib.rs_dqn_grad(self._h, C.byref(ring), idx32.data_ptr(), idx32.shape[0], self.loss_out.data_ptr(), torch_stream(self.device.index))
+        if rc != 0:
+            self._fail('rs_dqn_grad', rc)
+        return self.grads
+
+    def step(self):
+        """One Adam step on what .grads holds."""
+        rc = self._lib.rs_dqn_step(self._h, torch_stream(self.device.index))
+        if rc != 0:
+            self._fail('rs_dqn_step', rc)
+
+    def update(self, replay, updates=1):
+        """`updates` times [sample -> gradient -> Adam step], enqueued by one call.  Returns .loss_out (the last update's)."""
+        rc = self._lib.rs_dqn_update(self._h, C.byref(self._ring(replay)), self.batch_size, self.seed, int(updates), self.loss_out.data_ptr(),
+                                     torch_stream(self.device.index))
+        if rc != 0:
+            self._fail('rs_dqn_update', rc)
+        return self.loss_out
+
+    @torch.no_grad()
+    def sync_target(self):
+        """target <- parameters: device-to-device copies into the storages the library reads"""
+        for k in DQN_TENSORS:
+            getattr(self.target, k).copy_(getattr(self.net, k))
+
+    def observe_step(self, replay, generator=None, updates=1):
+        """One agent step of PFRL's DQN.observe(), in BatchedDQNLearner.observe_step's order: count it, copy the target network every
+        ``target_update`` steps, then update once the ring holds a minibatch.  `generator` is ignored: the minibatches are drawn by
+        the library's counter hash from (seed, Adam steps so far).  Returns .loss_out [S] after an update, else None."""
+        self.t += 1
+        if self.t % self.target_update == 0:
+            self.sync_target()
+        if len(replay) >= self.batch_size and updates >= 1:     # (no update asked for: nothing happens, as in BatchedDQNLearner's loop)
+            return self.update(replay, updates)
+        return None

@@ -174,6 +174,7 @@ struct PpoBatch {
     const float *logp, *adv, *ret;          // [n][S]
     const int32_t *idx;                     // [B]
     int32_t B;
+    __device__ const __half *row(int i, int s, int S, int ow) const { return obs + ((size_t)idx[i] * S + s) * ow; }
 };
 
 __device__ static inline ppt_f16 ppt_zero16() { ppt_f16 z; for (int i = 0; i < 16; ++i) z[i] = 0.0f; return z; }
@@ -350,7 +351,9 @@ __global__ void __launch_bounds__(PPT_T) ppo_fwd_bwd_kernel(PpoTrainTab T, PpoBa
 
 // ------------------------------------------------------------- 2. fc1 backward: dW1, dfeat and the conv gradients, per feature block
 // block (h, cb): conv row h, channels cb * 32 .. + 31 = 128 features m = (c - cb * 32) * 4 + w; wave wv owns features wv * 32 .. + 31
-__global__ void __launch_bounds__(PPT_T) ppo_fc1_bwd_kernel(PpoTrainTab T, PpoBatch D) {
+// The body is shared with the DQN update (resco_dqn_train.h): Tab = the table of either learner, Batch = its minibatch, which says
+// where row i of signal s has its observation (Batch::row) and how many rows there are (Batch::B).
+template <class Tab, class Batch> __device__ __forceinline__ void ppt_fc1_bwd_body(const Tab &T, const Batch &D) {
     constexpr int ZS = 65, OS = 11;
     __shared__ float dz_s[32 * ZS], ob_s[32 * OS];
     __shared__ float red_s[4 * 64 * 20];
@@ -392,7 +395,7 @@ __global__ void __launch_bounds__(PPT_T) ppo_fc1_bwd_kernel(PpoTrainTab T, PpoBa
         for (int e = tid; e < 32 * 10; e += PPT_T) {
             const int r = e / 10, q = e - r * 10;
             float x = 0.0f;
-            if (rb + r < D.B) x = __half2float(D.obs[((size_t)D.idx[rb + r] * S + s) * ow + h * 5 + q]);
+            if (rb + r < D.B) x = __half2float(D.row(rb + r, s, S, ow)[h * 5 + q]);
             ob_s[r * OS + q] = x;
         }
         __syncthreads();
@@ -447,6 +450,7 @@ __global__ void __launch_bounds__(PPT_T) ppo_fc1_bwd_kernel(PpoTrainTab T, PpoBa
         T.pconv[((((size_t)chunk * S + s) * T.H + h) * 64 + cC) * 5 + qe % 5] = acc;
     }
 }
+__global__ void __launch_bounds__(PPT_T) ppo_fc1_bwd_kernel(PpoTrainTab T, PpoBatch D) { ppt_fc1_bwd_body(T, D); }
 
 // --------------------------------------------------------------------------------------------- 3. partials -> gradients, fixed order
 // grid (S, H + ceil(PPT_N_SMALL / PPT_T)): part p < H = the fc1_w rows of conv row p, the others 256 small outputs each

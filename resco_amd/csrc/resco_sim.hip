@@ -111,6 +111,7 @@ __device__ unsigned long long *g_sec_prof;
 #include "resco_frap.h"
 #include "resco_ppo.h"
 #include "resco_ppo_train.h"
+#include "resco_dqn_train.h"
 
 // ------------------------------------------------------------------------------------------------ kernels
 // The tables / state / output descriptors live in ONE constant block in device memory (StepArgs): passed by value they
@@ -931,6 +932,173 @@ extern "C" int rs_ppo_fit(rs_ppo_handle p, const void *obs, const int32_t *act, 
 }
 
 extern "C" int64_t rs_ppo_steps(rs_ppo_handle p) { return p ? (int64_t)p->t : -1; }
+
+// ---- IDQN: the DQN update (resco_dqn_train.h).  The five tensor sets and the ring are the caller's; the library owns the workspace,
+// the index array of rs_dqn_update and t.
+struct rs_dqn {
+    int device = 0;
+    DqnTrainTab T{};
+    rs_dqn_config cfg{};
+    int max_batch = 0;
+    long long t = 0;            // Adam steps taken
+    int32_t *idx = nullptr;     // [max_batch][S][2]: the minibatch rs_dqn_update draws
+    const void *ring_ok[4] = {nullptr, nullptr, nullptr, nullptr};     // the ring arrays last found on this handle's device (dqn_check)
+    std::vector<void *> allocs;
+};
+
+extern "C" void rs_dqn_destroy(rs_dqn_handle p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    (void)hipDeviceSynchronize();
+    for (void *d : p->allocs) (void)hipFree(d);
+    delete p;
+}
+
+static bool dqn_tensors_complete(const rs_dqn_tensors *t) {
+    return t && t->conv_w && t->conv_b && t->fc1_w && t->fc1_b && t->fc2_w && t->fc2_b && t->fc3_w && t->fc3_b;
+}
+static DqnTensors dqn_tensors(const rs_dqn_tensors *t) {
+    return DqnTensors{{t->conv_w, t->conv_b, t->fc1_w, t->fc1_b, t->fc2_w, t->fc2_b, t->fc3_w, t->fc3_b}};
+}
+
+extern "C" int rs_dqn_create(int32_t device_id, int32_t n_signals, int32_t lmax, const int32_t *lanes, const int32_t *n_actions, int32_t amax,
+                             const rs_dqn_config *cfg, const rs_dqn_tensors *params, const rs_dqn_tensors *target, const rs_dqn_tensors *grads,
+                             const rs_dqn_tensors *m, const rs_dqn_tensors *v, int32_t max_batch, rs_dqn_handle *out) {
+    if (!out) return RS_EINVAL;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_err = "no HIP device visible (this library has no CPU fallback)"; return RS_EHIP; }
+    if (device_id < 0 || device_id >= ndev || n_signals <= 0 || lmax < 2 || lmax > 17 || amax < 1 || amax > PPT_AMAX || !lanes || !n_actions || !cfg ||
+        max_batch < 1) {
+        g_create_err = "rs_dqn_create: bad argument (a visible device, 1 <= signals, 2 <= lmax <= 17, 1 <= amax <= 8, 1 <= max_batch)"; return RS_EINVAL;
+    }
+    if (!dqn_tensors_complete(params) || !dqn_tensors_complete(target) || !dqn_tensors_complete(grads) || !dqn_tensors_complete(m) ||
+        !dqn_tensors_complete(v)) {
+        g_create_err = "rs_dqn_create: a tensor pointer is NULL"; return RS_EINVAL;
+    }
+    for (int s = 0; s < n_signals; ++s)
+        if (lanes[s] < 2 || lanes[s] > lmax || n_actions[s] < 1 || n_actions[s] > amax) {
+            g_create_err = "rs_dqn_create: 2 <= lanes[s] <= lmax and 1 <= n_actions[s] <= amax"; return RS_EINVAL;
+        }
+    if (hipSetDevice(device_id) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RS_EHIP; }
+    rs_dqn *p = new (std::nothrow) rs_dqn();
+    if (!p) return RS_ENOMEM;
+    p->device = device_id; p->max_batch = max_batch; p->cfg = *cfg;
+    DqnTrainTab &T = p->T;
+    T.S = n_signals; T.lmax = lmax; T.amax = amax; T.H = lmax - 1;
+    T.par = dqn_tensors(params); T.tgt = dqn_tensors(target); T.grad = dqn_tensors(grads); T.m = dqn_tensors(m); T.v = dqn_tensors(v);
+    T.gamma = (float)cfg->gamma;
+    T.tiles_max = (max_batch + PPT_TM - 1) / PPT_TM;
+    T.bpad_max = T.tiles_max * PPT_TM;
+    T.chunks_max = (T.bpad_max + PPT_CH - 1) / PPT_CH;
+    const size_t S = (size_t)n_signals, H = (size_t)T.H;
+    auto dev_alloc = [&](void **d, size_t bytes) {
+        if (hipMalloc(d, bytes) != hipSuccess) return false;
+        p->allocs.push_back(*d);
+        return true;
+    };
+    void *d_lanes = nullptr, *d_act = nullptr;
+    if (!dev_alloc(&d_lanes, S * 4) || !dev_alloc(&d_act, S * 4) || !dev_alloc((void **)&T.dz1, S * T.bpad_max * 64 * sizeof(float)) ||
+        !dev_alloc((void **)&T.y, S * T.bpad_max * sizeof(float)) || !dev_alloc((void **)&T.part, S * T.tiles_max * DQT_P_SIZE * sizeof(float)) ||
+        !dev_alloc((void **)&T.pw1, (size_t)T.chunks_max * S * H * 256 * 64 * sizeof(float)) ||
+        !dev_alloc((void **)&T.pconv, (size_t)T.chunks_max * S * H * 64 * 5 * sizeof(float)) ||
+        !dev_alloc((void **)&p->idx, (size_t)max_batch * S * 2 * sizeof(int32_t)) ||
+        hipMemcpy(d_lanes, lanes, S * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_act, n_actions, S * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        g_create_err = "rs_dqn_create: device allocation / upload failed";
+        (void)hipGetLastError();
+        rs_dqn_destroy(p);
+        return RS_ENOMEM;
+    }
+    T.lanes = (const int32_t *)d_lanes; T.n_actions = (const int32_t *)d_act;
+    *out = p;
+    return RS_OK;
+}
+
+// what every call that reads the ring checks before it launches anything; `name` goes into the message
+static bool dqn_on_device(const void *ptr, int device) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }     // (not memory the runtime knows)
+    return at.device == device;
+}
+static int dqn_check(rs_dqn *p, const rs_dqn_ring *r, int32_t batch, const char *name) {
+    auto refuse = [&](const char *why) { g_create_err = std::string(name) + ": " + why; return RS_EINVAL; };
+    if (!p) return refuse("NULL handle");
+    if (!r || !r->obs || !r->act || !r->rew || !r->done) return refuse("a ring pointer is NULL");
+    if (batch < 1 || batch > p->max_batch) return refuse("need 1 <= batch <= max_batch of rs_dqn_create");
+    if (r->capacity < 2 || r->n_envs < 1) return refuse("the ring needs capacity >= 2 and n_envs >= 1");
+    if (r->count < 2) return refuse("the ring needs count >= 2: a transition is a slot and its written successor");
+    if (r->count > r->capacity || r->head < 0 || r->head >= r->capacity) return refuse("head or count outside the ring");
+    // where the four arrays live is asked of the runtime once per ring, not once per step: a ring keeps its storages
+    const void *ring[4] = {r->obs, r->act, r->rew, r->done};
+    if (memcmp(ring, p->ring_ok, sizeof(ring)) != 0) {
+        for (const void *a : ring)
+            if (!dqn_on_device(a, p->device)) return refuse("a ring array is not device memory of this handle's device (another device, or host memory)");
+        memcpy(p->ring_ok, ring, sizeof(ring));
+    }
+    return RS_OK;
+}
+static DqnBatch dqn_batch(const rs_dqn_ring *r, const int32_t *idx, int32_t B) {
+    return DqnBatch{(const __half *)r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, idx, B};
+}
+
+// the launches; the arguments have been checked
+static void dqn_sample_launch(const rs_dqn *p, const rs_dqn_ring *r, int B, uint32_t seed, uint32_t key, int32_t *idx, hipStream_t st) {
+    hipLaunchKernelGGL(dqn_sample_kernel, dim3((B * p->T.S + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, seed, key, p->T.S, r->capacity, r->n_envs, r->head,
+                       r->count, B, idx);
+}
+static void dqn_grad_launch(const rs_dqn *p, const DqnBatch &D, float *loss_out, hipStream_t st) {
+    const DqnTrainTab &T = p->T;
+    const int tiles = (D.B + PPT_TM - 1) / PPT_TM, chunks = (tiles * PPT_TM + PPT_CH - 1) / PPT_CH;
+    hipLaunchKernelGGL(dqn_target_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
+    hipLaunchKernelGGL(dqn_fwd_bwd_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
+    hipLaunchKernelGGL(dqn_fc1_bwd_kernel, dim3(T.H * 2, chunks, T.S), dim3(PPT_T), 0, st, T, D);
+    hipLaunchKernelGGL(dqn_reduce_kernel, dim3(T.S, T.H + (DQT_N_SMALL + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, T, D.B, loss_out);
+}
+static void dqn_step_launch(rs_dqn *p, hipStream_t st) {
+    const PpoStepConsts K = ppo_step_consts(p->cfg.lr, p->cfg.adam_eps, p->cfg.beta1, p->cfg.beta2, 0.0, p->t + 1);
+    hipLaunchKernelGGL(dqn_adam_kernel, dim3(p->T.S, p->T.H + 1), dim3(PPT_T), 0, st, p->T, K);
+    if (hipPeekAtLastError() == hipSuccess) p->t += 1;      // a step that could not be launched is not counted
+}
+
+extern "C" int rs_dqn_sample(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key, int32_t *idx_out, void *stream) {
+    if (int rc = dqn_check(p, ring, batch, "rs_dqn_sample")) return rc;
+    if (!idx_out) { g_create_err = "rs_dqn_sample: idx_out is NULL"; return RS_EINVAL; }
+    if (!dqn_on_device(idx_out, p->device)) { g_create_err = "rs_dqn_sample: idx_out is not device memory of this handle's device"; return RS_EINVAL; }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    dqn_sample_launch(p, ring, batch, seed, update_key, idx_out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_dqn_grad(rs_dqn_handle p, const rs_dqn_ring *ring, const int32_t *idx, int32_t batch, float *loss_out, void *stream) {
+    if (int rc = dqn_check(p, ring, batch, "rs_dqn_grad")) return rc;
+    if (!idx) { g_create_err = "rs_dqn_grad: idx is NULL"; return RS_EINVAL; }
+    if (!dqn_on_device(idx, p->device)) { g_create_err = "rs_dqn_grad: idx is not device memory of this handle's device"; return RS_EINVAL; }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    dqn_grad_launch(p, dqn_batch(ring, idx, batch), loss_out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_dqn_step(rs_dqn_handle p, void *stream) {
+    if (!p) { g_create_err = "rs_dqn_step: NULL handle"; return RS_EINVAL; }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    dqn_step_launch(p, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_dqn_update(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out, void *stream) {
+    if (int rc = dqn_check(p, ring, batch, "rs_dqn_update")) return rc;
+    if (n_updates < 1) { g_create_err = "rs_dqn_update: need 1 <= n_updates"; return RS_EINVAL; }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    for (int j = 0; j < n_updates; ++j) {       // the launches of a stream run in order: update j + 1 may overwrite idx and the workspace
+        dqn_sample_launch(p, ring, batch, seed, (uint32_t)p->t, p->idx, (hipStream_t)stream);
+        dqn_grad_launch(p, dqn_batch(ring, p->idx, batch), loss_out, (hipStream_t)stream);
+        dqn_step_launch(p, (hipStream_t)stream);
+        if (hipPeekAtLastError() != hipSuccess) break;      // nothing more is enqueued behind a launch that failed
+    }
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int64_t rs_dqn_steps(rs_dqn_handle p) { return p ? (int64_t)p->t : -1; }
 
 // ------------------------------------------------------------------------------------------------ fused MPLight (FRAP) policy
 static void mplight_launch(const FrapTab &F, const void *obs, int n_envs, int env_base, float eps, uint32_t seed, uint32_t step_key,

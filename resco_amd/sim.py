@@ -34,7 +34,8 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_idqn_create', 'rs_idqn_act', 'rs_idqn_set_device_weights', 'rs_idqn_set_lanes', 'rs_idqn_destroy', 'rs_group_step',
                'rs_default_block', 'rs_mplight_create', 'rs_mplight_act', 'rs_mplight_set_device_weights', 'rs_mplight_destroy',
                'rs_ippo_act', 'rs_group_rollout', 'rs_ppo_gae',
-               'rs_ppo_create', 'rs_ppo_grad', 'rs_ppo_step', 'rs_ppo_fit', 'rs_ppo_steps', 'rs_ppo_destroy']
+               'rs_ppo_create', 'rs_ppo_grad', 'rs_ppo_step', 'rs_ppo_fit', 'rs_ppo_steps', 'rs_ppo_destroy',
+               'rs_dqn_create', 'rs_dqn_sample', 'rs_dqn_grad', 'rs_dqn_step', 'rs_dqn_update', 'rs_dqn_steps', 'rs_dqn_destroy']
 
 _lib = None
 
@@ -83,6 +84,17 @@ def bind(L):
         L.rs_ppo_steps.restype = C.c_int64
         L.rs_ppo_destroy.argtypes = [vp]
         L.rs_ppo_destroy.restype = None
+    if hasattr(L, 'rs_dqn_create'):
+        u32 = C.c_uint32
+        L.rs_dqn_create.argtypes = [i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)]
+        L.rs_dqn_sample.argtypes = [vp, vp, i32, u32, u32, vp, vp]
+        L.rs_dqn_grad.argtypes = [vp, vp, vp, i32, vp, vp]
+        L.rs_dqn_step.argtypes = [vp, vp]
+        L.rs_dqn_update.argtypes = [vp, vp, i32, u32, i32, vp, vp]
+        L.rs_dqn_steps.argtypes = [vp]
+        L.rs_dqn_steps.restype = C.c_int64
+        L.rs_dqn_destroy.argtypes = [vp]
+        L.rs_dqn_destroy.restype = None
     if hasattr(L, 'rs_default_block'):      # (the host emulation of the CPU tests exports only what it implements)
         L.rs_default_block.argtypes = [i32, i32, i32]
         L.rs_default_block.restype = i32
@@ -134,6 +146,24 @@ class PPOTensors(C.Structure):
 class PPOConfig(C.Structure):
     """ctypes mirror of rs_ppo_config (include/resco_sim.h)"""
     _fields_ = [(k, C.c_double) for k in ('lr', 'adam_eps', 'beta1', 'beta2', 'clip_eps', 'entropy_coef', 'value_coef', 'max_grad_norm')]
+
+
+DQN_TENSORS = PPO_TENSORS[:8]
+
+
+class DQNTensors(C.Structure):
+    """ctypes mirror of rs_dqn_tensors (include/resco_sim.h): eight device pointers in BatchedIDQN's layouts"""
+    _fields_ = [(k, C.c_void_p) for k in DQN_TENSORS]
+
+
+class DQNConfig(C.Structure):
+    """ctypes mirror of rs_dqn_config (include/resco_sim.h)"""
+    _fields_ = [(k, C.c_double) for k in ('lr', 'adam_eps', 'beta1', 'beta2', 'gamma')]
+
+
+class DQNRing(C.Structure):
+    """ctypes mirror of rs_dqn_ring (include/resco_sim.h): the device arrays of a DeviceReplay and its position"""
+    _fields_ = [(k, C.c_void_p) for k in ('obs', 'act', 'rew', 'done')] + [(k, C.c_int32) for k in ('capacity', 'n_envs', 'head', 'count')]
 
 
 class SimGroup:

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """IDQN training loop entirely on the GPU: HIP simulator -> fp16 observations -> fused HIP policy kernel
-(rs_idqn_act) -> device replay ring -> batched DQN update (PyTorch) -> weights re-packed on the device.  Nothing crosses PCIe per step except the launch calls.
+(rs_idqn_act) -> device replay ring -> batched DQN update (PyTorch, or HIP with --device-update) -> weights re-packed on the device.  Nothing crosses PCIe per step except the launch calls.
 
-    python tools/idqn_train.py [map] [n_envs] [episodes] [batch] [updates_per_step] [graph|nograph] [replay_steps] [eps_end] [seed]
+    python tools/idqn_train.py [--device-update] [map] [n_envs] [episodes] [batch] [updates_per_step] [graph|nograph] [replay_steps] [eps_end] [seed]
+
+--device-update: the update itself in HIP kernels as well (FusedDQNLearner, rs_dqn_update: sampling, target, backward and Adam of all
+updates of a step in one call; no HIP graph is captured).  Without it: the batched PyTorch learner, graph-captured unless `nograph`.
 
 Prints one JSON line per episode (mean episode return of rewards.wait_norm per signal, average trip delay as
 utils/readXML.py computes it, epsilon, env-steps/s including learning) and a final line comparing with the
@@ -17,6 +20,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from resco_amd.agents.idqn_learn import BatchedDQNLearner, DeviceReplay, linear_epsilon      # noqa: E402
+from resco_amd.agents.idqn_learn_fused import FusedDQNLearner                               # noqa: E402
 from resco_amd.agents.idqn_fused import FusedIDQN                                           # noqa: E402
 from resco_amd.agents.idqn_rollout import BatchedIDQN                                       # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                                           # noqa: E402
@@ -27,13 +31,18 @@ def delay(env):
     return float(env.sim.trip_delay().mean()), float(env.sim.stats()['arrived'].mean())
 
 
-def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_graph=True, replay_steps=0, eps_end=0.0, evaluate=True, quiet=False, seed=0, tls_expiry=True):
+def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_graph=True, replay_steps=0, eps_end=0.0, evaluate=True, quiet=False, seed=0, tls_expiry=True,
+         device_update=False):
     rows = []
     env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0, tls_expiry=tls_expiry)
     S, steps = env.n_signals, env.horizon_steps
     net = BatchedIDQN.from_scenario(env.scenario, dtype=torch.float32, device='cuda')
     net.init_like_reference(seed=seed)
-    learner = BatchedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch)
+    if device_update:
+        learner = FusedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed)
+        use_graph = False                               # one call enqueues the update's few launches: nothing to capture
+    else:
+        learner = BatchedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch)
     policy = FusedIDQN(net, seed=7 + seed)             # acting: one HIP kernel; weights re-packed on the device after each update
     actions = env.tensor('actions')
     # the reference keeps the last 10 000 transitions of its ONE environment = 27.8 episodes of history (pfrl_dqn.py:55); a ring of
@@ -96,12 +105,16 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
                  random_avg_delay_s=round(rnd_delay, 2))
     if not quiet:
         print(json.dumps(final))
+    if device_update:
+        learner.close()
     env.close()
     return rows, final
 
 
 if __name__ == '__main__':
     a = sys.argv[1:]
+    dev = a[:1] == ['--device-update']
+    a = a[1:] if dev else a
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 12,
          int(a[3]) if len(a) > 3 else 256, int(a[4]) if len(a) > 4 else 1, (a[5] != 'nograph') if len(a) > 5 else True,
-         int(a[6]) if len(a) > 6 else 0, float(a[7]) if len(a) > 7 else 0.0, seed=int(a[8]) if len(a) > 8 else 0)
+         int(a[6]) if len(a) > 6 else 0, float(a[7]) if len(a) > 7 else 0.0, seed=int(a[8]) if len(a) > 8 else 0, device_update=dev)
