@@ -7,7 +7,7 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, 'csrc', 'resco_sim.hip')
 LIB = os.path.join(HERE, 'csrc', 'libresco_sim.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-# -ffp-contract=off: fp32 results must equal the CPU oracle bit-for-bit (no FMA fusion).  The fp32-pair sums of resco_ppo_train.h
+# -ffp-contract=off: fp32 results must equal the CPU oracle bit-for-bit (no FMA fusion).  The fp32-pair sums of resco_train.h
 #   (ppo_pair_add and the helpers after it: two-sum, fmaf product errors) are exact only with it and without fast-math: a contracted
 #   or re-associated `(hi - (s - bb)) + (x - bb)` is zero.  Keep it (tests/test_ppo_train_cpu.py and test_gpu_ppo_train.py notice).
 # -disable-machine-licm: the step kernel's tick loop is long and register-starved (80 VGPRs for three workgroups per CU); with
@@ -17,7 +17,7 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 #   v_cndmask pairs (and the s_nop the pair needs on gfx950): +0.6-0.9 % (profiles/r06_ab_linkrec_nnan.txt); results bit-identical
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fno-honor-nans', '-mllvm', '-disable-machine-licm', '-fPIC', '-shared',
          '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(HERE, 'csrc')]
-_DEPS = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('resco_host.h', 'resco_step.h', 'resco_tables.h', 'resco_policy.h', 'resco_frap.h', 'resco_ppo.h', 'resco_ppo_train.h', 'resco_dqn_train.h')] + \
+_DEPS = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('resco_host.h', 'resco_step.h', 'resco_tables.h', 'resco_policy.h', 'resco_frap.h', 'resco_ppo.h', 'resco_train.h', 'resco_ppo_train.h', 'resco_dqn_train.h')] + \
         [os.path.join(ROOT, 'include', f) for f in ('resco_sim.h', 'resco_model.h')]
 
 

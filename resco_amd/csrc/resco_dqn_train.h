@@ -5,11 +5,11 @@
 // What it replaces (resco_amd/agents/idqn_learn.py: DeviceReplay.sample, BatchedDQNLearner.loss, its backward, torch.optim.Adam):
 // ~150 small launches per Adam step of the batched PyTorch learner, which pads every signal to lmax lanes and copies the sampled
 // observations twice.  Here the ring is read in place (obs f16 [T][N][S][lmax][5], act int16, rew f32 [T][N][S], done one byte per
-// slot), every signal runs at its own lane count L_s and action count A_s, and all arithmetic is fp32.
+// slot), every signal runs at its own lane count and action count, and all arithmetic is fp32.
 //
-// The network of one signal is the PPO trunk of resco_ppo_train.h without the value head (BatchedIDQN's layouts, the first eight
-// tensors of that file's order), so the tile, chunk and workgroup shapes, the fp32 pair sums and the Adam element update are that
-// file's, and the fc1 backward is its very body (ppt_fc1_bwd_body).
+// The network, its forward and backward, the reduction and the Adam body are resco_train.h's, with NH = 8 head columns (no value
+// head: the tensor sets leave PT_V_W and PT_V_B NULL) and NL = 1 loss term.  This file adds the draw (dqn_sample_index), the per-row
+// loss gradient (dqn_row_loss_grad; both built for the host as well by tests/dqn_train_host), the minibatch and the kernels.
 //
 // Launches of one minibatch gradient (rs_dqn_grad); row i of signal s is ring row idx[i][s] = (slot t, environment e):
 //   1. dqn_target_kernel, one workgroup per (64-row tile, signal): the TARGET network forward on the successor row ((t + 1) mod T, e)
@@ -17,27 +17,14 @@
 //      A launch of its own, not a first pass of the workgroup below: a workgroup is bound by the dependent MFMA chain of its fc1, and
 //      a minibatch of 256 rows x 21 signals is 84 workgroups on 256 CUs -- one workgroup running both forwards would take twice as
 //      long on the same 84 CUs, two launches cost one launch gap and 1 KB of targets per signal through memory (T.y).
-//   2. dqn_fwd_bwd_kernel, one workgroup per (tile, signal): forward as ppo_fwd_bwd_kernel, the per-row loss gradient
-//      (dqn_row_loss_grad), backward to dz1 and the tile's partial sums of the small layers' gradients.
-//   3. dqn_fc1_bwd_kernel = ppt_fc1_bwd_body on this minibatch;  4. dqn_reduce_kernel: partials -> gradients, ascending order.
-// and of one optimiser step (rs_dqn_step): dqn_adam_kernel (PFRL's DQN does not clip gradients: ppo_adam_element with scale {1, 0}).
-// rs_dqn_sample is dqn_sample_kernel.
-//
-// Every sum has ONE order fixed by the shapes alone and there are no floating-point atomics: two runs from the same state give the
-// same bits.  Padded fc1_w rows and fc3 columns are never read or written (a target network may hold anything there).
+//   2. dqn_fwd_bwd_kernel;  3. dqn_fc1_bwd_kernel;  4. dqn_reduce_kernel
+// and of one optimiser step (rs_dqn_step): dqn_adam_kernel (PFRL's DQN does not clip gradients: scale {1, 0}).
+// rs_dqn_sample is dqn_sample_kernel.  A target network may hold anything in its padded fc1_w rows and fc3 columns.
 #pragma once
-#include "resco_ppo_train.h"
+#include "resco_train.h"
 
-#define DQT_NT 8            // tensors of a BatchedIDQN, in rs_dqn_tensors order = PT_CONV_W .. PT_FC3_B
-// per-tile partial sums of the small layers, floats from the tile's base
-#define DQT_P_W2 0          // [64 k][64 j]
-#define DQT_P_B2 4096       // [64]
-#define DQT_P_W3 4160       // [64 k][8]
-#define DQT_P_B3 4672       // [8] (+ 8 unused)
-#define DQT_P_B1 4688       // [64]
-#define DQT_P_LOSS 4752     // the Huber terms' sum as a pair: hi, lo (+ 14 unused)
-#define DQT_P_SIZE 4768
-#define DQT_N_SMALL (DQT_P_SIZE + 320)      // outputs of the reduction beyond fc1_w: the tile partials, then conv [64 c][5]
+#define DQN_NH PPT_AMAX     // head columns of a tile: the Q values
+#define DQN_NL 1            // loss terms of a row: the Huber term
 
 #ifdef __HIPCC__
 #define RS_DQN_DEV __device__ static inline     // (d_hash of resco_step.h is a device function)
@@ -70,20 +57,10 @@ RS_DQN_DEV void dqn_sample_index(uint32_t seed, uint32_t u, uint32_t s, uint32_t
 }
 
 #ifdef __HIPCC__
-struct DqnTensors { float *p[DQT_NT]; };
-
-struct DqnTrainTab {
-    int32_t S, lmax, amax, H;               // H = lmax - 1
-    const int32_t *lanes, *n_actions;       // device [S]
-    DqnTensors par, tgt, grad, m, v;        // tgt: the target network (borrowed like the parameters, only read)
+struct DqnTrainTab : PptTab {
+    PptTensors tgt;                         // the target network (borrowed like the parameters, only read)
     float gamma;
-    int32_t bpad_max;                       // rows of the dz1 workspace per signal (max_batch rounded up to PPT_TM)
-    int32_t tiles_max, chunks_max;
-    float *dz1;                             // [S][bpad_max][64]
     float *y;                               // [S][bpad_max]: the rows' targets
-    float *part;                            // [S][tiles_max][DQT_P_SIZE]
-    float *pw1;                             // [chunks_max][S][H * 256][64]
-    float *pconv;                           // [chunks_max][S][H][64][5]
 };
 
 struct DqnBatch {
@@ -100,10 +77,10 @@ struct DqnBatch {
         *t = min(max(p[0], 0), T - 1);
         *e = min(max(p[1], 0), N - 1);
     }
-    __device__ const __half *row(int i, int s, int S, int ow) const {
+    __device__ long long src(int i, int s, int S) const {
         int t, e;
         at(i, s, S, &t, &e);
-        return obs + (((size_t)t * N + e) * S + s) * ow;
+        return (long long)t * N + e;
     }
 };
 
@@ -114,296 +91,68 @@ __global__ void __launch_bounds__(PPT_T) dqn_sample_kernel(uint32_t seed, uint32
     dqn_sample_index(seed, u, (uint32_t)s, (uint32_t)i, T, N, head, count, idx + (size_t)o * 2);
 }
 
-// ------------------------------------------------------------------------------------- the forward of a 64-row tile, shared by 1. and 2.
-// bufA: the tile's observations [row][OS] (zero for the rows a short tile pads), cw_s the conv weights [c][w00 w01 w10 w11 b . . .];
-// leaves relu(z1) in a1_s, relu(z2) in a2_s ([row][ZS]) and Q[a < A] in lg_s[row * 8 + a].  Ends with a barrier.
-constexpr int DQT_OS = 85, DQT_ZS = 65;
-__device__ __forceinline__ void dqn_tile_forward(const DqnTensors &par, int s, int hs, int A, int amax, int H4, const float *bufA, const float *cw_s,
-                                                 float *a1_s, float *a2_s, float *lg_s, int lane, int wv) {
-    constexpr int OS = DQT_OS, ZS = DQT_ZS;
-    // ---- fc1: wave wv owns rows (wv & 1) * 32 .. + 31 and outputs (wv >> 1) * 32 .. + 31; k order h, w, c; one accumulator per w
-    {
-        const int i = lane & 31, g = lane >> 5, mt = wv & 1, nt = wv >> 1, row = mt * 32 + i;
-        const float *w1 = par.p[PT_FC1_W] + (size_t)s * H4 * 64 * 64 + nt * 32 + i;
-        ppt_f16 acc[4];
-        for (int w = 0; w < 4; ++w) acc[w] = ppt_zero16();
-        for (int h = 0; h < hs; ++h) {
-            float o[2][5];
-            for (int q = 0; q < 5; ++q) { o[0][q] = bufA[row * OS + h * 5 + q]; o[1][q] = bufA[row * OS + h * 5 + 5 + q]; }
-#pragma unroll 4
-            for (int c = 0; c < 64; c += 2) {
-                const int cc = c + g;
-                const float4 cw = *(const float4 *)&cw_s[cc * 8];
-                const float cb = cw_s[cc * 8 + 4];
-                const float *wk = w1 + ((size_t)cc * H4 + h * 4) * 64;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const float f = fmaxf(ppt_conv(cb, cw.x, cw.y, cw.z, cw.w, o[0][w], o[0][w + 1], o[1][w], o[1][w + 1]), 0.0f);
-                    acc[w] = __builtin_amdgcn_mfma_f32_32x32x2f32(f, wk[w * 64], acc[w], 0, 0, 0);
-                }
-            }
-        }
-        const float b1 = par.p[PT_FC1_B][s * 64 + nt * 32 + i];
-        for (int r = 0; r < 16; ++r) {
-            const int rr = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-            const float z = ((acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r])) + b1;
-            a1_s[rr * ZS + nt * 32 + i] = fmaxf(z, 0.0f);
-        }
-    }
-    __syncthreads();
-    const int row = lane, kg = wv * 16;             // the small layers: a thread owns one row and 16 wave-uniform columns
-    {
-        const float *w2 = par.p[PT_FC2_W] + (size_t)s * 4096 + kg;
-        float z[16];
-        for (int j = 0; j < 16; ++j) z[j] = par.p[PT_FC2_B][s * 64 + kg + j];
-        for (int k = 0; k < 64; ++k) {
-            const float a = a1_s[row * ZS + k];
-            for (int j = 0; j < 16; ++j) z[j] = fmaf(a, w2[k * 64 + j], z[j]);
-        }
-        for (int j = 0; j < 16; ++j) a2_s[row * ZS + kg + j] = fmaxf(z[j], 0.0f);
-    }
-    __syncthreads();
-    for (int a = wv; a < A; a += 4) {               // the head: wave wv computes columns wv, wv + 4 of the signal's own A
-        const float *wc = par.p[PT_FC3_W] + (size_t)s * 64 * amax + a;
-        float z = par.p[PT_FC3_B][s * amax + a];
-        for (int k = 0; k < 64; ++k) z = fmaf(a2_s[row * ZS + k], wc[k * amax], z);
-        lg_s[row * 8 + a] = z;
-    }
-    __syncthreads();
-}
-
-// the tile's observations and conv weights into LDS; src_s[r]: the ring row (t * N + e) of tile row r, < 0 = none (zeros)
-__device__ __forceinline__ void dqn_tile_load(const DqnTensors &par, const DqnBatch &D, int s, int S, int ow, const long long *src_s, float *bufA,
-                                              float *cw_s, int tid) {
-    for (int e = tid; e < PPT_TM * ow; e += PPT_T) {
-        const int r = e / ow, q = e - r * ow;
-        const long long src = src_s[r];
-        bufA[r * DQT_OS + q] = src < 0 ? 0.0f : __half2float(D.obs[((size_t)src * S + s) * ow + q]);
-    }
-    for (int e = tid; e < 64 * 8; e += PPT_T) {
-        const int c = e >> 3, q = e & 7;
-        cw_s[e] = q < 4 ? par.p[PT_CONV_W][((size_t)s * 64 + c) * 4 + q] : (q == 4 ? par.p[PT_CONV_B][s * 64 + c] : 0.0f);
-    }
-}
-
 // ------------------------------------------------------------------------------------------- 1. the rows' targets, per tile
 __global__ void __launch_bounds__(PPT_T, 2) dqn_target_kernel(DqnTrainTab T, DqnBatch D) {
-    __shared__ float bufA[PPT_TM * DQT_OS], a1_s[PPT_TM * DQT_ZS], a2_s[PPT_TM * DQT_ZS], cw_s[64 * 8], lg_s[PPT_TM * 8];
-    __shared__ long long src_s[PPT_TM], cur_s[PPT_TM];
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = blockIdx.x, s = blockIdx.y, S = T.S;
-    const int hs = T.lanes[s] - 1, A = T.n_actions[s];
-    const int r0 = tile * PPT_TM, nrows = min(PPT_TM, D.B - r0);
+    __shared__ PptTileLds<DQN_NH> L;
+    __shared__ long long cur_s[PPT_TM];
+    const PptTile X = ppt_tile(T, D.B);
+    const int tid = X.tid, S = T.S, s = X.s;
     if (tid < PPT_TM) {
         long long cur = -1, nxt = -1;
-        if (tid < nrows) {
+        if (tid < X.nrows) {
             int t, e;
-            D.at(r0 + tid, s, S, &t, &e);
+            D.at(X.r0 + tid, s, S, &t, &e);
             cur = (long long)t * D.N + e;
             if (!D.done[t]) nxt = (long long)(t + 1 == D.T ? 0 : t + 1) * D.N + e;      // an episode end cuts the bootstrap: nothing is read
         }
-        cur_s[tid] = cur; src_s[tid] = nxt;
+        cur_s[tid] = cur; L.src[tid] = nxt;
     }
     __syncthreads();
-    dqn_tile_load(T.tgt, D, s, S, T.lmax * 5, src_s, bufA, cw_s, tid);
+    ppt_tile_load(T.tgt, T, X, D.obs, L);
     __syncthreads();
-    dqn_tile_forward(T.tgt, s, hs, A, T.amax, T.H * 4, bufA, cw_s, a1_s, a2_s, lg_s, lane, wv);
+    ppt_tile_forward(T.tgt, T, X, L);
     if (tid < PPT_TM) {
         float y = 0.0f;
-        if (tid < nrows) {
+        if (tid < X.nrows) {
             y = D.rew[(size_t)cur_s[tid] * S + s];
-            if (src_s[tid] >= 0) {
-                float mx = lg_s[tid * 8];
-                for (int a = 1; a < A; ++a) mx = lg_s[tid * 8 + a] > mx ? lg_s[tid * 8 + a] : mx;
+            if (L.src[tid] >= 0) {
+                float mx = L.lg[tid * DQN_NH];
+                for (int a = 1; a < X.A; ++a) mx = L.lg[tid * DQN_NH + a] > mx ? L.lg[tid * DQN_NH + a] : mx;
                 y = y + T.gamma * mx;
             }
         }
-        T.y[(size_t)s * T.bpad_max + r0 + tid] = y;
+        T.y[(size_t)s * T.bpad_max + X.r0 + tid] = y;
     }
 }
 
 // ------------------------------------------------------------------------------------- 2. forward, loss, backward to dz1, per tile
 __global__ void __launch_bounds__(PPT_T, 2) dqn_fwd_bwd_kernel(DqnTrainTab T, DqnBatch D) {
-    constexpr int ZS = DQT_ZS;
-    __shared__ float bufA[PPT_TM * DQT_OS];         // observations, later dz2, later dz1 (both with stride ZS)
-    __shared__ float a1_s[PPT_TM * ZS], a2_s[PPT_TM * ZS], cw_s[64 * 8];
-    __shared__ float lg_s[PPT_TM * 8], dl_s[PPT_TM * 8], lt_s[PPT_TM];
-    __shared__ long long src_s[PPT_TM];
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = blockIdx.x, s = blockIdx.y, S = T.S;
-    const int hs = T.lanes[s] - 1, A = T.n_actions[s], amax = T.amax;
-    const int r0 = tile * PPT_TM, nrows = min(PPT_TM, D.B - r0);
-    if (tid < PPT_TM) {
-        long long cur = -1;
-        if (tid < nrows) {
-            int t, e;
-            D.at(r0 + tid, s, S, &t, &e);
-            cur = (long long)t * D.N + e;
-        }
-        src_s[tid] = cur;
-    }
+    __shared__ PptTileLds<DQN_NH> L;
+    __shared__ float dl_s[PPT_TM * DQN_NH], lt_s[PPT_TM * DQN_NL];
+    const PptTile X = ppt_tile(T, D.B);
+    const int tid = X.tid, S = T.S, s = X.s, A = X.A;
+    if (tid < PPT_TM) L.src[tid] = tid < X.nrows ? D.src(X.r0 + tid, s, S) : -1;
     __syncthreads();
-    dqn_tile_load(T.par, D, s, S, T.lmax * 5, src_s, bufA, cw_s, tid);
+    ppt_tile_load(T.par, T, X, D.obs, L);
     __syncthreads();
-    dqn_tile_forward(T.par, s, hs, A, amax, T.H * 4, bufA, cw_s, a1_s, a2_s, lg_s, lane, wv);
-    const int row = lane, kg = wv * 16;
+    ppt_tile_forward(T.par, T, X, L);
     // ---- the loss gradient of every row; rows past the minibatch contribute nothing
     if (tid < PPT_TM) {
         float dl[PPT_AMAX], tm = 0.0f;
         for (int a = 0; a < PPT_AMAX; ++a) dl[a] = 0.0f;
-        if (tid < nrows) {
+        if (tid < X.nrows) {
             float q[PPT_AMAX];
-            for (int a = 0; a < PPT_AMAX; ++a) q[a] = a < A ? lg_s[tid * 8 + a] : 0.0f;
-            dqn_row_loss_grad(q, A, (int)D.act[(size_t)src_s[tid] * S + s], T.y[(size_t)s * T.bpad_max + r0 + tid], (float)D.B, dl, &tm);
+            for (int a = 0; a < PPT_AMAX; ++a) q[a] = a < A ? L.lg[tid * DQN_NH + a] : 0.0f;
+            dqn_row_loss_grad(q, A, (int)D.act[(size_t)L.src[tid] * S + s], T.y[(size_t)s * T.bpad_max + X.r0 + tid], (float)D.B, dl, &tm);
         }
-        for (int a = 0; a < PPT_AMAX; ++a) dl_s[tid * 8 + a] = a < A ? dl[a] : 0.0f;
+        for (int a = 0; a < PPT_AMAX; ++a) dl_s[tid * DQN_NH + a] = a < A ? dl[a] : 0.0f;
         lt_s[tid] = tm;
     }
     __syncthreads();
-    // ---- dz2 = (z2 > 0) dQ W3^T -> bufA (the observations are no longer needed)
-    {
-        float d[16];
-        for (int j = 0; j < 16; ++j) d[j] = 0.0f;
-        const float *w3 = T.par.p[PT_FC3_W] + ((size_t)s * 64 + kg) * amax;
-        for (int a = 0; a < A; ++a) {
-            const float x = dl_s[row * 8 + a];
-            for (int j = 0; j < 16; ++j) d[j] = fmaf(x, w3[j * amax + a], d[j]);
-        }
-        for (int j = 0; j < 16; ++j) bufA[row * ZS + kg + j] = a2_s[row * ZS + kg + j] > 0.0f ? d[j] : 0.0f;
-    }
-    __syncthreads();
-    float *P = T.part + ((size_t)s * T.tiles_max + tile) * DQT_P_SIZE;
-    // ---- partial sums over the tile's rows that need dz2: dW2 = a1^T dz2, db2, dW3 = a2^T dQ, db3, the loss
-    {
-        float g2[16];
-        for (int j = 0; j < 16; ++j) g2[j] = 0.0f;
-        for (int r = 0; r < PPT_TM; ++r) {
-            const float dz = bufA[r * ZS + lane];
-            for (int j = 0; j < 16; ++j) g2[j] = fmaf(a1_s[r * ZS + kg + j], dz, g2[j]);
-        }
-        for (int j = 0; j < 16; ++j) P[DQT_P_W2 + (kg + j) * 64 + lane] = g2[j];
-        for (int o = tid; o < 64 * 8; o += PPT_T) {
-            const int k = o >> 3, a = o & 7;
-            float acc = 0.0f;
-            for (int r = 0; r < PPT_TM; ++r) acc = fmaf(a2_s[r * ZS + k], dl_s[r * 8 + a], acc);
-            P[DQT_P_W3 + o] = acc;
-        }
-        if (tid < 64) {
-            float acc = 0.0f;
-            for (int r = 0; r < PPT_TM; ++r) acc += bufA[r * ZS + tid];
-            P[DQT_P_B2 + tid] = acc;
-        } else if (tid < 64 + 8) {
-            float acc = 0.0f;
-            for (int r = 0; r < PPT_TM; ++r) acc += dl_s[r * 8 + (tid - 64)];
-            P[DQT_P_B3 + tid - 64] = acc;
-        } else if (tid == 128) {
-            float hi = 0.0f, lo = 0.0f;
-            for (int r = 0; r < PPT_TM; ++r) ppo_pair_add(&hi, &lo, lt_s[r], 0.0f);
-            P[DQT_P_LOSS] = hi;
-            P[DQT_P_LOSS + 1] = lo;
-        }
-    }
-    // ---- dz1 = (z1 > 0) dz2 W2^T: into registers, then (every wave has read its rows' dz2) over dz2 in bufA
-    float d1[16];
-    {
-        const float *w2 = T.par.p[PT_FC2_W] + (size_t)s * 4096 + (size_t)kg * 64;
-        for (int j = 0; j < 16; ++j) d1[j] = 0.0f;
-        for (int q = 0; q < 64; ++q) {
-            const float dz = bufA[row * ZS + q];
-            for (int j = 0; j < 16; ++j) d1[j] = fmaf(dz, w2[j * 64 + q], d1[j]);
-        }
-        for (int j = 0; j < 16; ++j) d1[j] = a1_s[row * ZS + kg + j] > 0.0f ? d1[j] : 0.0f;
-    }
-    __syncthreads();
-    for (int j = 0; j < 16; ++j) bufA[row * ZS + kg + j] = d1[j];
-    __syncthreads();
-    {
-        float *dz = T.dz1 + ((size_t)s * T.bpad_max + r0) * 64;
-        for (int e = tid; e < PPT_TM * 64; e += PPT_T) dz[e] = bufA[(e >> 6) * ZS + (e & 63)];
-        if (tid < 64) {
-            float acc = 0.0f;
-            for (int r = 0; r < PPT_TM; ++r) acc += bufA[r * ZS + tid];
-            P[DQT_P_B1 + tid] = acc;
-        }
-    }
+    ppt_tile_backward<DQN_NH, DQN_NL>(T, X, L, dl_s, lt_s);
 }
 
-// ------------------------------------------------------------- 3. fc1 backward: the PPO update's body on this minibatch
 __global__ void __launch_bounds__(PPT_T) dqn_fc1_bwd_kernel(DqnTrainTab T, DqnBatch D) { ppt_fc1_bwd_body(T, D); }
-
-// --------------------------------------------------------------------------------------------- 4. partials -> gradients, fixed order
-// grid (S, H + ceil(DQT_N_SMALL / PPT_T)): part p < H = the fc1_w rows of conv row p, the others 256 small outputs each
-__global__ void __launch_bounds__(PPT_T) dqn_reduce_kernel(DqnTrainTab T, int B, float *loss_out) {
-    const int s = blockIdx.x, p = blockIdx.y, tid = threadIdx.x;
-    const int hs = T.lanes[s] - 1, A = T.n_actions[s], amax = T.amax, H4 = T.H * 4, S = T.S;
-    const int tiles = (B + PPT_TM - 1) / PPT_TM, chunks = (tiles * PPT_TM + PPT_CH - 1) / PPT_CH;
-    if (p < T.H) {
-        if (p >= hs) return;
-        const size_t per = (size_t)H4 * 64 * 64;
-        for (int e = tid; e < 64 * 4 * 64; e += PPT_T) {
-            const int j = e & 63, w = (e >> 6) & 3, c = e >> 8;
-            const size_t o = (size_t)s * per + ((size_t)c * H4 + p * 4 + w) * 64 + j;
-            float acc = 0.0f;
-            for (int ch = 0; ch < chunks; ++ch) acc += T.pw1[(size_t)ch * S * per + o];
-            T.grad.p[PT_FC1_W][o] = acc;
-        }
-        return;
-    }
-    const int o = (p - T.H) * PPT_T + tid;
-    if (o >= DQT_N_SMALL) return;
-    if (o < DQT_P_SIZE) {
-        float *dst = nullptr;
-        if (o < DQT_P_B2) dst = T.grad.p[PT_FC2_W] + (size_t)s * 4096 + o;
-        else if (o < DQT_P_W3) dst = T.grad.p[PT_FC2_B] + s * 64 + (o - DQT_P_B2);
-        else if (o < DQT_P_B3) {
-            const int k = (o - DQT_P_W3) >> 3, a = (o - DQT_P_W3) & 7;
-            if (a < A) dst = T.grad.p[PT_FC3_W] + ((size_t)s * 64 + k) * amax + a;
-        } else if (o < DQT_P_B1) {
-            const int a = o - DQT_P_B3;
-            if (a < A) dst = T.grad.p[PT_FC3_B] + s * amax + a;
-        } else if (o < DQT_P_LOSS) dst = T.grad.p[PT_FC1_B] + s * 64 + (o - DQT_P_B1);
-        else if (o == DQT_P_LOSS && loss_out) dst = loss_out + s;
-        if (!dst) return;
-        const float *src = T.part + (size_t)s * T.tiles_max * DQT_P_SIZE + o;
-        if (o == DQT_P_LOSS) {
-            float hi = 0.0f, lo = 0.0f;
-            for (int t = 0; t < tiles; ++t) ppo_pair_add(&hi, &lo, src[(size_t)t * DQT_P_SIZE], src[(size_t)t * DQT_P_SIZE + 1]);
-            *dst = (hi + lo) / (float)B;
-            return;
-        }
-        float acc = 0.0f;
-        for (int t = 0; t < tiles; ++t) acc += src[(size_t)t * DQT_P_SIZE];
-        *dst = acc;
-        return;
-    }
-    const int e = o - DQT_P_SIZE, c = e / 5, q = e - c * 5;
-    float acc = 0.0f;
-    for (int ch = 0; ch < chunks; ++ch)
-        for (int h = 0; h < hs; ++h) acc += T.pconv[((((size_t)ch * S + s) * T.H + h) * 64 + c) * 5 + q];
-    if (q < 4) T.grad.p[PT_CONV_W][((size_t)s * 64 + c) * 4 + q] = acc;
-    else T.grad.p[PT_CONV_B][s * 64 + c] = acc;
-}
-
-// ----------------------------------------------------------------------------------------------------------------------- 5. Adam
-// grid (S, H + 1): part p < H the fc1_w rows of conv row p (none when p >= hs), p == H every other tensor; padded fc1 rows and fc3
-// columns are never visited
-__global__ void __launch_bounds__(PPT_T) dqn_adam_kernel(DqnTrainTab T, PpoStepConsts K) {
-    const int s = blockIdx.x, p = blockIdx.y, tid = threadIdx.x;
-    const int hs = T.lanes[s] - 1, A = T.n_actions[s], amax = T.amax, H4 = T.H * 4;
-    const PpoPair one{1.0f, 0.0f};
-    auto f = [&](int t, size_t o) { ppo_adam_element(&T.par.p[t][o], &T.m.p[t][o], &T.v.p[t][o], T.grad.p[t][o], one, K); };
-    if (p < T.H) {
-        if (p >= hs) return;
-        for (int e = tid; e < 64 * 4 * 64; e += PPT_T)
-            f(PT_FC1_W, (size_t)s * H4 * 4096 + ((size_t)(e >> 8) * H4 + p * 4 + ((e >> 6) & 3)) * 64 + (e & 63));
-        return;
-    }
-    for (int e = tid; e < 256; e += PPT_T) f(PT_CONV_W, (size_t)s * 256 + e);
-    for (int e = tid; e < 64; e += PPT_T) f(PT_CONV_B, (size_t)s * 64 + e);
-    for (int e = tid; e < 64; e += PPT_T) f(PT_FC1_B, (size_t)s * 64 + e);
-    for (int e = tid; e < 4096; e += PPT_T) f(PT_FC2_W, (size_t)s * 4096 + e);
-    for (int e = tid; e < 64; e += PPT_T) f(PT_FC2_B, (size_t)s * 64 + e);
-    for (int e = tid; e < 64 * A; e += PPT_T) f(PT_FC3_W, ((size_t)s * 64 + e / A) * amax + e % A);
-    for (int e = tid; e < A; e += PPT_T) f(PT_FC3_B, (size_t)s * amax + e);
-}
+__global__ void __launch_bounds__(PPT_T) dqn_reduce_kernel(DqnTrainTab T, int B, float *loss_out) { ppt_reduce_body<DQN_NH, DQN_NL>(T, B, loss_out); }
+__global__ void __launch_bounds__(PPT_T) dqn_adam_kernel(DqnTrainTab T, PpoStepConsts K) { ppt_adam_body<DQN_NH>(T, K, PpoPair{1.0f, 0.0f}); }
 #endif

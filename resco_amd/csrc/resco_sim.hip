@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
@@ -804,17 +805,20 @@ extern "C" int rs_ppo_gae(const float *rew, const float *value, const float *las
     return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
 }
 
-// ---- PPO: the update itself (resco_ppo_train.h).  The four tensor sets are the caller's; the library owns the workspace and t.
-struct rs_ppo {
+// ---- The learner updates (resco_train.h).  What the handles of rs_ppo_create and rs_dqn_create share: the tensor sets are the
+// caller's; the library owns the workspace and t.
+struct TrainHandle {
     int device = 0;
-    PpoTrainTab T{};
-    rs_ppo_config cfg{};
-    int max_minibatch = 0;
+    int max_batch = 0;          // the largest minibatch the workspace holds
     long long t = 0;            // Adam steps taken
     std::vector<void *> allocs;
+    bool alloc(void **d, size_t bytes) {
+        if (hipMalloc(d, bytes) != hipSuccess) return false;
+        allocs.push_back(*d);
+        return true;
+    }
 };
-
-extern "C" void rs_ppo_destroy(rs_ppo_handle p) {
+template <class Handle> static void train_destroy(Handle *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
     (void)hipDeviceSynchronize();
@@ -822,62 +826,88 @@ extern "C" void rs_ppo_destroy(rs_ppo_handle p) {
     delete p;
 }
 
-static bool ppo_tensors_complete(const rs_ppo_tensors *t) {
-    return t && t->conv_w && t->conv_b && t->fc1_w && t->fc1_b && t->fc2_w && t->fc2_b && t->fc3_w && t->fc3_b && t->v_w && t->v_b;
+// rs_ppo_tensors / rs_dqn_tensors are the first nt pointers of the PT_* order
+static_assert(sizeof(rs_ppo_tensors) == PPT_NT * sizeof(float *) && sizeof(rs_dqn_tensors) == (PT_FC3_B + 1) * sizeof(float *), "tensor sets");
+static bool train_tensors_complete(const void *set, int nt) {
+    for (int i = 0; set && i < nt; ++i)
+        if (!((float *const *)set)[i]) return false;
+    return set != nullptr;
 }
-static PpoTensors ppo_tensors(const rs_ppo_tensors *t) {
-    return PpoTensors{{t->conv_w, t->conv_b, t->fc1_w, t->fc1_b, t->fc2_w, t->fc2_b, t->fc3_w, t->fc3_b, t->v_w, t->v_b}};
+static PptTensors train_tensors(const void *set, int nt) {
+    PptTensors t{};
+    for (int i = 0; i < nt; ++i) t.p[i] = ((float *const *)set)[i];
+    return t;
 }
 
-extern "C" int rs_ppo_create(int32_t device_id, int32_t n_signals, int32_t lmax, const int32_t *lanes, const int32_t *n_actions, int32_t amax,
-                             const rs_ppo_config *cfg, const rs_ppo_tensors *params, const rs_ppo_tensors *grads, const rs_ppo_tensors *m,
-                             const rs_ppo_tensors *v, int32_t max_minibatch, rs_ppo_handle *out) {
+// What rs_ppo_create and rs_dqn_create share: the argument checks (`name` and the caller's wording of its limits go into the text),
+// the handle, the common fields of its table and the common workspace; part_size = ppt_p_size(NH).  sets: the caller's tensor sets of
+// nt pointers each, params first; the table's par is set, the caller sets the others.  own(p): the caller's own allocations.
+template <class Handle, class Own>
+static int train_create(const char *name, const char *limits, int32_t device_id, int32_t n_signals, int32_t lmax, const int32_t *lanes,
+                        const int32_t *n_actions, int32_t amax, const void *cfg, std::initializer_list<const void *> sets, int nt, int32_t max_batch,
+                        int part_size, Handle **out, Own own) {
     if (!out) return RS_EINVAL;
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_err = "no HIP device visible (this library has no CPU fallback)"; return RS_EHIP; }
     if (device_id < 0 || device_id >= ndev || n_signals <= 0 || lmax < 2 || lmax > 17 || amax < 1 || amax > PPT_AMAX || !lanes || !n_actions || !cfg ||
-        max_minibatch < 1) {
-        g_create_err = "rs_ppo_create: bad argument (1 <= signals, 2 <= lmax <= 17, 1 <= amax <= 8, 1 <= max_minibatch)"; return RS_EINVAL;
+        max_batch < 1) {
+        g_create_err = std::string(name) + ": bad argument (" + limits + ")"; return RS_EINVAL;
     }
-    if (!ppo_tensors_complete(params) || !ppo_tensors_complete(grads) || !ppo_tensors_complete(m) || !ppo_tensors_complete(v)) {
-        g_create_err = "rs_ppo_create: a tensor pointer is NULL"; return RS_EINVAL;
-    }
+    for (const void *set : sets)
+        if (!train_tensors_complete(set, nt)) { g_create_err = std::string(name) + ": a tensor pointer is NULL"; return RS_EINVAL; }
     for (int s = 0; s < n_signals; ++s)
         if (lanes[s] < 2 || lanes[s] > lmax || n_actions[s] < 1 || n_actions[s] > amax) {
-            g_create_err = "rs_ppo_create: 2 <= lanes[s] <= lmax and 1 <= n_actions[s] <= amax"; return RS_EINVAL;
+            g_create_err = std::string(name) + ": 2 <= lanes[s] <= lmax and 1 <= n_actions[s] <= amax"; return RS_EINVAL;
         }
     if (hipSetDevice(device_id) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RS_EHIP; }
-    rs_ppo *p = new (std::nothrow) rs_ppo();
+    Handle *p = new (std::nothrow) Handle();
     if (!p) return RS_ENOMEM;
-    p->device = device_id; p->max_minibatch = max_minibatch;
-    PpoTrainTab &T = p->T;
+    p->device = device_id; p->max_batch = max_batch;
+    PptTab &T = p->T;
     T.S = n_signals; T.lmax = lmax; T.amax = amax; T.H = lmax - 1;
-    T.par = ppo_tensors(params); T.grad = ppo_tensors(grads); T.m = ppo_tensors(m); T.v = ppo_tensors(v);
-    p->cfg = *cfg;
-    T.hp = PpoHyper{(float)cfg->clip_eps, (float)cfg->entropy_coef, (float)cfg->value_coef};
-    T.tiles_max = (max_minibatch + PPT_TM - 1) / PPT_TM;
+    T.par = train_tensors(*sets.begin(), nt);
+    T.tiles_max = (max_batch + PPT_TM - 1) / PPT_TM;
     T.bpad_max = T.tiles_max * PPT_TM;
     T.chunks_max = (T.bpad_max + PPT_CH - 1) / PPT_CH;
     const size_t S = (size_t)n_signals, H = (size_t)T.H;
-    auto dev_alloc = [&](void **d, size_t bytes) {
-        if (hipMalloc(d, bytes) != hipSuccess) return false;
-        p->allocs.push_back(*d);
-        return true;
-    };
     void *d_lanes = nullptr, *d_act = nullptr;
-    if (!dev_alloc(&d_lanes, S * 4) || !dev_alloc(&d_act, S * 4) || !dev_alloc((void **)&T.dz1, S * T.bpad_max * 64 * sizeof(float)) ||
-        !dev_alloc((void **)&T.part, S * T.tiles_max * PPT_P_SIZE * sizeof(float)) ||
-        !dev_alloc((void **)&T.pw1, (size_t)T.chunks_max * S * H * 256 * 64 * sizeof(float)) ||
-        !dev_alloc((void **)&T.pconv, (size_t)T.chunks_max * S * H * 64 * 5 * sizeof(float)) || !dev_alloc((void **)&T.sqpart, S * (H + 1) * 2 * sizeof(float)) ||
+    if (!p->alloc(&d_lanes, S * 4) || !p->alloc(&d_act, S * 4) || !p->alloc((void **)&T.dz1, S * T.bpad_max * 64 * sizeof(float)) ||
+        !p->alloc((void **)&T.part, S * T.tiles_max * part_size * sizeof(float)) ||
+        !p->alloc((void **)&T.pw1, (size_t)T.chunks_max * S * H * 256 * 64 * sizeof(float)) ||
+        !p->alloc((void **)&T.pconv, (size_t)T.chunks_max * S * H * 64 * 5 * sizeof(float)) || !own(p) ||
         hipMemcpy(d_lanes, lanes, S * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_act, n_actions, S * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        g_create_err = "rs_ppo_create: device allocation / upload failed";
+        g_create_err = std::string(name) + ": device allocation / upload failed";
         (void)hipGetLastError();
-        rs_ppo_destroy(p);
+        train_destroy(p);
         return RS_ENOMEM;
     }
     T.lanes = (const int32_t *)d_lanes; T.n_actions = (const int32_t *)d_act;
     *out = p;
+    return RS_OK;
+}
+
+// ---- PPO: the update itself (resco_ppo_train.h), four tensor sets
+struct rs_ppo : TrainHandle {
+    PpoTrainTab T{};
+    rs_ppo_config cfg{};
+};
+
+extern "C" void rs_ppo_destroy(rs_ppo_handle p) { train_destroy(p); }
+
+extern "C" int rs_ppo_create(int32_t device_id, int32_t n_signals, int32_t lmax, const int32_t *lanes, const int32_t *n_actions, int32_t amax,
+                             const rs_ppo_config *cfg, const rs_ppo_tensors *params, const rs_ppo_tensors *grads, const rs_ppo_tensors *m,
+                             const rs_ppo_tensors *v, int32_t max_minibatch, rs_ppo_handle *out) {
+    const int rc = train_create("rs_ppo_create", "1 <= signals, 2 <= lmax <= 17, 1 <= amax <= 8, 1 <= max_minibatch", device_id, n_signals, lmax, lanes,
+                                n_actions, amax, cfg, {params, grads, m, v}, PPT_NT, max_minibatch, ppt_p_size(PPO_NH), out, [&](rs_ppo *p) {
+        return p->alloc((void **)&p->T.sqpart, (size_t)n_signals * (p->T.H + 1) * 2 * sizeof(float));
+    });
+    if (rc != RS_OK) return rc;
+    rs_ppo *p = *out;
+    p->cfg = *cfg;
+    PpoTrainTab &T = p->T;
+    T.grad = train_tensors(grads, PPT_NT); T.m = train_tensors(m, PPT_NT); T.v = train_tensors(v, PPT_NT);
+    T.hp = PpoHyper{(float)cfg->clip_eps, (float)cfg->entropy_coef, (float)cfg->value_coef};
     return RS_OK;
 }
 
@@ -887,7 +917,7 @@ static void ppo_grad_launch(const rs_ppo *p, const PpoBatch &D, float *loss_out,
     const int tiles = (D.B + PPT_TM - 1) / PPT_TM, chunks = (tiles * PPT_TM + PPT_CH - 1) / PPT_CH;
     hipLaunchKernelGGL(ppo_fwd_bwd_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
     hipLaunchKernelGGL(ppo_fc1_bwd_kernel, dim3(T.H * 2, chunks, T.S), dim3(PPT_T), 0, st, T, D);
-    hipLaunchKernelGGL(ppo_reduce_kernel, dim3(T.S, T.H + (PPT_N_SMALL + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, T, D.B, loss_out);
+    hipLaunchKernelGGL(ppo_reduce_kernel, dim3(T.S, T.H + (ppt_n_small(PPO_NH) + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, T, D.B, loss_out);
 }
 static void ppo_step_launch(rs_ppo *p, hipStream_t st) {
     const PpoTrainTab &T = p->T;
@@ -901,7 +931,7 @@ extern "C" int rs_ppo_grad(rs_ppo_handle p, const void *obs, const int32_t *act,
                            const int32_t *idx, int32_t B, float *loss_out, void *stream) {
     if (!p) { g_create_err = "rs_ppo_grad: NULL handle"; return RS_EINVAL; }
     if (!obs || !act || !logp || !adv || !ret || !idx) { g_create_err = "rs_ppo_grad: a data pointer is NULL"; return RS_EINVAL; }
-    if (B < 1 || B > p->max_minibatch) { g_create_err = "rs_ppo_grad: need 1 <= B <= max_minibatch of rs_ppo_create"; return RS_EINVAL; }
+    if (B < 1 || B > p->max_batch) { g_create_err = "rs_ppo_grad: need 1 <= B <= max_minibatch of rs_ppo_create"; return RS_EINVAL; }
     if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
     ppo_grad_launch(p, PpoBatch{(const __half *)obs, act, logp, adv, ret, idx, B}, loss_out, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
@@ -918,7 +948,7 @@ extern "C" int rs_ppo_fit(rs_ppo_handle p, const void *obs, const int32_t *act, 
                           const int32_t *perm, int32_t epochs, int32_t minibatch, float *loss_out, void *stream) {
     if (!p) { g_create_err = "rs_ppo_fit: NULL handle"; return RS_EINVAL; }
     if (!obs || !act || !logp || !adv || !ret || !perm) { g_create_err = "rs_ppo_fit: a data pointer is NULL"; return RS_EINVAL; }
-    if (n < 1 || epochs < 1 || minibatch < 1 || minibatch > p->max_minibatch) {
+    if (n < 1 || epochs < 1 || minibatch < 1 || minibatch > p->max_batch) {
         g_create_err = "rs_ppo_fit: need 1 <= n, 1 <= epochs, 1 <= minibatch <= max_minibatch of rs_ppo_create"; return RS_EINVAL;
     }
     if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
@@ -933,84 +963,32 @@ extern "C" int rs_ppo_fit(rs_ppo_handle p, const void *obs, const int32_t *act, 
 
 extern "C" int64_t rs_ppo_steps(rs_ppo_handle p) { return p ? (int64_t)p->t : -1; }
 
-// ---- IDQN: the DQN update (resco_dqn_train.h).  The five tensor sets and the ring are the caller's; the library owns the workspace,
-// the index array of rs_dqn_update and t.
-struct rs_dqn {
-    int device = 0;
+// ---- IDQN: the DQN update (resco_dqn_train.h), five tensor sets and the caller's ring; the library also owns the index array of
+// rs_dqn_update
+struct rs_dqn : TrainHandle {
     DqnTrainTab T{};
     rs_dqn_config cfg{};
-    int max_batch = 0;
-    long long t = 0;            // Adam steps taken
     int32_t *idx = nullptr;     // [max_batch][S][2]: the minibatch rs_dqn_update draws
     const void *ring_ok[4] = {nullptr, nullptr, nullptr, nullptr};     // the ring arrays last found on this handle's device (dqn_check)
-    std::vector<void *> allocs;
 };
 
-extern "C" void rs_dqn_destroy(rs_dqn_handle p) {
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    (void)hipDeviceSynchronize();
-    for (void *d : p->allocs) (void)hipFree(d);
-    delete p;
-}
-
-static bool dqn_tensors_complete(const rs_dqn_tensors *t) {
-    return t && t->conv_w && t->conv_b && t->fc1_w && t->fc1_b && t->fc2_w && t->fc2_b && t->fc3_w && t->fc3_b;
-}
-static DqnTensors dqn_tensors(const rs_dqn_tensors *t) {
-    return DqnTensors{{t->conv_w, t->conv_b, t->fc1_w, t->fc1_b, t->fc2_w, t->fc2_b, t->fc3_w, t->fc3_b}};
-}
+extern "C" void rs_dqn_destroy(rs_dqn_handle p) { train_destroy(p); }
 
 extern "C" int rs_dqn_create(int32_t device_id, int32_t n_signals, int32_t lmax, const int32_t *lanes, const int32_t *n_actions, int32_t amax,
                              const rs_dqn_config *cfg, const rs_dqn_tensors *params, const rs_dqn_tensors *target, const rs_dqn_tensors *grads,
                              const rs_dqn_tensors *m, const rs_dqn_tensors *v, int32_t max_batch, rs_dqn_handle *out) {
-    if (!out) return RS_EINVAL;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_err = "no HIP device visible (this library has no CPU fallback)"; return RS_EHIP; }
-    if (device_id < 0 || device_id >= ndev || n_signals <= 0 || lmax < 2 || lmax > 17 || amax < 1 || amax > PPT_AMAX || !lanes || !n_actions || !cfg ||
-        max_batch < 1) {
-        g_create_err = "rs_dqn_create: bad argument (a visible device, 1 <= signals, 2 <= lmax <= 17, 1 <= amax <= 8, 1 <= max_batch)"; return RS_EINVAL;
-    }
-    if (!dqn_tensors_complete(params) || !dqn_tensors_complete(target) || !dqn_tensors_complete(grads) || !dqn_tensors_complete(m) ||
-        !dqn_tensors_complete(v)) {
-        g_create_err = "rs_dqn_create: a tensor pointer is NULL"; return RS_EINVAL;
-    }
-    for (int s = 0; s < n_signals; ++s)
-        if (lanes[s] < 2 || lanes[s] > lmax || n_actions[s] < 1 || n_actions[s] > amax) {
-            g_create_err = "rs_dqn_create: 2 <= lanes[s] <= lmax and 1 <= n_actions[s] <= amax"; return RS_EINVAL;
-        }
-    if (hipSetDevice(device_id) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RS_EHIP; }
-    rs_dqn *p = new (std::nothrow) rs_dqn();
-    if (!p) return RS_ENOMEM;
-    p->device = device_id; p->max_batch = max_batch; p->cfg = *cfg;
+    constexpr int NT = PT_FC3_B + 1;
+    const int rc = train_create("rs_dqn_create", "a visible device, 1 <= signals, 2 <= lmax <= 17, 1 <= amax <= 8, 1 <= max_batch", device_id, n_signals, lmax,
+                                lanes, n_actions, amax, cfg, {params, target, grads, m, v}, NT, max_batch, ppt_p_size(DQN_NH), out, [&](rs_dqn *p) {
+        return p->alloc((void **)&p->T.y, (size_t)n_signals * p->T.bpad_max * sizeof(float)) &&
+               p->alloc((void **)&p->idx, (size_t)max_batch * n_signals * 2 * sizeof(int32_t));
+    });
+    if (rc != RS_OK) return rc;
+    rs_dqn *p = *out;
+    p->cfg = *cfg;
     DqnTrainTab &T = p->T;
-    T.S = n_signals; T.lmax = lmax; T.amax = amax; T.H = lmax - 1;
-    T.par = dqn_tensors(params); T.tgt = dqn_tensors(target); T.grad = dqn_tensors(grads); T.m = dqn_tensors(m); T.v = dqn_tensors(v);
+    T.tgt = train_tensors(target, NT); T.grad = train_tensors(grads, NT); T.m = train_tensors(m, NT); T.v = train_tensors(v, NT);
     T.gamma = (float)cfg->gamma;
-    T.tiles_max = (max_batch + PPT_TM - 1) / PPT_TM;
-    T.bpad_max = T.tiles_max * PPT_TM;
-    T.chunks_max = (T.bpad_max + PPT_CH - 1) / PPT_CH;
-    const size_t S = (size_t)n_signals, H = (size_t)T.H;
-    auto dev_alloc = [&](void **d, size_t bytes) {
-        if (hipMalloc(d, bytes) != hipSuccess) return false;
-        p->allocs.push_back(*d);
-        return true;
-    };
-    void *d_lanes = nullptr, *d_act = nullptr;
-    if (!dev_alloc(&d_lanes, S * 4) || !dev_alloc(&d_act, S * 4) || !dev_alloc((void **)&T.dz1, S * T.bpad_max * 64 * sizeof(float)) ||
-        !dev_alloc((void **)&T.y, S * T.bpad_max * sizeof(float)) || !dev_alloc((void **)&T.part, S * T.tiles_max * DQT_P_SIZE * sizeof(float)) ||
-        !dev_alloc((void **)&T.pw1, (size_t)T.chunks_max * S * H * 256 * 64 * sizeof(float)) ||
-        !dev_alloc((void **)&T.pconv, (size_t)T.chunks_max * S * H * 64 * 5 * sizeof(float)) ||
-        !dev_alloc((void **)&p->idx, (size_t)max_batch * S * 2 * sizeof(int32_t)) ||
-        hipMemcpy(d_lanes, lanes, S * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_act, n_actions, S * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        g_create_err = "rs_dqn_create: device allocation / upload failed";
-        (void)hipGetLastError();
-        rs_dqn_destroy(p);
-        return RS_ENOMEM;
-    }
-    T.lanes = (const int32_t *)d_lanes; T.n_actions = (const int32_t *)d_act;
-    *out = p;
     return RS_OK;
 }
 
@@ -1052,7 +1030,7 @@ static void dqn_grad_launch(const rs_dqn *p, const DqnBatch &D, float *loss_out,
     hipLaunchKernelGGL(dqn_target_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
     hipLaunchKernelGGL(dqn_fwd_bwd_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
     hipLaunchKernelGGL(dqn_fc1_bwd_kernel, dim3(T.H * 2, chunks, T.S), dim3(PPT_T), 0, st, T, D);
-    hipLaunchKernelGGL(dqn_reduce_kernel, dim3(T.S, T.H + (DQT_N_SMALL + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, T, D.B, loss_out);
+    hipLaunchKernelGGL(dqn_reduce_kernel, dim3(T.S, T.H + (ppt_n_small(DQN_NH) + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, T, D.B, loss_out);
 }
 static void dqn_step_launch(rs_dqn *p, hipStream_t st) {
     const PpoStepConsts K = ppo_step_consts(p->cfg.lr, p->cfg.adam_eps, p->cfg.beta1, p->cfg.beta2, 0.0, p->t + 1);
