@@ -73,12 +73,6 @@ class FusedIDQN:
         self.net, self.device, self.seed = net, int(device), int(seed) & 0xFFFFFFFF
         self.S, self.lmax = len(net.lanes), net.lmax
         self._lib = load_library()
-        L = self._lib
-        vp = C.c_void_p
-        L.rs_idqn_create.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [vp] * 9 + [C.POINTER(vp)]
-        L.rs_idqn_act.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
-        L.rs_idqn_destroy.argtypes = [vp]
-        L.rs_idqn_destroy.restype = None
         self._h = None
         self._actions = {}
         self.refresh()
@@ -113,7 +107,6 @@ class FusedIDQN:
         self._h = h
         lanes = np.asarray(self.net.lanes, np.int32)            # the signals' own head sizes: padded lanes are skipped
         self._check_padded_rows_are_zero()
-        self._lib.rs_idqn_set_lanes.argtypes = [C.c_void_p, C.c_void_p]
         if self._lib.rs_idqn_set_lanes(self._h, lanes.ctypes.data) != 0:
             raise RuntimeError('rs_idqn_set_lanes failed')
 
@@ -156,9 +149,7 @@ class FusedIDQN:
         in_place = net.conv_w.dtype == torch.float32
         for k, t in (('conv_w', net.conv_w), ('conv_b', net.conv_b), ('b1', net.fc1_b), ('b2', net.fc2_b)):
             d[k] = t.detach() if (in_place and t.is_contiguous()) else t.detach().float().contiguous()
-        L = self._lib
-        L.rs_idqn_set_device_weights.argtypes = [C.c_void_p] * 9
-        rc = L.rs_idqn_set_device_weights(self._h, *[d[k].data_ptr() for k in ('conv_w', 'conv_b', 'w1', 'b1', 'w2', 'b2', 'w3', 'b3')])
+        rc = self._lib.rs_idqn_set_device_weights(self._h, *[d[k].data_ptr() for k in ('conv_w', 'conv_b', 'w1', 'b1', 'w2', 'b2', 'w3', 'b3')])
         if rc != 0:
             raise RuntimeError('rs_idqn_set_device_weights failed (%d)' % rc)
 

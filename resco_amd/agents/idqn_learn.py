@@ -22,6 +22,7 @@ import copy
 import torch
 
 from .idqn_rollout import BatchedIDQN
+from .trunk import fc1_row_mask
 
 
 class DeviceReplay:
@@ -126,11 +127,7 @@ class BatchedDQNLearner:
         self.t = 0              # agent steps seen (PFRL's self.t)
         self.n_updates = 0
         # padded lanes feed relu(conv bias) into fc1: their rows are zero at load and must stay zero
-        H = qnet.lmax - 1
-        mask = torch.zeros(len(qnet.lanes), 64, H, 4, dtype=qnet.fc1_w.dtype, device=qnet.fc1_w.device)
-        for s, l in enumerate(qnet.lanes):
-            mask[s, :, :l - 1] = 1.0
-        self._fc1_mask = mask.reshape(len(qnet.lanes), 64 * H * 4, 1)
+        self._fc1_mask = fc1_row_mask(qnet.lanes, qnet.lmax, qnet.fc1_w.dtype, qnet.fc1_w.device)
         qnet.fc1_w.register_hook(lambda g: g * self._fc1_mask)
 
     def loss(self, o, a, r, o2, d):

@@ -6,71 +6,33 @@ stacked Q-networks, torch.optim.Adam -- in HIP kernels, all in fp32, every signa
 read in place.  All updates of an agent step are ONE call through the ABI.  The network's own parameter storages are updated in
 place: `net` stays the source of truth, `FusedIDQN.refresh_on_device()` and `state_dict()` work unchanged.  Gradients, Adam moments
 and the target network are torch tensors this object owns (`.grads`, `.m`, `.v`: name -> tensor; `.target`: a BatchedIDQN); the
-library owns only its workspace and the step counter.  The minibatches come from the library's counter hash, not from a torch
-generator: the distribution is DeviceReplay.sample's, the draws are not.  There is no CPU fallback.
+library owns only its workspace and the step counter (the handle's life cycle, .n_updates and .step() are
+learn_fused.FusedLearnerBase's).  The minibatches come from the library's counter hash, not from a torch generator: the distribution
+is DeviceReplay.sample's, the draws are not.  There is no CPU fallback.
 """
 import copy
 import ctypes as C
 
 import torch
 
-from ..sim import DQN_TENSORS, DQNConfig, DQNRing, DQNTensors, load_library, torch_stream
+from ..sim import DQN_TENSORS, DQNConfig, DQNRing, DQNTensors, torch_stream
 from .idqn_rollout import BatchedIDQN
+from .learn_fused import FusedLearnerBase
 
 
-class FusedDQNLearner:
+class FusedDQNLearner(FusedLearnerBase):
+    NAME, PREFIX, TENSORS, TENSOR_SET = 'FusedDQNLearner', 'rs_dqn', DQN_TENSORS, DQNTensors
+
     def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, seed=0):
         assert isinstance(net, BatchedIDQN)
-        for k in DQN_TENSORS:
-            p = getattr(net, k)
-            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                raise RuntimeError('FusedDQNLearner needs contiguous float32 device parameters: the update is a HIP kernel (there is no CPU fallback)')
-        self.net = net
+        super().__init__(net)
         self.gamma, self.lr, self.adam_eps = float(gamma), float(lr), 1e-8
         self.batch_size, self.target_update, self.seed = int(batch_size), int(target_update), int(seed) & 0xFFFFFFFF
         self.t = 0              # agent steps seen (PFRL's self.t)
-        self._lib = load_library()
-        if not hasattr(self._lib, 'rs_dqn_create'):
-            raise RuntimeError('the loaded library has no rs_dqn_create: rebuild it (there is no CPU fallback)')
-        self.device = net.fc1_w.device
         self.target = copy.deepcopy(net)
         for p in self.target.parameters():
             p.requires_grad_(False)
-        S = len(net.lanes)
-        zeros = lambda: {k: torch.zeros_like(getattr(net, k).detach()) for k in DQN_TENSORS}
-        self.grads, self.m, self.v = zeros(), zeros(), zeros()
-        self.loss_out = torch.zeros(S, dtype=torch.float32, device=self.device)
-        sets = [DQNTensors(*[getattr(n, k).data_ptr() for k in DQN_TENSORS]) for n in (net, self.target)]
-        sets += [DQNTensors(*[d[k].data_ptr() for k in DQN_TENSORS]) for d in (self.grads, self.m, self.v)]
-        cfg = DQNConfig(self.lr, self.adam_eps, 0.9, 0.999, self.gamma)
-        lanes, acts = (C.c_int32 * S)(*net.lanes), (C.c_int32 * S)(*net.actions)
-        h = C.c_void_p()
-        self._h, self._keep = None, None
-        torch.cuda.synchronize(self.device)
-        rc = self._lib.rs_dqn_create(self.device.index or 0, S, net.lmax, lanes, acts, net.amax, C.byref(cfg), *[C.byref(t) for t in sets],
-                                     self.batch_size, C.byref(h))
-        if rc != 0:
-            self._fail('rs_dqn_create', rc)
-        self._h = h
-
-    def close(self):
-        if self._h is not None:
-            self._lib.rs_dqn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def n_updates(self):
-        """Adam steps taken so far"""
-        return 0 if self._h is None else int(self._lib.rs_dqn_steps(self._h))
-
-    def _fail(self, name, rc):
-        raise RuntimeError('%s failed (%d): %s' % (name, rc, (self._lib.rs_last_error(None) or b'').decode()))
+        self._create(DQNConfig(self.lr, self.adam_eps, 0.9, 0.999, self.gamma), self.batch_size, more_nets=(self.target,))     # (a CPU net raises)
 
     def _ring(self, replay):
         """rs_dqn_ring over a DeviceReplay's own arrays (no copies) at its present position"""
@@ -111,12 +73,6 @@ class FusedDQNLearner:
         if rc != 0:
             self._fail('rs_dqn_grad', rc)
         return self.grads
-
-    def step(self):
-        """One Adam step on what .grads holds."""
-        rc = self._lib.rs_dqn_step(self._h, torch_stream(self.device.index))
-        if rc != 0:
-            self._fail('rs_dqn_step', rc)
 
     def update(self, replay, updates=1):
         """`updates` times [sample -> gradient -> Adam step], enqueued by one call.  Returns .loss_out (the last update's)."""

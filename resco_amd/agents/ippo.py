@@ -12,6 +12,9 @@ PFRL is not vendored in the reference tree and not installed here, so - as for D
 restates the published PPO update with those settings and is checked against an unbatched PyTorch fp32 restatement
 built from `reference_ppo_network` (tests/test_ippo.py), not against PFRL itself.
 
+The trunk -- stacked parameters, weight import, forward up to fc2 -- is trunk.BatchedTrunk's, shared with IDQN; BatchedIPPO adds the
+value head and the gradient hooks that keep the weights of padded lanes and actions zero.
+
 What is different by design: the S agents are one set of stacked parameters under one Adam (element-wise, disjoint
 parameters: equal to S optimisers); the loss is the sum of the per-signal losses; gradient clipping and advantage
 standardisation are done per signal as S separate agents would.  A rollout segment holds T env-steps of all N
@@ -23,6 +26,8 @@ import math
 
 import torch
 import torch.nn as nn
+
+from .trunk import BatchedTrunk, fc1_row_mask
 
 
 class ReferencePPONet(nn.Module):
@@ -45,84 +50,35 @@ class ReferencePPONet(nn.Module):
         return self.pi(z), self.v(z).squeeze(-1)
 
 
-class BatchedIPPO(nn.Module):
+class BatchedIPPO(BatchedTrunk):
+    """The trunk with fc3 as the policy head, plus a value head."""
+    reference_module = ReferencePPONet
+
     def __init__(self, lanes_per_signal, actions_per_signal, dtype=torch.float32, device='cpu'):
-        super().__init__()
-        self.lanes = [int(x) for x in lanes_per_signal]
-        self.actions = [int(x) for x in actions_per_signal]
-        S, self.lmax, self.amax = len(self.lanes), max(self.lanes), max(self.actions)
-        H = self.lmax - 1
-        kw = dict(dtype=dtype, device=device)
-        self.conv_w = nn.Parameter(torch.zeros(S * 64, 1, 2, 2, **kw))
-        self.conv_b = nn.Parameter(torch.zeros(S * 64, **kw))
-        self.fc1_w = nn.Parameter(torch.zeros(S, 64 * H * 4, 64, **kw))
-        self.fc1_b = nn.Parameter(torch.zeros(S, 64, **kw))
-        self.fc2_w = nn.Parameter(torch.zeros(S, 64, 64, **kw))
-        self.fc2_b = nn.Parameter(torch.zeros(S, 64, **kw))
-        self.fc3_w = nn.Parameter(torch.zeros(S, 64, self.amax, **kw))      # policy head (named as FusedIDQN packs it)
-        self.fc3_b = nn.Parameter(torch.zeros(S, self.amax, **kw))
-        self.v_w = nn.Parameter(torch.zeros(S, 64, 1, **kw))
-        self.v_b = nn.Parameter(torch.zeros(S, 1, **kw))
-        amask = torch.zeros(S, self.amax, dtype=torch.bool)
-        for s, a in enumerate(self.actions):
-            amask[s, :a] = True
-        self.register_buffer('action_mask', amask.to(device))
-        fmask = torch.zeros(S, 64, H, 4, dtype=dtype)
-        for s, l in enumerate(self.lanes):
-            fmask[s, :, :l - 1] = 1.0
-        self.register_buffer('fc1_mask', fmask.reshape(S, 64 * H * 4, 1).to(device))
+        super().__init__(lanes_per_signal, actions_per_signal, dtype=dtype, device=device)
+        S = len(self.lanes)
+        self.v_w = nn.Parameter(torch.zeros(S, 64, 1, dtype=dtype, device=device))
+        self.v_b = nn.Parameter(torch.zeros(S, 1, dtype=dtype, device=device))
+        self.register_buffer('fc1_mask', fc1_row_mask(self.lanes, self.lmax, dtype, device))
         # padded lanes feed relu(conv bias) into fc1 and padded actions are masked: their weights stay zero
         self.fc1_w.register_hook(lambda g: g * self.fc1_mask)
         self.fc3_w.register_hook(lambda g: g * self.action_mask.unsqueeze(1))
         self.fc3_b.register_hook(lambda g: g * self.action_mask)
 
-    @classmethod
-    def from_scenario(cls, sc, **kw):
-        lanes = (sc.sig_obs_start[1:] - sc.sig_obs_start[:-1]).tolist()
-        return cls(lanes, sc.tls_ngreen.tolist(), **kw)
-
     @torch.no_grad()
     def load_reference_modules(self, modules):
         """modules[s]: a ReferencePPONet(L_s, A_s) (or any module with the same .trunk / .pi / .v)."""
-        H = self.lmax - 1
         for s, m in enumerate(modules):
-            conv, fc1, fc2 = m.trunk[0], m.trunk[3], m.trunk[5]
-            hs, A = self.lanes[s] - 1, self.actions[s]
-            self.conv_w[s * 64:(s + 1) * 64] = conv.weight.to(self.conv_w)
-            self.conv_b[s * 64:(s + 1) * 64] = conv.bias.to(self.conv_b)
-            full = torch.zeros(64, 64, H, 4, dtype=fc1.weight.dtype)
-            full[:, :, :hs] = fc1.weight.reshape(64, 64, hs, 4)
-            self.fc1_w[s] = full.reshape(64, 64 * H * 4).t().to(self.fc1_w)
-            self.fc1_b[s] = fc1.bias.to(self.fc1_b)
-            self.fc2_w[s] = fc2.weight.t().to(self.fc2_w)
-            self.fc2_b[s] = fc2.bias.to(self.fc2_b)
-            self.fc3_w[s].zero_()
-            self.fc3_b[s].zero_()
-            self.fc3_w[s, :, :A] = m.pi.weight.t().to(self.fc3_w)
-            self.fc3_b[s, :A] = m.pi.bias.to(self.fc3_b)
+            self.load_trunk(s, m.trunk[0], m.trunk[3], m.trunk[5])
+            self.load_head(s, m.pi.weight, m.pi.bias)
             self.v_w[s] = m.v.weight.t().to(self.v_w)
             self.v_b[s] = m.v.bias.to(self.v_b)
         return self
 
-    @torch.no_grad()
-    def init_like_reference(self, seed=0):
-        g = torch.random.get_rng_state()
-        torch.manual_seed(seed)
-        mods = [ReferencePPONet(l, a) for l, a in zip(self.lanes, self.actions)]
-        torch.random.set_rng_state(g)
-        self.load_reference_modules(mods)
-        return mods
-
     def forward(self, obs):
         """obs [B, S, Lmax, 5] -> logits [B, S, Amax] (-inf beyond a signal's actions), value [B, S]."""
-        B, S = obs.shape[0], obs.shape[1]
-        y = torch.nn.functional.conv2d(obs.to(self.conv_w.dtype), self.conv_w, self.conv_b, groups=S)
-        y = torch.relu(y).reshape(B, S, -1).transpose(0, 1)
-        y = torch.relu(torch.baddbmm(self.fc1_b.unsqueeze(1), y, self.fc1_w))
-        y = torch.relu(torch.baddbmm(self.fc2_b.unsqueeze(1), y, self.fc2_w))
-        logits = torch.baddbmm(self.fc3_b.unsqueeze(1), y, self.fc3_w).transpose(0, 1)
-        value = torch.baddbmm(self.v_b.unsqueeze(1), y, self.v_w).squeeze(-1).transpose(0, 1)
-        return logits.masked_fill(~self.action_mask, float('-inf')), value
+        y = self.features(obs)
+        return self.head(y), torch.baddbmm(self.v_b.unsqueeze(1), y, self.v_w).squeeze(-1).transpose(0, 1)
 
     @torch.no_grad()
     def act(self, obs, generator=None):

@@ -6,81 +6,37 @@ clip_grad_per_signal, torch.optim.Adam -- in HIP kernels, all in fp32, every sig
 rows gathered through an index array.  One update (all epochs and minibatches) is ONE call through the ABI.  The network's own
 parameter storages are updated in place: `net` stays the source of truth, `FusedIPPO.refresh_on_device()` and `state_dict()` work
 unchanged.  Gradients and Adam moments are torch tensors this object owns (`.grads`, `.m`, `.v`: name -> tensor); the library owns
-only its workspace and the step counter.  There is no CPU fallback.
+only its workspace and the step counter (the handle's life cycle, .n_updates and .step() -- per-signal clipping and one Adam step
+on what .grads holds -- are learn_fused.FusedLearnerBase's).  There is no CPU fallback.
 """
-import ctypes as C
-
 import torch
 
-from ..sim import PPO_TENSORS, PPOConfig, PPOTensors, load_library, torch_stream
+from ..sim import PPO_TENSORS, PPOConfig, PPOTensors, torch_stream
 from .ippo import BatchedIPPO, BatchedPPOLearner
+from .learn_fused import FusedLearnerBase
 
 
-class FusedPPOLearner:
+class FusedPPOLearner(FusedLearnerBase):
+    NAME, PREFIX, TENSORS, TENSOR_SET, LOSS_SHAPE = 'FusedPPOLearner', 'rs_ppo', PPO_TENSORS, PPOTensors, (3,)
+
     def __init__(self, net, lr=2.5e-4, adam_eps=1e-5, gamma=0.99, lambd=0.95, clip_eps=0.1, epochs=4, minibatch=256,
                  entropy_coef=0.001, value_coef=1.0, max_grad_norm=0.5):
         assert isinstance(net, BatchedIPPO)
-        self.net = net
+        super().__init__(net)
         self.lr, self.adam_eps = lr, adam_eps
         self.gamma, self.lambd, self.clip_eps, self.epochs, self.minibatch = gamma, lambd, clip_eps, int(epochs), int(minibatch)
         self.entropy_coef, self.value_coef, self.max_grad_norm = entropy_coef, value_coef, max_grad_norm
-        self._lib, self._h, self._keep = None, None, None
-        self.grads = self.m = self.v = self.loss_out = None
         if net.fc1_w.is_cuda:
-            self._create()
-
-    # ---- the handle
-    def _create(self):
-        net = self.net
-        for k in PPO_TENSORS:
-            p = getattr(net, k)
-            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                raise RuntimeError('FusedPPOLearner needs contiguous float32 device parameters: the update is a HIP kernel (there is no CPU fallback)')
-        self._lib = load_library()
-        if not hasattr(self._lib, 'rs_ppo_create'):
-            raise RuntimeError('the loaded library has no rs_ppo_create: rebuild it (there is no CPU fallback)')
-        self.device = net.fc1_w.device
-        S = len(net.lanes)
-        zeros = lambda: {k: torch.zeros_like(getattr(net, k).detach()) for k in PPO_TENSORS}
-        self.grads, self.m, self.v = zeros(), zeros(), zeros()
-        self.loss_out = torch.zeros(S, 3, dtype=torch.float32, device=self.device)
-        sets = [PPOTensors(*[getattr(net, k).data_ptr() for k in PPO_TENSORS])]
-        sets += [PPOTensors(*[d[k].data_ptr() for k in PPO_TENSORS]) for d in (self.grads, self.m, self.v)]
-        cfg = PPOConfig(self.lr, self.adam_eps, 0.9, 0.999, self.clip_eps, self.entropy_coef, self.value_coef, self.max_grad_norm)
-        lanes, acts = (C.c_int32 * S)(*net.lanes), (C.c_int32 * S)(*net.actions)
-        h = C.c_void_p()
-        torch.cuda.synchronize(self.device)
-        rc = self._lib.rs_ppo_create(self.device.index or 0, S, net.lmax, lanes, acts, net.amax, C.byref(cfg), *[C.byref(t) for t in sets],
-                                     self.minibatch, C.byref(h))
-        if rc != 0:
-            raise RuntimeError('rs_ppo_create failed (%d): %s' % (rc, (self._lib.rs_last_error(None) or b'').decode()))
-        self._h = h
+            self._need_handle()
 
     def _need_handle(self):
+        """the handle is created as soon as the network is on the device: at construction, else at the first use (a CPU net raises)"""
         if self._h is None:
             if self.net.fc1_w.is_cuda:
-                self._create()
+                self._create(PPOConfig(self.lr, self.adam_eps, 0.9, 0.999, self.clip_eps, self.entropy_coef, self.value_coef, self.max_grad_norm),
+                             self.minibatch)
             else:
                 raise RuntimeError('FusedPPOLearner needs the network on the device: the update is a HIP kernel (there is no CPU fallback)')
-
-    def close(self):
-        if self._h is not None:
-            self._lib.rs_ppo_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def n_updates(self):
-        """Adam steps taken so far"""
-        return 0 if self._h is None else int(self._lib.rs_ppo_steps(self._h))
-
-    def _fail(self, name, rc):
-        raise RuntimeError('%s failed (%d): %s' % (name, rc, (self._lib.rs_last_error(None) or b'').decode()))
 
     # ---- the dataset as the kernels read it
     def _device_dataset(self, ds):
@@ -115,13 +71,6 @@ class FusedPPOLearner:
         if rc != 0:
             self._fail('rs_ppo_grad', rc)
         return self.grads
-
-    def step(self):
-        """Per-signal clipping and one Adam step on what .grads holds (.grads itself stays un-scaled)."""
-        self._need_handle()
-        rc = self._lib.rs_ppo_step(self._h, torch_stream(self.device.index))
-        if rc != 0:
-            self._fail('rs_ppo_step', rc)
 
     def fit(self, dataset, perm):
         """All Adam steps of an update in one call: minibatches perm[e][i : i + minibatch] as BatchedPPOLearner._fit takes them.

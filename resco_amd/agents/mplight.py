@@ -147,13 +147,7 @@ class FusedMPLight:
         if [list(map(int, p)) for p in scenario.phase_pairs] != net.phase_pairs:
             raise ValueError('the network was built for other phase pairs than the scenario has')
         self.pairs, self.valid, self.order = mplight_tables(scenario)
-        self._lib = L = load_library()
-        vp, i32 = C.c_void_p, C.c_int32
-        L.rs_mplight_create.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, C.POINTER(vp)]
-        L.rs_mplight_act.argtypes = [vp, vp, i32, i32, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
-        L.rs_mplight_set_device_weights.argtypes = [vp, vp]
-        L.rs_mplight_destroy.argtypes = [vp]
-        L.rs_mplight_destroy.restype = None
+        self._lib = load_library()
         self._h = None
         self._actions = {}
         self._wdev = None

@@ -42,7 +42,7 @@ _lib = None
 
 def bind(L):
     """ctypes signatures of the C ABI (include/resco_sim.h) on an opened library."""
-    vp, i32 = C.c_void_p, C.c_int32
+    vp, i32, u32, f32 = C.c_void_p, C.c_int32, C.c_uint32, C.c_float
     L.rs_create.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(vp)]
     L.rs_destroy.argtypes = [vp]
     L.rs_destroy.restype = None
@@ -70,8 +70,20 @@ def bind(L):
     L.rs_phase_profile.argtypes = [vp, i32, vp]
     L.rs_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.rs_group_step.argtypes = [vp, i32, vp, i32]
+    if hasattr(L, 'rs_idqn_create'):
+        L.rs_idqn_create.argtypes = [i32, i32, i32] + [vp] * 9 + [C.POINTER(vp)]
+        L.rs_idqn_act.argtypes = [vp, vp, i32, i32, i32, f32, u32, u32, vp, vp, vp, vp]
+        L.rs_idqn_set_lanes.argtypes = [vp, vp]
+        L.rs_idqn_set_device_weights.argtypes = [vp] * 9
+        L.rs_idqn_destroy.argtypes = [vp]
+        L.rs_idqn_destroy.restype = None
+    if hasattr(L, 'rs_mplight_create'):
+        L.rs_mplight_create.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, C.POINTER(vp)]
+        L.rs_mplight_act.argtypes = [vp, vp, i32, i32, f32, u32, u32, vp, vp, vp, vp, vp]
+        L.rs_mplight_set_device_weights.argtypes = [vp, vp]
+        L.rs_mplight_destroy.argtypes = [vp]
+        L.rs_mplight_destroy.restype = None
     if hasattr(L, 'rs_group_rollout'):
-        u32, f32 = C.c_uint32, C.c_float
         L.rs_ippo_act.argtypes = [vp, vp, i32, i32, u32, u32, vp, vp, vp, vp, vp, vp]
         L.rs_group_rollout.argtypes = [vp, i32, vp, vp, i32, i32]
         L.rs_ppo_gae.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp]
@@ -85,7 +97,6 @@ def bind(L):
         L.rs_ppo_destroy.argtypes = [vp]
         L.rs_ppo_destroy.restype = None
     if hasattr(L, 'rs_dqn_create'):
-        u32 = C.c_uint32
         L.rs_dqn_create.argtypes = [i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)]
         L.rs_dqn_sample.argtypes = [vp, vp, i32, u32, u32, vp, vp]
         L.rs_dqn_grad.argtypes = [vp, vp, vp, i32, vp, vp]

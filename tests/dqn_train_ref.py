@@ -2,23 +2,22 @@
 measured against -- BatchedDQNLearner.loss of resco_amd/agents/idqn_learn.py and torch.optim.Adam, evaluated by torch in float64 --
 the same in float32, whose distance from the truth is the yardstick e_ref (a candidate gets 4 e_ref per tensor, for a different
 fixed summation order and nothing else), the Python twin of the minibatch draw, and the host build of the header's scalar functions
-(tests/dqn_train_host).  Everything asserted in here is asserted on the references alone.
+(tests/dqn_train_host).  Everything asserted in here is asserted on the references alone.  What it shares with the PPO update's
+reference (tests/ppo_train_ref.py) -- the trunk, the kink-free redraw, Adam from given gradients, the host build -- is tests/train_ref.py.
 
 The net is small and stacked as idqn_kernel_ref.make_net stacks its own (BatchedIDQN.init_like_reference), but of three signals that
 pair the extremes: lane counts (2, mid, lmax) with action counts (1, 3, 8)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import torch
 
 from idqn_kernel_ref import random_obs
 from oracle_batch import murmur_hash
-from ppo_train_ref import TAU, _real_conv
 from resco_amd.agents.idqn_rollout import BatchedIDQN
+from resco_amd.agents.trunk import fc1_row_mask
+from train_ref import adam_step, build_host, fc3_head, grads_as, near_relu_kinks, net_as, redraw_near_kinks, relu_masks, state_arrays, trunk_forward
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ('conv_w', 'conv_b', 'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b', 'fc3_w', 'fc3_b')
 GAMMA, LR = 0.99, 1e-3
 ACTIONS = (1, 3, 8)
@@ -34,40 +33,15 @@ def make_net(lmax, seed):
     return net
 
 
-def net_as(net, dtype):
-    """a BatchedIDQN of the same signals with net's parameters in `dtype` (CPU)"""
-    m = BatchedIDQN(net.lanes, net.actions, dtype=dtype)
-    with torch.no_grad():
-        for k in NAMES:
-            getattr(m, k).copy_(getattr(net, k).detach().cpu().to(dtype))
-    return m
-
-
-def fc1_mask(net):
-    """float [S, 64 H 4, 1]: 1 on the fc1_w rows of conv rows a signal really has (BatchedDQNLearner's gradient hook)"""
-    H = net.lmax - 1
-    mask = torch.zeros(len(net.lanes), 64, H, 4)
-    for s, l in enumerate(net.lanes):
-        mask[s, :, :l - 1] = 1.0
-    return mask.reshape(len(net.lanes), 64 * H * 4, 1)
-
-
 def forward_all(net, obs):
     """BatchedIDQN.forward restated with every pre-activation returned: conv [n, S, 64, H, 4], z1, z2 [n, S, 64], q [n, S, amax]"""
-    n, S = obs.shape[0], obs.shape[1]
-    H = net.lmax - 1
-    c = torch.nn.functional.conv2d(obs.to(net.conv_w.dtype), net.conv_w, net.conv_b, groups=S)
-    y = torch.relu(c).reshape(n, S, -1).transpose(0, 1)
-    z1 = torch.baddbmm(net.fc1_b.unsqueeze(1), y, net.fc1_w)
-    z2 = torch.baddbmm(net.fc2_b.unsqueeze(1), torch.relu(z1), net.fc2_w)
-    q = torch.baddbmm(net.fc3_b.unsqueeze(1), torch.relu(z2), net.fc3_w).transpose(0, 1)
-    return c.reshape(n, S, 64, H, 4), z1.transpose(0, 1), z2.transpose(0, 1), q.masked_fill(~net.action_mask, float('-inf'))
+    c, z1, z2, a2 = trunk_forward(net, obs)
+    return c, z1, z2, fc3_head(net, a2)
 
 
 def _relu_masks(net, obs):
     with torch.no_grad():
-        c, z1, z2, _ = forward_all(net, torch.from_numpy(obs))
-        return ((c > 0) & _real_conv(net)).numpy(), (z1 > 0).numpy(), (z2 > 0).numpy()
+        return relu_masks(net, *forward_all(net, torch.from_numpy(obs))[:3])
 
 
 def _near_kinks(nets64, obs):
@@ -75,8 +49,7 @@ def _near_kinks(nets64, obs):
     near = np.zeros(obs.shape[:2], bool)
     with torch.no_grad():
         for net in nets64:
-            c, z1, z2, _ = forward_all(net, torch.from_numpy(obs))
-            near |= (((c.abs() < TAU) & _real_conv(net)).flatten(2).any(-1) | (z1.abs() < TAU).any(-1) | (z2.abs() < TAU).any(-1)).numpy()
+            near |= near_relu_kinks(net, *forward_all(net, torch.from_numpy(obs))[:3]).numpy()
     return near
 
 
@@ -94,12 +67,7 @@ def case(lmax, T, N, seed, done_slots=()):
     S = 3
     obs = random_obs(net.lanes, lmax, T * N, rng)
     nets64 = [net_as(net, torch.float64), net_as(target, torch.float64)]
-    for _ in range(100):                                # observations whose forward comes near a ReLU's zero are drawn again
-        near = _near_kinks(nets64, obs)
-        if not near.any():
-            break
-        for r, s in zip(*np.nonzero(near)):
-            obs[r, s, :net.lanes[s]] = rng.random((net.lanes[s], 5)).astype(np.float16)
+    redraw_near_kinks(obs, net.lanes, rng, lambda o: _near_kinks(nets64, o))
     assert not _near_kinks(nets64, obs).any(), 'the case generator left a kink'
     for m64 in nets64:
         m32 = net_as(m64, torch.float32)
@@ -147,29 +115,14 @@ def torch_grads(case, idx, dtype, target=None):
     per, delta = _loss(net, tgt, _batch(case, idx, dtype))
     per.sum().backward()
     grads = {k: getattr(net, k).grad.detach().double() for k in NAMES}
-    grads['fc1_w'] = grads['fc1_w'] * fc1_mask(net).double()
+    grads['fc1_w'] = grads['fc1_w'] * fc1_row_mask(net.lanes, net.lmax, torch.float64)
     return {k: v.numpy() for k, v in grads.items()}, per.detach().double().numpy(), delta.double().numpy()
 
 
 def torch_step(params, grads, state, dtype):
     """torch.optim.Adam(lr=1e-3).step from GIVEN gradients in dtype.  params: a BatchedIDQN (read when state is None); grads: dict name
     -> array; state: what the previous call returned, or None.  -> state: dict(net, opt)"""
-    if state is None:
-        net = net_as(params, dtype)
-        state = dict(net=net, opt=torch.optim.Adam(net.parameters(), lr=LR))
-    for k in NAMES:
-        p = getattr(state['net'], k)
-        p.grad = torch.as_tensor(np.asarray(grads[k])).to(dtype).reshape(p.shape).clone()
-    state['opt'].step()
-    return state
-
-
-def state_arrays(state):
-    """(params, m, v): dicts name -> float64 numpy of a torch_step state"""
-    net, opt = state['net'], state['opt']
-    f = lambda t: t.detach().double().numpy()
-    return ({k: f(getattr(net, k)) for k in NAMES}, {k: f(opt.state[getattr(net, k)]['exp_avg']) for k in NAMES},
-            {k: f(opt.state[getattr(net, k)]['exp_avg_sq']) for k in NAMES})
+    return adam_step(params, grads_as(grads, NAMES, dtype), state, dtype, lr=LR)
 
 
 def torch_update(case, idx, dtype):
@@ -201,12 +154,6 @@ def check_sample(idx, T, N, head, count):
 
 
 def build_dqn_train_host(out_dir):
-    out = os.path.join(str(out_dir), 'dqn_train_host.so')
-    subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math', '-shared',
-                           '-I' + os.path.join(ROOT, 'resco_amd', 'csrc'), os.path.join(ROOT, 'tests', 'dqn_train_host', 'dqn_train_host.cpp'),
-                           '-o', out])
-    L = C.CDLL(out)
     vp, i32, u32, f32 = C.c_void_p, C.c_int32, C.c_uint32, C.c_float
-    L.dqn_train_rows.argtypes = [vp, i32, i32, vp, vp, f32, vp, vp]
-    L.dqn_train_sample.argtypes = [u32, u32, i32, i32, i32, i32, i32, i32, vp]
-    return L
+    return build_host('dqn_train', out_dir, dict(dqn_train_rows=[vp, i32, i32, vp, vp, f32, vp, vp],
+                                                 dqn_train_sample=[u32, u32, i32, i32, i32, i32, i32, i32, vp]))

@@ -2,58 +2,34 @@
 against -- the loss of BatchedPPOLearner.loss, clip_grad_per_signal and torch.optim.Adam of resco_amd/agents/ippo.py, evaluated by
 torch in float64 -- the same in float32, whose distance from the truth is the yardstick e_ref (a candidate gets 4 e_ref per tensor,
 for a different fixed summation order and nothing else), and the host build of the header's scalar functions (tests/ppo_train_host).
-Everything asserted in here is asserted on the references alone."""
+Everything asserted in here is asserted on the references alone.  What it shares with the DQN update's reference
+(tests/dqn_train_ref.py) -- the trunk, the kink-free redraw, Adam from given gradients, the host build -- is tests/train_ref.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import torch
 
 from idqn_kernel_ref import make_net, random_obs
 from resco_amd.agents.ippo import BatchedIPPO
+from train_ref import adam_step, build_host, fc3_head, grads_as, near_relu_kinks, net_as, redraw_near_kinks, relu_masks, state_arrays, trunk_forward  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TAU, RATIO_GAP = 2e-5, 1e-4                 # distance kept from a ReLU's zero / from ratio = 1 -+ clip_eps
+RATIO_GAP = 1e-4                            # distance kept from ratio = 1 -+ clip_eps (from a ReLU's zero: train_ref.TAU)
 HYPER = dict(lr=2.5e-4, adam_eps=1e-5, clip_eps=0.1, entropy_coef=0.001, value_coef=1.0, max_grad_norm=0.5)
 NAMES = ('conv_w', 'conv_b', 'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b', 'fc3_w', 'fc3_b', 'v_w', 'v_b')
-
-
-def net_as(net, dtype):
-    """a BatchedIPPO of the same signals with net's parameters in `dtype` (CPU)"""
-    m = BatchedIPPO(net.lanes, net.actions, dtype=dtype)
-    with torch.no_grad():
-        for k in NAMES:
-            getattr(m, k).copy_(getattr(net, k).detach().cpu().to(dtype))
-    return m
 
 
 def forward_all(net, obs):
     """BatchedIPPO.forward restated with every pre-activation returned: conv [B, S, 64, H, 4], z1, z2 [B, S, 64], logits [B, S, amax]
     (-inf beyond a signal's actions), value [B, S] -- in the dtype of net's parameters"""
-    B, S = obs.shape[0], obs.shape[1]
-    H = net.lmax - 1
-    c = torch.nn.functional.conv2d(obs.to(net.conv_w.dtype), net.conv_w, net.conv_b, groups=S)
-    y = torch.relu(c).reshape(B, S, -1).transpose(0, 1)
-    z1 = torch.baddbmm(net.fc1_b.unsqueeze(1), y, net.fc1_w)
-    z2 = torch.baddbmm(net.fc2_b.unsqueeze(1), torch.relu(z1), net.fc2_w)
-    a2 = torch.relu(z2)
-    logits = torch.baddbmm(net.fc3_b.unsqueeze(1), a2, net.fc3_w).transpose(0, 1)
-    value = torch.baddbmm(net.v_b.unsqueeze(1), a2, net.v_w).squeeze(-1).transpose(0, 1)
-    return (c.reshape(B, S, 64, H, 4), z1.transpose(0, 1), z2.transpose(0, 1), logits.masked_fill(~net.action_mask, float('-inf')), value)
-
-
-def _real_conv(net):
-    """bool [S, 1, H, 1]: conv rows a signal really has (h < L_s - 1)"""
-    H = net.lmax - 1
-    return (torch.arange(H)[None, :] < (torch.tensor(net.lanes)[:, None] - 1)).reshape(len(net.lanes), 1, H, 1)
+    c, z1, z2, a2 = trunk_forward(net, obs)
+    return c, z1, z2, fc3_head(net, a2), torch.baddbmm(net.v_b.unsqueeze(1), a2, net.v_w).squeeze(-1).transpose(0, 1)
 
 
 def _near_kinks(net64, obs, act, logp_old):
     """(bool [n, S]: a real unit's pre-activation within TAU of zero, bool [n, S]: ratio within RATIO_GAP of 1 -+ clip_eps, lp64, v64)"""
     with torch.no_grad():
         c, z1, z2, logits, v = forward_all(net64, torch.from_numpy(obs))
-        near = ((c.abs() < TAU) & _real_conv(net64)).flatten(2).any(-1) | (z1.abs() < TAU).any(-1) | (z2.abs() < TAU).any(-1)
+        near = near_relu_kinks(net64, c, z1, z2)
         lp = torch.log_softmax(logits, -1).gather(-1, torch.from_numpy(act).long().unsqueeze(-1)).squeeze(-1)
         if logp_old is None:
             return near, None, lp, v
@@ -68,7 +44,7 @@ def relu_masks_and_clipped(net, case):
         lp = torch.log_softmax(logits, -1).gather(-1, torch.from_numpy(case['act']).long().unsqueeze(-1)).squeeze(-1)
         ratio = torch.exp(lp - torch.from_numpy(case['logp']).to(lp.dtype))
         e = HYPER['clip_eps']
-        return ((c > 0) & _real_conv(net)).numpy(), (z1 > 0).numpy(), (z2 > 0).numpy(), ((ratio < 1 - e) | (ratio > 1 + e)).numpy()
+        return relu_masks(net, c, z1, z2) + (((ratio < 1 - e) | (ratio > 1 + e)).numpy(),)
 
 
 def case(lmax, n, seed):
@@ -84,12 +60,7 @@ def case(lmax, n, seed):
     obs = random_obs(net.lanes, lmax, n, rng)
     act = np.stack([rng.integers(0, a, n) for a in net.actions], 1).astype(np.int32)
     net64 = net_as(net, torch.float64)
-    for _ in range(100):                                # 1. - 2. observations whose forward comes near a ReLU's zero are drawn again
-        near = _near_kinks(net64, obs, act, None)[0].numpy()
-        if not near.any():
-            break
-        for r, s in zip(*np.nonzero(near)):
-            obs[r, s, :net.lanes[s]] = rng.random((net.lanes[s], 5)).astype(np.float16)
+    redraw_near_kinks(obs, net.lanes, rng, lambda o: _near_kinks(net64, o, act, None)[0].numpy())      # 1. - 2.
     noise = rng.standard_normal((n, S))
     for _ in range(100):                                # 3. the logp_old noise of samples whose ratio comes near a clip boundary likewise
         _, _, lp, v = _near_kinks(net64, obs, act, None)
@@ -134,42 +105,20 @@ def torch_step(params, grads, state, dtype):
     """clip_grad_per_signal (restated without its .float() casts) + torch.optim.Adam.step from GIVEN gradients in dtype.
     params: a BatchedIPPO (read when state is None); grads: dict name -> array; state: what the previous call returned, or None.
     -> state: dict(net, opt, scale [S] of this step); the parameters are state['net']'s, the moments state['opt'].state[p]"""
-    if state is None:
-        net = net_as(params, dtype)
-        state = dict(net=net, opt=torch.optim.Adam(net.parameters(), lr=HYPER['lr'], eps=HYPER['adam_eps']))
-    net = state['net']
-    S = len(net.lanes)
-    g = {k: torch.as_tensor(np.asarray(grads[k])).to(dtype).clone() for k in NAMES}
+    S = len(params.lanes)
+    g = grads_as(grads, NAMES, dtype)
     sq = torch.zeros(S, dtype=dtype)
     for k in NAMES:
         sq += (g[k].reshape(S, -1) ** 2).sum(1)
     scale = torch.clamp(HYPER['max_grad_norm'] / (sq.sqrt() + 1e-6), max=1.0)
-    for k in NAMES:
-        p = getattr(net, k)
-        p.grad = (g[k].reshape(S, -1) * scale.unsqueeze(1)).reshape(p.shape)
-    state['opt'].step()
+    g = {k: g[k].reshape(S, -1) * scale.unsqueeze(1) for k in NAMES}
+    state = adam_step(params, g, state, dtype, lr=HYPER['lr'], eps=HYPER['adam_eps'])
     state['scale'] = scale.double().numpy()
     return state
 
 
-def state_arrays(state):
-    """(params, m, v): dicts name -> float64 numpy of a torch_step state"""
-    net, opt = state['net'], state['opt']
-    f = lambda t: t.detach().double().numpy()
-    return ({k: f(getattr(net, k)) for k in NAMES}, {k: f(opt.state[getattr(net, k)]['exp_avg']) for k in NAMES},
-            {k: f(opt.state[getattr(net, k)]['exp_avg_sq']) for k in NAMES})
-
-
 def build_ppo_train_host(out_dir):
-    out = os.path.join(str(out_dir), 'ppo_train_host.so')
-    subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math', '-shared',
-                           '-I' + os.path.join(ROOT, 'resco_amd', 'csrc'), os.path.join(ROOT, 'tests', 'ppo_train_host', 'ppo_train_host.cpp'),
-                           '-o', out])
-    L = C.CDLL(out)
-    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-    L.ppo_train_rows.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, vp]
-    f64 = C.c_double
-    L.ppo_train_clip.argtypes = [f64, f64, vp]
-    L.ppo_train_clip.restype = None
-    L.ppo_train_adam.argtypes = [vp, vp, vp, vp, vp, i32, f64, f64, f64, f64, i32]
-    return L
+    vp, i32, f32, f64 = C.c_void_p, C.c_int32, C.c_float, C.c_double
+    return build_host('ppo_train', out_dir, dict(ppo_train_rows=[vp, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, vp],
+                                                 ppo_train_clip=([f64, f64, vp], None),
+                                                 ppo_train_adam=[vp, vp, vp, vp, vp, i32, f64, f64, f64, f64, i32]))

@@ -13,12 +13,11 @@ import numpy as np
 import pytest
 import torch
 
-from dqn_train_ref import (NAMES, RING_STATES, _batch, case, check_sample, predict_sample, state_arrays, torch_grads, torch_step,
-                           torch_update)
+from dqn_train_ref import NAMES, RING_STATES, _batch, case, check_sample, predict_sample, torch_grads, torch_step, torch_update
 from resco_amd.agents.idqn_learn import BatchedDQNLearner, DeviceReplay
 from resco_amd.agents.idqn_learn_fused import FusedDQNLearner
-from resco_amd.agents.idqn_rollout import BatchedIDQN
 from resco_amd.sim import DQNConfig, DQNRing, DQNTensors, load_library, torch_stream
+from train_ref import _device_net, _np, assert_adam_state, check_4_e_ref, compare_gradients
 
 pytestmark = pytest.mark.gpu
 
@@ -48,12 +47,6 @@ def _reference(lmax, T, N, B, slots=None):
     frac = (np.abs(d64) > 1).mean()
     assert 0.2 <= frac <= 0.8, 'both branches of the Huber loss must be well populated: %.2f' % frac
     return idx, g64, g32, l64, l32
-
-
-def _device_net(net):
-    m = BatchedIDQN(net.lanes, net.actions)
-    m.load_state_dict(net.state_dict())
-    return m.cuda()
 
 
 def _learner(c, B, **kw):
@@ -88,23 +81,9 @@ def _device_ring(c, unreadable=(), head=0, count=None, pad=PAD_ENVS):
     return rp
 
 
-def _np(d):
-    torch.cuda.synchronize()
-    return {k: (d[k] if isinstance(d, dict) else getattr(d, k)).detach().cpu().numpy().copy() for k in NAMES}
-
-
 def _compare(got, loss, g64, g32, l64, l32):
-    worst = []
-    for k in NAMES:
-        assert np.isfinite(got[k]).all(), k
-        err, e_ref = np.abs(got[k].astype(np.float64) - g64[k]).max(), np.abs(g32[k] - g64[k]).max()
-        print('  %-7s max |g| %.3e  |dev - truth| %.3e  e_ref %.3e  ratio %.2f' % (k, np.abs(g64[k]).max(), err, e_ref, err / max(e_ref, 1e-300)))
-        if err > 4 * e_ref:
-            worst.append((k, err, e_ref))
-    err, e_ref = np.abs(loss.astype(np.float64) - l64).max(), np.abs(l32 - l64).max()
-    print('  loss    max %.3e  |dev - truth| %.3e  e_ref %.3e  ratio %.2f' % (l64.max(), err, e_ref, err / max(e_ref, 1e-300)))
-    if err > 4 * e_ref:
-        worst.append(('loss', err, e_ref))
+    worst = compare_gradients(NAMES, got, g64, g32)
+    check_4_e_ref('loss', loss, l64, l32, worst)
     assert not worst, worst
 
 
@@ -189,10 +168,6 @@ def test_sample_on_the_device(T, N, head, count):
     learner.close()
 
 
-def _ulp(x):
-    return np.spacing(np.abs(x).astype(np.float32)).astype(np.float64)
-
-
 def test_adam_step():
     """Equal gradients into both sides, three steps against torch.optim.Adam(lr=1e-3); the yardstick of the PPO update's Adam test"""
     c = _case(9, 6, 9)
@@ -207,13 +182,7 @@ def test_adam_step():
         learner.step()
         assert learner.n_updates == t
         mine = (_np(net), _np(learner.m), _np(learner.v))
-        for name, got, t64, t32, ulps in zip(('param', 'm', 'v'), mine, state_arrays(st64), state_arrays(st32), (1.0, 0.0, 0.0)):
-            for k in NAMES:
-                err, e_ref = np.abs(got[k].astype(np.float64) - t64[k]), np.abs(t32[k] - t64[k]).max()
-                excess = (err - (4 * e_ref + ulps * _ulp(t64[k]))).max()
-                if excess > 0:
-                    print('t %d %s %s: |dev - truth| %.3e e_ref %.3e' % (t, name, k, err.max(), e_ref))
-                assert excess <= 0.0, (t, name, k, err.max(), e_ref)
+        assert_adam_state(t, NAMES, mine, st64, st32)
     for k in NAMES:                                         # the gradients stay as they were loaded
         assert np.array_equal(learner.grads[k].cpu().numpy(), g[k])
     assert np.abs(_np(net)['fc2_w'] - c['net'].fc2_w.detach().numpy()).max() > 1e-4

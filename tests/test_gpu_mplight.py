@@ -2,7 +2,6 @@
 the fp32 PyTorch FRAP on the simulator's own buffers, through rs_group_step (RS_AGENT_MPLIGHT) against per-pipe act + step and
 against one handle with the whole batch, its refusals, a whole episode, and the held-out training check against the reference's
 published MPLight curves."""
-import ctypes as C
 import json
 import os
 import sys
@@ -153,7 +152,6 @@ def test_refusals():
     L = pol._lib
     acts = torch.zeros(16, 1, dtype=torch.int32, device='cuda')
     assert L.rs_mplight_act(idqn._h, sim.tensor('mplight').data_ptr(), 16, 0, 0.0, 0, 0, None, acts.data_ptr(), None, None, None) != 0
-    L.rs_idqn_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
     assert L.rs_idqn_act(pol.handle, sim.tensor('drq_norm_f16').data_ptr(), 16, 0, 0, 0.0, 0, 0, None, acts.data_ptr(), None, None) != 0
     sim.set_outputs(('drq_norm',))                                      # the mplight buffer switched off
     with pytest.raises(RuntimeError):

@@ -11,11 +11,12 @@ import pytest
 import torch
 
 from conftest import load_scenario
-from ppo_train_ref import NAMES, case, state_arrays, torch_grads, torch_step
+from ppo_train_ref import NAMES, case, torch_grads, torch_step
 from resco_amd.agents.ippo import BatchedIPPO
 from resco_amd.agents.ippo_fused import DeviceRollout, FusedIPPO
 from resco_amd.agents.ippo_learn_fused import FusedPPOLearner
 from resco_amd.sim import BatchedSim, SimGroup, load_library, torch_stream
+from train_ref import _device_net, _np, assert_adam_state, check_4_e_ref, compare_gradients
 
 pytestmark = pytest.mark.gpu
 
@@ -38,12 +39,6 @@ def _reference(lmax, n, B):
     return idx, g64, g32, l64, l32
 
 
-def _device_net(c):
-    net = BatchedIPPO(c['net'].lanes, c['net'].actions)
-    net.load_state_dict(c['net'].state_dict())
-    return net.cuda()
-
-
 def _device_dataset(c, pad=PAD_ROWS):
     """the case's rows followed by `pad` sentinel rows (NaN, action -777) that no kernel may read"""
     S, lmax = c['obs'].shape[1], c['obs'].shape[2]
@@ -53,11 +48,6 @@ def _device_dataset(c, pad=PAD_ROWS):
                 logp=f('logp'), adv=f('adv'), ret=f('ret'))
 
 
-def _np(d):
-    torch.cuda.synchronize()
-    return {k: d[k].detach().cpu().numpy().copy() for k in NAMES}
-
-
 @pytest.mark.parametrize('lmax,n,B', [(2, 40, 33), (9, 130, 96), (17, 100, 70), (5, 1100, 1050)])
 def test_minibatch_gradient(lmax, n, B):
     """B below and across a 64-row tile, every lane count 2 .. 17; B = 1050 = 17 tiles in 3 chunks of the fc1 backward (PPT_CH = 512
@@ -65,25 +55,16 @@ def test_minibatch_gradient(lmax, n, B):
     (1920, 7680 rows) goes through"""
     c = _case(lmax, n)
     idx, g64, g32, l64, l32 = _reference(lmax, n, B)
-    net = _device_net(c)
+    net = _device_net(c['net'])
     learner = FusedPPOLearner(net, minibatch=B)
     ds = _device_dataset(c)
     idx_t = torch.from_numpy(idx).cuda()
     got = _np(learner.grad(ds, idx_t))
     loss = learner.loss_out.cpu().numpy().copy()
     print('lmax %d n %d B %d: %.0f %% of the samples clipped' % (lmax, n, B, 100 * c['clipped_fraction']))
-    worst = []
-    for k in NAMES:
-        assert np.isfinite(got[k]).all(), k
-        err, e_ref = np.abs(got[k].astype(np.float64) - g64[k]).max(), np.abs(g32[k] - g64[k]).max()
-        print('  %-7s max |g| %.3e  |dev - truth| %.3e  e_ref %.3e  ratio %.2f' % (k, np.abs(g64[k]).max(), err, e_ref, err / max(e_ref, 1e-300)))
-        if err > 4 * e_ref:
-            worst.append((k, err, e_ref))
+    worst = compare_gradients(NAMES, got, g64, g32)
     for q, name in enumerate(('policy', 'value', 'entropy')):
-        err, e_ref = np.abs(loss[:, q].astype(np.float64) - l64[:, q]).max(), np.abs(l32[:, q] - l64[:, q]).max()
-        print('  loss %-7s |dev - truth| %.3e  e_ref %.3e' % (name, err, e_ref))
-        if err > 4 * e_ref:
-            worst.append((name, err, e_ref))
+        check_4_e_ref('loss ' + name, loss[:, q], l64[:, q], l32[:, q], worst)
     assert not worst, worst
     # padded fc1 rows and fc3 columns: exactly zero
     pad1 = c['net'].fc1_mask.numpy() == 0
@@ -99,10 +80,6 @@ def test_minibatch_gradient(lmax, n, B):
     learner.close()
 
 
-def _ulp(x):
-    return np.spacing(np.abs(x).astype(np.float32)).astype(np.float64)
-
-
 @pytest.mark.parametrize('gscale', [1.0, 100.0, 0.01])
 def test_clip_and_adam_step(gscale):
     """Equal gradients into both sides, three steps: as they are, x 100 (the clip binds on every signal) and x 0.01 (it binds on
@@ -110,7 +87,7 @@ def test_clip_and_adam_step(gscale):
     c = _case(9, 130)
     _, _, g32, _, _ = _reference(9, 130, 96)
     g = {k: (gscale * g32[k]).astype(np.float32) for k in NAMES}
-    net = _device_net(c)
+    net = _device_net(c['net'])
     learner = FusedPPOLearner(net, minibatch=96)
     for k in NAMES:
         learner.grads[k].copy_(torch.from_numpy(g[k]))
@@ -121,13 +98,7 @@ def test_clip_and_adam_step(gscale):
         learner.step()
         assert learner.n_updates == t
         mine = (_np({k: getattr(net, k) for k in NAMES}), _np(learner.m), _np(learner.v))
-        for name, got, t64, t32, ulps in zip(('param', 'm', 'v'), mine, state_arrays(st64), state_arrays(st32), (1.0, 0.0, 0.0)):
-            for k in NAMES:
-                err, e_ref = np.abs(got[k].astype(np.float64) - t64[k]), np.abs(t32[k] - t64[k]).max()
-                excess = (err - (4 * e_ref + ulps * _ulp(t64[k]))).max()
-                if excess > 0:
-                    print('t %d %s %s: |dev - truth| %.3e e_ref %.3e' % (t, name, k, err.max(), e_ref))
-                assert excess <= 0.0, (t, name, k, err.max(), e_ref)
+        assert_adam_state(t, NAMES, mine, st64, st32)
     for k in NAMES:                                         # the gradients stay as they were loaded
         assert np.array_equal(learner.grads[k].cpu().numpy(), g[k])
     learner.close()
@@ -141,7 +112,7 @@ def test_fit_is_the_loop_of_single_calls(lmax, n, mb, epochs, steps):
     perm = torch.stack([torch.randperm(n, generator=torch.Generator().manual_seed(e)) for e in range(epochs)]).cuda()
 
     def run(fit):
-        net = _device_net(c)
+        net = _device_net(c['net'])
         learner = FusedPPOLearner(net, minibatch=mb, epochs=epochs)
         if fit:
             learner.fit(ds, perm)

@@ -56,3 +56,37 @@ def test_fused_policy_weight_packing():
     f = 5 * H * 4 + 2 * 4 + 1
     assert pk['w1'][1, 5, 1, 1, 3, 1] == np.float16(net.fc1_w[1, f, 32 + 3].item())
     assert not pk['w3'][0][:, 2:32].any() and not pk['w3'][0][:, 34:].any()        # columns beyond the 2 actions of signal 0
+
+
+def test_checkpoint_layout_and_who_masks_the_padded_fc1_rows():
+    """The state_dict keys and the parameter order (saved checkpoints and Adam state depend on them) of both trunk subclasses; and
+    the gradient of an fc1 row of a padded lane -- lanes (2, 3): the smallest net with one -- which a bare BatchedIDQN leaves as it
+    is, its learner's hook makes exactly zero, and BatchedIPPO's own hook makes exactly zero from the start."""
+    from resco_amd.agents.idqn_learn import BatchedDQNLearner
+    from resco_amd.agents.ippo import BatchedIPPO
+    trunk = ['conv_w', 'conv_b', 'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b', 'fc3_w', 'fc3_b']
+    obs = torch.zeros(4, 2, 3, 5)
+    obs[:, 0, :2] = torch.rand(4, 2, 5, generator=torch.Generator().manual_seed(0))
+    obs[:, 1] = torch.rand(4, 3, 5, generator=torch.Generator().manual_seed(1))
+
+    def padded_row_gradient(net):
+        net.zero_grad()
+        out = net(obs)
+        (out[..., 0].sum() if torch.is_tensor(out) else out[0][..., 0].sum() + out[1].sum()).backward()
+        g = net.fc1_w.grad.reshape(2, 64, 2, 4, 64)             # [S, c, h, w, out]
+        assert g[0, :, :1].abs().max() > 0 and g[1].abs().max() > 0
+        return g[0, :, 1:]                                      # signal 0 has one conv row: h = 1 is padding
+
+    nets = []
+    for cls, params, buffers in ((BatchedIDQN, trunk, ['action_mask']), (BatchedIPPO, trunk + ['v_w', 'v_b'], ['action_mask', 'fc1_mask'])):
+        net = cls((2, 3), (2, 3))
+        assert [k for k, _ in net.named_parameters()] == params and list(net.state_dict().keys()) == params + buffers
+        net.init_like_reference(seed=0)
+        with torch.no_grad():
+            net.conv_b.fill_(0.1)                               # relu(conv bias) > 0 is what a padded lane feeds into fc1
+        nets.append(net)
+    idqn, ippo = nets
+    assert padded_row_gradient(idqn).abs().max() > 0, 'the mask is the learner\'s hook, not the net\'s'
+    BatchedDQNLearner(idqn)
+    assert (padded_row_gradient(idqn) == 0).all()
+    assert (padded_row_gradient(ippo) == 0).all()
