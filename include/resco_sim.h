@@ -478,6 +478,59 @@ int rs_dqn_update(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint3
 int64_t rs_dqn_steps(rs_dqn_handle p);
 void rs_dqn_destroy(rs_dqn_handle p);
 
+/* ---- MPLight: the shared-DQN update on the device (resco_amd/csrc/resco_frap_train.h) -------------------------------
+ * What resco_amd/agents/mplight.py does per update -- MPLightReplay.sample, MPLightLearner.loss, its backward through the ONE shared
+ * FRAP network, torch.optim.Adam, the re-pack of the weights for the policy -- as HIP kernels, the replay ring read in place.
+ * params, target, grads, m and v are five caller-owned flat DEVICE vectors of 1365 + 4 D floats in the packed layout of
+ * rs_mplight_create, borrowed for the life of the handle: params, m and v are updated in place, grads is written, target is only
+ * read (copying params into it every target_update env-steps stays with the caller: one device-to-device copy).  A policy pointed
+ * at params (rs_mplight_set_device_weights) acts on the updated weights without any copy.  rs_dqn_config is reused.
+ * rs_mplight_ring: the DEVICE arrays of an MPLightReplay -- obs f32 [capacity][n_envs][n_signals][width], width = 1 + 12 D, act
+ * int16 and rew f32 [capacity][n_envs][n_signals], done one byte per slot -- and its position, by value: head = the next slot to
+ * write, count = slots written.
+ * rs_mplight_dqn_sample: for draw i < batch, k = hash(seed ^ 0x7B1D5C33, update_key, i, 0, 0) % (count - 1), e = hash(.., 1) %
+ * n_envs, s = hash(.., 2) % n_signals, t = (head - count + k) mod capacity, idx_out[i] = (t, e, s) (device int32 [batch][3]); hash =
+ * the simulator's counter hash.  Slot head - 1 (no successor yet) and unwritten slots are never drawn.  (The modulo's bias, below
+ * 2^-32 n per value, is accepted.)
+ * rs_mplight_dqn_grad: the gradient of the minibatch idx (rows (t, e, s); the library holds them inside the ring) into grads:
+ * tgt = rew[t][e][s] + gamma max over ALL n_pairs outputs of Q_target(obs[(t + 1) mod capacity][e][s]) -- not masked by a signal's
+ * valid pairs, as the reference -- or rew alone where done[t] (the successor is then not read); loss = mean over the batch of
+ * Huber(Q(obs[t][e][s])[act] - tgt, delta 1), act clamped into 0 .. n_pairs - 1; loss_out: ONE device float or NULL.
+ * rs_mplight_dqn_step: Adam (no gradient clipping, as PFRL's DQN) on what grads holds; advances the step count.
+ * rs_mplight_dqn_steps: that count.
+ * rs_mplight_dqn_update: for j < n_updates: rs_mplight_dqn_sample with update_key = the step count so far into the handle's own
+ * index array, rs_mplight_dqn_grad, rs_mplight_dqn_step -- the same launches, all enqueued by one call without host synchronisation
+ * or copies.
+ * All calls are asynchronous on `stream`; every sum has one fixed order (no float atomics): the same state gives the same bits.
+ * Workspace, allocated once by rs_mplight_dqn_create: 10 KB per 4 rows of max_batch.  The five vectors, the Adam step and every
+ * result are fp32; the gradient is evaluated in double and rounded once per element (resco_frap_train.h says why), so the Q-values
+ * behind the target are not bit-equal to rs_mplight_act's Q of the same weights.
+ * Refusals (RS_EINVAL, text in rs_last_error(NULL), nothing launched): a NULL handle or pointer, batch outside 1 .. max_batch,
+ * count < 2, capacity < 2, n_envs < 1, n_signals or width not the handle's, head or count outside the ring, n_updates < 1, a ring
+ * array (obs, act, rew, done) or an index array that the runtime does not know as memory of the handle's device (asked once per set
+ * of ring pointers, every call for idx); rs_mplight_dqn_update stops enqueueing at the first launch that fails (RS_EHIP;
+ * rs_mplight_dqn_steps counts the steps that were launched); rs_mplight_dqn_create: a device that is not there, demand_shape not 1
+ * or 4, n_pairs outside 2 .. 16, a movement outside 0 .. 11, n_signals < 1, max_batch < 1. */
+typedef struct rs_mplight_dqn *rs_mplight_dqn_handle;
+typedef struct rs_mplight_ring {
+    const float *obs;
+    const int16_t *act;
+    const float *rew;
+    const uint8_t *done;
+    int32_t capacity, n_envs, n_signals, width, head, count;
+} rs_mplight_ring;
+int rs_mplight_dqn_create(int32_t device_id, int32_t demand_shape, int32_t n_pairs, const int32_t *pairs /* [n_pairs][2] */, int32_t n_signals,
+                          const rs_dqn_config *config, float *params, const float *target, float *grads, float *m, float *v, int32_t max_batch,
+                          rs_mplight_dqn_handle *out);
+int rs_mplight_dqn_sample(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key,
+                          int32_t *idx_out, void *stream);
+int rs_mplight_dqn_grad(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, const int32_t *idx, int32_t batch, float *loss_out, void *stream);
+int rs_mplight_dqn_step(rs_mplight_dqn_handle p, void *stream);
+int rs_mplight_dqn_update(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out,
+                          void *stream);
+int64_t rs_mplight_dqn_steps(rs_mplight_dqn_handle p);
+void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p);
+
 /* static facts */
 int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal);
 

@@ -183,6 +183,20 @@ class FusedMPLight:
         if rc != 0:
             raise RuntimeError('rs_mplight_set_device_weights failed (%d)' % rc)
 
+    def share_weights(self, flat):
+        """Point the kernel at a caller-owned packed float32 device vector (pack_mplight_weights' layout; e.g. the parameter vector
+        of mplight_learn_fused.FusedMPLightLearner) and keep a reference to it: whoever updates that vector in stream order updates
+        the policy, with no re-pack.  refresh() ends the sharing (a new policy over a host copy); refresh_on_device() does not: it
+        packs the network into this same vector -- a copy onto itself where the network's parameters are views of it -- and points
+        the kernel at it again."""
+        n = sum(p.numel() for p in self.net.parameters())
+        if not (flat.is_cuda and flat.dtype == torch.float32 and flat.is_contiguous() and flat.dim() == 1 and flat.numel() == n):
+            raise ValueError('share_weights needs a contiguous float32 device vector of %d elements' % n)
+        rc = self._lib.rs_mplight_set_device_weights(self._h, flat.data_ptr())
+        if rc != 0:
+            raise RuntimeError('rs_mplight_set_device_weights failed (%d)' % rc)
+        self._wdev = flat
+
     def close(self):
         if getattr(self, '_h', None) is not None:
             self._lib.rs_mplight_destroy(self._h)

@@ -1,0 +1,638 @@
+// resco_frap_train.h -- the DQN update of MPLight's ONE shared FRAP network on the device: minibatch sampling from the replay ring,
+// target, loss, the backward through FRAP and Adam (rs_mplight_dqn_create / _sample / _grad / _step / _update of include/resco_sim.h).
+//
+// What it replaces (resco_amd/agents/mplight.py: MPLightReplay.sample, MPLightLearner.loss, its backward, torch.optim.Adam over 14
+// tiny tensors, the torch.cat re-pack for the policy): on the order of a hundred launches per env-step for 1365 + 4 D parameters.
+// Here the ring is read in place (obs f32 [T][N][S][1 + 12 D], act int16 and rew f32 [T][N][S], done one byte per slot), the five
+// vectors (parameters, target, gradients, Adam moments) are flat in the packed layout of resco_frap.h and fp32, as is Adam; the gradient itself is evaluated in double and rounded once
+// (see Precision below).
+//
+// One minibatch row i = ring row idx[i] = (slot t, environment e, signal s), action g = act clamped into 0 .. P - 1:
+//     tgt = rew + gamma max over ALL P outputs of Q_target(obs[(t + 1) mod T][e][s])      (not masked by valid_acts, as the reference)
+//           -- where done[t] is set the successor row is not read at all and tgt = rew
+//     y = Q(obs[t][e][s])[g] = sum_{j != g} y_gj;   loss = mean over the batch of Huber(y - tgt, delta 1)     (dqn_row_loss_grad)
+// Only row g of the P x (P - 1) relation grid carries gradient: the P - 1 items (g, j).  With the forward's split of lane_conv
+// (resco_frap.h) dA_g = sum_j dx_gj, dB_j = dx_gj, and all 12 movement embeddings receive gradient through pair_g and every pair_j.
+// The relation branch and the phase half of the lane embedding depend on no observation: the items accumulate only dR[comp][c]
+// (40 values) and dPE[bit][u] (32 values), and the chains through relation_conv / relation_embedding and through
+// lane_embedding.weight[:, :4] / lane_embedding.bias / p.weight are applied ONCE, in the reduction (frap_grad_element).
+//
+// Launches of one minibatch gradient (rs_mplight_dqn_grad):
+//   1. frap_dqn_tile_kernel, one workgroup of FPT_T = FPT_TM x 16 threads per tile of FPT_TM rows; thread (r, j) is lane j of tile
+//      row r: pair j, the item (g, j) or (j < 12) movement j.  The phases, a barrier between each two, all through the tile's stage
+//      in LDS (FrapStage): the target network's forward on the successor rows (all P outputs), then
+//      the movement embeddings, the pairs, the items' forward with saved activations, the row's loss gradient, the items' backward,
+//      dA_g, the movements' backward.  Then threads own gradient ENTRIES (FG_*: 1258 sums of products over the tile's items or
+//      movements) and walk the stage in one fixed order (frap_tile_entry); the tile's partials go to the workspace (doubles).
+//   2. frap_dqn_reduce_kernel: partials -> gradients, tiles in ascending order, with the two one-time chains; the mean loss.
+// and of one optimiser step (rs_mplight_dqn_step): frap_dqn_adam_kernel (ppo_adam_element with scale {1, 0}: PFRL's DQN does not clip).
+// rs_mplight_dqn_sample is frap_dqn_sample_kernel.
+//
+// Every sum has ONE order, fixed by the shapes alone; no floating-point atomics: the same state gives the same bits.
+//
+// Precision.  y - tgt is a difference of two Q-values several times its size, a row's dy multiplies every gradient the row
+// contributes, and the rows' contributions cancel: an fp32 evaluation of this gradient is about 1e-5 of its largest element away from
+// float64 (torch's own float32 is), and two fp32 evaluations in different operation orders are that far from EACH OTHER -- so how far
+// "a float32 evaluation" is from the truth, the tests' yardstick, depends on the CPU whose torch computes it, by a factor of ten.
+// Compensated fp32 sums remove the summation error, not the rounding of the activations between the layers.  The network is 1.4 k
+// weights and a row a few thousand multiply-adds, FP64 runs at half the fp32 rate on this hardware and one double fma costs less
+// than the ten operations of a compensated fp32 one: the phases, the entries and the reduction compute in double (fpt_t), and every
+// gradient element and the loss are rounded to fp32 once, at the end.  Parameters, gradients, moments and the Adam step stay fp32
+// (ppo_adam_element).  Two consequences.  The pieces below are FRAP's forward written a second time, in double, next to
+// frap_lane_ab / frap_lane_y of resco_frap.h, which stay fp32 for acting (fpt_row_loss likewise restates dqn_row_loss_grad).  And
+// the Q-values the target is formed from are NOT bit-equal to the Q rs_mplight_act computes from the same weights: they differ by
+// fp32 rounding.  The cost: profiles/r11_mplight_device_update.txt (one update 170 - 224 us, 95 % of it the tile kernel).
+//
+// Everything but the kernels is RS_HD and written for the host as well: tests/frap_train_host compiles the phases, the entries, the
+// reduction with its chains and the draw with the host compiler and runs whole minibatches through them on the CPU.
+// Needs resco_frap.h (and its RS_HD, d_hash) before it.
+#pragma once
+#include "resco_dqn_train.h"
+
+#define FRAP_TRAIN_SALT 0x7B1D5C33u     // minibatch draws: d_hash(seed ^ FRAP_TRAIN_SALT; update, draw, 0, 0 | 1 | 2) (distinct from FRAP_SALT)
+#define FPT_TM 4                        // rows of a tile
+#define FPT_G FRAP_PMAX                 // lanes of a row
+#define FPT_T (FPT_TM * FPT_G)          // threads of a tile's workgroup
+#define FPT_W 49                        // the widest observation row (1 + 12 x 4)
+#define FPT_CS (FRAP_C + 1)             // LDS strides of a lane's 20, 16 and 4 values: odd, so that the lanes of a wave spread over the banks
+#define FPT_ES (FRAP_E + 1)
+#define FPT_QS 5
+
+// the gradient entries of a tile: what the items and movements are summed into (the one-time chains turn FG_DR and FG_PE into the
+// gradients of five tensors; every other entry is an element of a tensor)
+enum { FG_H = 0,                        // hidden_layer.weight [k][c]
+       FG_HB = FG_H + 400,              // hidden_layer.bias [k]
+       FG_BM = FG_HB + 20,              // before_merge.weight [k]
+       FG_BMB = FG_BM + 20,             // before_merge.bias
+       FG_LCB = FG_BMB + 1,             // lane_conv.bias [c]
+       FG_LC = FG_LCB + 20,             // lane_conv.weight [c][32]
+       FG_DR = FG_LC + 640,             // d loss / d R[comp][c]
+       FG_PE = FG_DR + 40,              // d loss / d PE[bit][u]
+       FG_LE = FG_PE + 32,              // lane_embedding.weight[u][4 + t]
+       FG_DB = FG_LE + 64,              // d.bias [t]
+       FG_DW = FG_DB + 4,               // d.weight [t][v] (4 D of 16 used)
+       FG_LOSS = FG_DW + 16,            // the rows' Huber terms
+       FG_N = FG_LOSS + 1 };
+
+#ifdef __HIPCC__
+#define RS_FPT_DEV __device__ static inline     // (d_hash of resco_step.h is a device function)
+#else
+#define RS_FPT_DEV static inline                // the host build of the tests brings a d_hash of its own
+#endif
+
+// The weights of one output unit are read when its dot product begins: without the fence the compiler turns the wave-uniform reads
+// of a whole layer (400 to 640 weights) into scalar loads ahead of their use, into SGPRs that then spill by the hundred.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FPT_UNIT(w) asm volatile("" : "+s"(w));
+#else
+#define FPT_UNIT(w)
+#endif
+
+// Draw i of update u: uniform and independent over the slots with a written successor, the environments and the signals, from the
+// project's counter hash.  The oldest valid slot is head - count; slot head - 1 has no successor yet.  hash % n is not exactly
+// uniform: value v < 2^32 mod n is 2^-32 more likely than the others -- with n below 2^21 a relative bias under 5e-4, accepted (as
+// dqn_sample_index).  Needs 2 <= count <= T, 0 <= head < T, 1 <= N, 1 <= S.  out: (t, e, s)
+RS_FPT_DEV void frap_dqn_sample_index(uint32_t seed, uint32_t u, uint32_t i, int T, int N, int S, int head, int count, int32_t *out) {
+    const uint32_t k = d_hash(seed ^ FRAP_TRAIN_SALT, u, i, 0u, 0u) % (uint32_t)(count - 1);
+    out[0] = (int32_t)(((uint32_t)(head - count + T) + k) % (uint32_t)T);
+    out[1] = (int32_t)(d_hash(seed ^ FRAP_TRAIN_SALT, u, i, 0u, 1u) % (uint32_t)N);
+    out[2] = (int32_t)(d_hash(seed ^ FRAP_TRAIN_SALT, u, i, 0u, 2u) % (uint32_t)S);
+}
+
+// ------------------------------------------------------------------------------------------------ the per-lane arithmetic
+typedef double fpt_t;       // what the gradient is evaluated in
+RS_HD inline fpt_t fpt_relu(fpt_t x) { return x > 0.0 ? x : 0.0; }
+// a dot product: one fma per term
+struct FrapDot {
+    fpt_t s;
+    RS_HD explicit FrapDot(fpt_t init) : s(init) {}
+    RS_HD void fma(fpt_t a, fpt_t b) { s = ::fma(a, b, s); }
+    RS_HD void add(fpt_t x) { s += x; }
+    RS_HD fpt_t get() const { return s; }
+};
+RS_HD inline fpt_t frap_sigmoid_once(fpt_t x) { return 1.0 / (1.0 + exp(-x)); }
+// the derived tables of frap_prep_value, in double
+RS_HD inline fpt_t frap_prep_once(const float *w, int D, int k) {
+    const FrapOff o(D);
+    if (k < 32) {
+        const int bit = k >> 4, u = k & 15;
+        FrapDot a(w[o.leb + u]);
+        for (int t = 0; t < 4; ++t) a.fma(w[o.le + u * 8 + t], frap_sigmoid_once(w[o.p + bit * 4 + t]));
+        return a.get();
+    }
+    const int comp = (k - 32) / FRAP_C, c = (k - 32) % FRAP_C;
+    FrapDot a(w[o.rcb + c]);
+    for (int t = 0; t < 4; ++t) a.fma(w[o.rc + c * 4 + t], fpt_relu(w[o.re + comp * 4 + t]));
+    return fpt_relu(a.get());
+}
+
+// movement m of a row: sd = sigmoid(d . demand + d_b) and e = relu(PE[bit] + LE[:, 4:] . sd)
+template <class WP, class Dem>
+RS_HD inline void frap_mv_forward(WP w, int D, const fpt_t *PE, int m, int bit, Dem dem, fpt_t sd[4], fpt_t e[FRAP_E]) {
+    const FrapOff o(D);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        FPT_UNIT(w)
+        FrapDot z(w[o.db + t]);
+        for (int v = 0; v < D; ++v) z.fma(w[o.dw + t * D + v], dem(m, v));
+        sd[t] = frap_sigmoid_once(z.get());
+    }
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) {
+        FPT_UNIT(w)
+        FrapDot x(PE[bit * 16 + u]);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) x.fma(w[o.le + u * 8 + 4 + t], sd[t]);
+        e[u] = fpt_relu(x.get());
+    }
+}
+// its backward from de: dpre = de (e > 0), dz = (LE[:, 4:]^T dpre) sd (1 - sd)
+template <class WP>
+RS_HD inline void frap_mv_backward(WP w, int D, const fpt_t de[FRAP_E], const fpt_t e[FRAP_E], const fpt_t sd[4], fpt_t dpre[FRAP_E], fpt_t dz[4]) {
+    const FrapOff o(D);
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) dpre[u] = e[u] > 0.0 ? de[u] : 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        FPT_UNIT(w)
+        FrapDot a(0.0);
+#pragma unroll
+        for (int u = 0; u < FRAP_E; ++u) a.fma(w[o.le + u * 8 + 4 + t], dpre[u]);
+        dz[t] = a.get() * (sd[t] * (1.0 - sd[t]));
+    }
+}
+// A = LC[:, :16] . pair, B = LC[:, 16:] . pair + LC_b (the forward's split of lane_conv)
+template <class WP>
+RS_HD inline void frap_pair_ab(WP w, int D, const fpt_t pr[FRAP_E], fpt_t A[FRAP_C], fpt_t B[FRAP_C]) {
+    const FrapOff o(D);
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) {
+        FPT_UNIT(w)
+        FrapDot x(0.0), y(w[o.lcb + c]);
+#pragma unroll
+        for (int u = 0; u < FRAP_E; ++u) {
+            x.fma(w[o.lc + c * 32 + u], pr[u]);
+            y.fma(w[o.lc + c * 32 + 16 + u], pr[u]);
+        }
+        A[c] = x.get(); B[c] = y.get();
+    }
+}
+// dpair = LC[:, 16 half : 16 half + 16]^T d
+template <class WP>
+RS_HD inline void frap_pair_backward(WP w, int D, int half, const fpt_t d[FRAP_C], fpt_t dpair[FRAP_E]) {
+    const FrapOff o(D);
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) {
+        FPT_UNIT(w)
+        FrapDot a(0.0);
+#pragma unroll
+        for (int c = 0; c < FRAP_C; ++c) a.fma(w[o.lc + c * 32 + half * 16 + u], d[c]);
+        dpair[u] = a.get();
+    }
+}
+// y_gj with what the backward needs: lc = relu(A_g + B_j), x = lc R, h = relu(H x + H_b)
+template <class WP>
+RS_HD inline fpt_t frap_item_forward(WP w, int D, const fpt_t *Ag, const fpt_t *Bj, const fpt_t *Rc, fpt_t lc[FRAP_C], fpt_t x[FRAP_C], fpt_t h[FRAP_C]) {
+    const FrapOff o(D);
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) { lc[c] = fpt_relu(Ag[c] + Bj[c]); x[c] = lc[c] * Rc[c]; }
+    FrapDot y(w[o.bmb]);
+#pragma unroll
+    for (int k = 0; k < FRAP_C; ++k) {
+        FPT_UNIT(w)
+        FrapDot a(w[o.hb + k]);
+#pragma unroll
+        for (int c = 0; c < FRAP_C; ++c) a.fma(w[o.h + k * FRAP_C + c], x[c]);
+        h[k] = fpt_relu(a.get());
+        y.fma(w[o.bm + k], h[k]);
+    }
+    return y.get();
+}
+// its backward from dy: dh = dy BM (h > 0), dx = H^T dh, drit = dx lc (the item's share of dR), dpx = dx R (lc > 0)
+template <class WP>
+RS_HD inline void frap_item_backward(WP w, int D, fpt_t dy, const fpt_t lc[FRAP_C], const fpt_t *Rc, const fpt_t *h, fpt_t dh[FRAP_C], fpt_t drit[FRAP_C],
+                                     fpt_t dpx[FRAP_C]) {
+    const FrapOff o(D);
+#pragma unroll
+    for (int k = 0; k < FRAP_C; ++k) dh[k] = h[k] > 0.0 ? dy * w[o.bm + k] : 0.0;
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) {
+        FPT_UNIT(w)
+        FrapDot a(0.0);
+#pragma unroll
+        for (int k = 0; k < FRAP_C; ++k) a.fma(w[o.h + k * FRAP_C + c], dh[k]);
+        const fpt_t dx = a.get();
+        drit[c] = dx * lc[c];
+        dpx[c] = lc[c] > 0.0 ? dx * Rc[c] : 0.0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ a tile's stage and its phases
+// The LDS image of a tile (the host build: a plain struct).  A phase is a function of (row r, lane j) that reads what earlier phases
+// left and writes its own lane's part; the kernel puts a barrier between two phases, the host build runs the lanes one after the
+// other.  Rows past the minibatch (ok = 0), lanes past P and the lane j = g hold zeros wherever an entry reads them.
+struct FrapStage {
+    fpt_t PE[2][32], R[2][2 * FRAP_C];                  // the derived tables (frap_prep_once): [0] of the parameters, [1] of the target
+    float obs[FPT_TM][FPT_W], nxt[FPT_TM][FPT_W];       // the rows and their successors (zeros where not read)
+    fpt_t rew[FPT_TM], tgt[FPT_TM], dy[FPT_TM], term[FPT_TM];
+    int32_t ok[FPT_TM], boot[FPT_TM], g[FPT_TM];        // row inside the minibatch; successor read (not done); the action
+    int32_t bit[FPT_TM][FRAP_MV];
+    fpt_t sd[FPT_TM][FRAP_MV][FPT_QS], e[FPT_TM][FRAP_MV][FPT_ES], dz[FPT_TM][FRAP_MV][FPT_QS];      // e: later dpre
+    fpt_t pair[FPT_TM][FPT_G][FPT_ES], dpair[FPT_TM][FPT_G][FPT_ES];
+    fpt_t A[FPT_TM][FRAP_C], dA[FPT_TM][FRAP_C];        // of pair g
+    fpt_t x[FPT_TM][FPT_G][FPT_CS], h[FPT_TM][FPT_G][FPT_CS];           // (the target pass: A_j and B_j of the successor row)
+    fpt_t dh[FPT_TM][FPT_G][FPT_CS], drit[FPT_TM][FPT_G][FPT_CS];       // drit: lc until the item's backward
+    fpt_t dpx[FPT_TM][FPT_G][FPT_CS];                   // B_j until the item's backward
+    fpt_t y[FPT_TM][FPT_G];                             // y_gj (the target pass: Q_j of the successor row)
+    int32_t comp[FPT_TM][FPT_G];
+};
+
+RS_HD inline int frap_phase_of(float o0, int P) {
+    const int ph = (int)o0;
+    return ph < 0 ? 0 : (ph >= P ? P - 1 : ph);
+}
+
+// the derived tables, value k < 144 of the stage
+RS_HD inline void fpt_prep(FrapStage &L, const float *w, const float *wt, int D, int k) {
+    const int net = k / 72, kk = k - net * 72;
+    const fpt_t v = frap_prep_once(net ? wt : w, D, kk);
+    if (kk < 32) L.PE[net][kk] = v;
+    else L.R[net][kk - 32] = v;
+}
+
+// ---- the target: lane (r, j < P) A_j, B_j of the successor row under the target network
+template <class WP>
+RS_HD inline void fpt_target_ab(FrapStage &L, WP wt, int D, int P, const int32_t *pairs, int r, int j) {
+    if (!L.boot[r] || j >= P) return;
+    const float *ob = L.nxt[r];
+    const int ph = frap_phase_of(ob[0], P), p0 = pairs[2 * ph], p1 = pairs[2 * ph + 1];
+    fpt_t pr[FRAP_E], A[FRAP_C], B[FRAP_C];
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) pr[u] = 0.0;
+    for (int side = 0; side < 2; ++side) {
+        const int m = pairs[2 * j + side];
+        fpt_t sd[4], e[FRAP_E];
+        frap_mv_forward(wt, D, L.PE[1], m, m == p0 || m == p1, [&](int mv, int v) { return ob[1 + mv + v]; }, sd, e);
+#pragma unroll
+        for (int u = 0; u < FRAP_E; ++u) pr[u] += e[u];
+    }
+    frap_pair_ab(wt, D, pr, A, B);
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) { L.x[r][j][c] = A[c]; L.h[r][j][c] = B[c]; }
+}
+// lane (r, i < P): Q_i = sum_{j != i} y_ij, j ascending
+template <class WP>
+RS_HD inline void fpt_target_q(FrapStage &L, WP wt, int D, int P, const int32_t *pairs, int r, int i) {
+    if (!L.boot[r] || i >= P) return;
+    fpt_t q = 0.0;
+    for (int j = 0; j < P; ++j) {
+        if (j == i) continue;
+        fpt_t lc[FRAP_C], x[FRAP_C], h[FRAP_C];
+        q += frap_item_forward(wt, D, L.x[r][i], L.h[r][j], L.R[1] + FRAP_C * frap_comp(pairs, i, j), lc, x, h);
+    }
+    L.y[r][i] = q;
+}
+// lane (r, 0): tgt = rew + gamma max_i Q_i, or rew where the episode ended
+RS_HD inline void fpt_target_value(FrapStage &L, int P, double gamma, int r) {
+    fpt_t t = L.rew[r];
+    if (L.boot[r]) {
+        fpt_t mx = L.y[r][0];
+        for (int i = 1; i < P; ++i) mx = L.y[r][i] > mx ? L.y[r][i] : mx;
+        t = t + gamma * mx;
+    }
+    L.tgt[r] = t;
+}
+
+// ---- the parameters' forward with saved activations.  Lane (r, m < 12): movement m
+template <class WP>
+RS_HD inline void fpt_mv_forward(FrapStage &L, WP w, int D, int P, const int32_t *pairs, int r, int m) {
+    fpt_t sd[4] = {0.0, 0.0, 0.0, 0.0}, e[FRAP_E];
+    int bit = 0;
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) e[u] = 0.0;
+    if (L.ok[r]) {
+        const float *ob = L.obs[r];
+        const int ph = frap_phase_of(ob[0], P);
+        bit = m == pairs[2 * ph] || m == pairs[2 * ph + 1];
+        frap_mv_forward(w, D, L.PE[0], m, bit, [&](int mv, int v) { return ob[1 + mv + v]; }, sd, e);
+    }
+    L.bit[r][m] = bit;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { L.sd[r][m][t] = sd[t]; L.dz[r][m][t] = 0.0; }
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) L.e[r][m][u] = e[u];
+}
+// lane (r, j < P): pair_j, B_j (into dpx) and, on lane g, A_g
+template <class WP>
+RS_HD inline void fpt_pair_forward(FrapStage &L, WP w, int D, int P, const int32_t *pairs, int r, int j) {
+    if (j >= P) return;
+    const int a = pairs[2 * j], b = pairs[2 * j + 1];
+    fpt_t pr[FRAP_E], A[FRAP_C], B[FRAP_C];
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) pr[u] = L.e[r][a][u] + L.e[r][b][u];
+    frap_pair_ab(w, D, pr, A, B);
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) { L.pair[r][j][u] = pr[u]; L.dpair[r][j][u] = 0.0; }
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) L.dpx[r][j][c] = B[c];
+    if (j == L.g[r]) {
+#pragma unroll
+        for (int c = 0; c < FRAP_C; ++c) L.A[r][c] = A[c];
+    }
+}
+// lane (r, j < P): the item (g, j)
+template <class WP>
+RS_HD inline void fpt_item_forward(FrapStage &L, WP w, int D, int P, const int32_t *pairs, int r, int j) {
+    if (j >= P) return;
+    const int g = L.g[r];
+    fpt_t lc[FRAP_C], x[FRAP_C], h[FRAP_C], y = 0.0;
+    int comp = 0;
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) lc[c] = x[c] = h[c] = 0.0;
+    if (L.ok[r] && j != g) {
+        comp = frap_comp(pairs, g, j);
+        y = frap_item_forward(w, D, L.A[r], L.dpx[r][j], L.R[0] + FRAP_C * comp, lc, x, h);
+    }
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) { L.drit[r][j][c] = lc[c]; L.x[r][j][c] = x[c]; L.h[r][j][c] = h[c]; }
+    L.y[r][j] = y;
+    L.comp[r][j] = comp;
+}
+// lane (r, 0): delta = y - tgt with y = sum_{j != g} y_gj (j ascending); the Huber term and dy = d loss / d y under the mean over
+// `batch` rows: dqn_row_loss_grad's arithmetic (resco_dqn_train.h) in double
+RS_HD inline void fpt_row_loss(FrapStage &L, int P, int batch, int r) {
+    L.dy[r] = 0.0; L.term[r] = 0.0;
+    if (!L.ok[r]) return;
+    const int g = L.g[r];
+    fpt_t y = 0.0;
+    for (int j = 0; j < P; ++j)
+        if (j != g) y += L.y[r][j];
+    const fpt_t delta = y - L.tgt[r], ad = fabs(delta);
+    L.dy[r] = (delta < -1.0 ? -1.0 : (delta > 1.0 ? 1.0 : delta)) / (fpt_t)batch;
+    L.term[r] = ad < 1.0 ? 0.5 * delta * delta : ad - 0.5;
+}
+// lane (r, j < P): the item's backward; dpair_j = LC[:, 16:]^T dpx
+template <class WP>
+RS_HD inline void fpt_item_backward(FrapStage &L, WP w, int D, int P, int r, int j) {
+    if (j >= P) return;
+    fpt_t dh[FRAP_C], drit[FRAP_C], dpx[FRAP_C], dpair[FRAP_E];
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) dh[c] = drit[c] = dpx[c] = 0.0;
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) dpair[u] = 0.0;
+    if (L.ok[r] && j != L.g[r]) {
+        fpt_t lc[FRAP_C];
+#pragma unroll
+        for (int c = 0; c < FRAP_C; ++c) lc[c] = L.drit[r][j][c];
+        frap_item_backward(w, D, L.dy[r], lc, L.R[0] + FRAP_C * L.comp[r][j], L.h[r][j], dh, drit, dpx);
+        frap_pair_backward(w, D, 1, dpx, dpair);
+    }
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) { L.dh[r][j][c] = dh[c]; L.drit[r][j][c] = drit[c]; L.dpx[r][j][c] = dpx[c]; }
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) L.dpair[r][j][u] = dpair[u];
+}
+// lane (r, g): dA_g = sum_{j != g} dpx_j (j ascending), dpair_g = LC[:, :16]^T dA_g
+template <class WP>
+RS_HD inline void fpt_row_backward(FrapStage &L, WP w, int D, int P, int r) {
+    const int g = L.g[r];
+    fpt_t dA[FRAP_C], dpair[FRAP_E];
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) {
+        FrapDot a(0.0);
+        for (int j = 0; j < P; ++j)
+            if (j != g) a.add(L.dpx[r][j][c]);
+        dA[c] = a.get();
+    }
+    frap_pair_backward(w, D, 0, dA, dpair);
+#pragma unroll
+    for (int c = 0; c < FRAP_C; ++c) L.dA[r][c] = dA[c];
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) L.dpair[r][g][u] = dpair[u];
+}
+// lane (r, m < 12): de_m = the dpair of every pair that names m (twice where it names it twice), then the movement's backward
+template <class WP>
+RS_HD inline void fpt_mv_backward(FrapStage &L, WP w, int D, int P, const int32_t *pairs, int r, int m) {
+    fpt_t de[FRAP_E], e[FRAP_E], sd[4], dpre[FRAP_E], dz[4];
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) { de[u] = 0.0; e[u] = L.e[r][m][u]; }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) sd[t] = L.sd[r][m][t];
+    for (int i = 0; i < 2 * P; ++i) {
+        if (pairs[i] != m) continue;
+#pragma unroll
+        for (int u = 0; u < FRAP_E; ++u) de[u] += L.dpair[r][i >> 1][u];
+    }
+    frap_mv_backward(w, D, de, e, sd, dpre, dz);
+#pragma unroll
+    for (int u = 0; u < FRAP_E; ++u) L.e[r][m][u] = dpre[u];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) L.dz[r][m][t] = dz[t];
+}
+
+// entry e of the tile: rows ascending, inside a row the items j or the movements m ascending
+RS_HD inline fpt_t frap_tile_entry(const FrapStage &L, int P, int D, int e) {
+    FrapDot a(0.0);
+    if (e < FG_HB) {
+        const int k = (e - FG_H) / FRAP_C, c = (e - FG_H) - k * FRAP_C;
+        for (int r = 0; r < FPT_TM; ++r)
+            for (int j = 0; j < P; ++j) a.fma(L.dh[r][j][k], L.x[r][j][c]);
+    } else if (e < FG_BM) {
+        for (int r = 0; r < FPT_TM; ++r)
+            for (int j = 0; j < P; ++j) a.add(L.dh[r][j][e - FG_HB]);
+    } else if (e < FG_BMB) {
+        for (int r = 0; r < FPT_TM; ++r)
+            for (int j = 0; j < P; ++j) a.fma(L.dy[r], L.h[r][j][e - FG_BM]);
+    } else if (e < FG_LCB) {
+        for (int r = 0; r < FPT_TM; ++r) a.fma(L.dy[r], (fpt_t)(P - 1));
+    } else if (e < FG_LC) {
+        for (int r = 0; r < FPT_TM; ++r)
+            for (int j = 0; j < P; ++j) a.add(L.dpx[r][j][e - FG_LCB]);
+    } else if (e < FG_DR) {
+        const int c = (e - FG_LC) >> 5, q = (e - FG_LC) & 31;
+        if (q < 16) {
+            for (int r = 0; r < FPT_TM; ++r) a.fma(L.dA[r][c], L.pair[r][L.g[r]][q]);
+        } else {
+            for (int r = 0; r < FPT_TM; ++r)
+                for (int j = 0; j < P; ++j) a.fma(L.dpx[r][j][c], L.pair[r][j][q - 16]);
+        }
+    } else if (e < FG_PE) {
+        const int comp = (e - FG_DR) / FRAP_C, c = (e - FG_DR) - comp * FRAP_C;
+        for (int r = 0; r < FPT_TM; ++r)
+            for (int j = 0; j < P; ++j)
+                if (L.comp[r][j] == comp) a.add(L.drit[r][j][c]);
+    } else if (e < FG_LE) {
+        const int bit = (e - FG_PE) >> 4, u = (e - FG_PE) & 15;
+        for (int r = 0; r < FPT_TM; ++r)
+            for (int m = 0; m < FRAP_MV; ++m)
+                if (L.bit[r][m] == bit) a.add(L.e[r][m][u]);
+    } else if (e < FG_DB) {
+        const int u = (e - FG_LE) >> 2, t = (e - FG_LE) & 3;
+        for (int r = 0; r < FPT_TM; ++r)
+            for (int m = 0; m < FRAP_MV; ++m) a.fma(L.e[r][m][u], L.sd[r][m][t]);
+    } else if (e < FG_DW) {
+        for (int r = 0; r < FPT_TM; ++r)
+            for (int m = 0; m < FRAP_MV; ++m) a.add(L.dz[r][m][e - FG_DB]);
+    } else if (e < FG_LOSS) {
+        if (e - FG_DW < 4 * D) {
+            const int t = (e - FG_DW) / D, v = (e - FG_DW) - t * D;
+            for (int r = 0; r < FPT_TM; ++r)
+                for (int m = 0; m < FRAP_MV; ++m) a.fma(L.dz[r][m][t], L.obs[r][1 + m + v]);
+        }
+    } else {
+        for (int r = 0; r < FPT_TM; ++r) a.add(L.term[r]);
+    }
+    return a.get();
+}
+
+// ------------------------------------------------------------------------------------------------ partials -> gradients
+// the workspace: part [tile][FG_N].  Entry e over the tiles in ascending order
+RS_HD inline fpt_t frap_reduce_entry(const fpt_t *part, int tiles, int e) {
+    fpt_t a = 0.0;
+    for (int t = 0; t < tiles; ++t) a += part[(size_t)t * FG_N + e];
+    return a;
+}
+
+// Element i of the packed gradient, rounded to fp32 here.  gPE [32], gR [40]: the reduced FG_PE and FG_DR entries.  The chains,
+// applied once:
+//   PE[bit][u] = LE_b[u] + sum_t LE[u][t] sigmoid(p[bit][t])           -> lane_embedding.bias, lane_embedding.weight[:, :4], p.weight
+//   R[comp][c] = relu(RC_b[c] + sum_t RC[c][t] relu(RE[comp][t]))      -> relation_conv.bias, relation_conv.weight, relation_embedding.weight
+RS_HD inline float frap_grad_element(const float *w, int D, int i, const fpt_t *part, int tiles, const fpt_t *gPE, const fpt_t *gR) {
+    const FrapOff o(D);
+    FrapDot a(0.0);
+    int entry = -1;
+    if (i < o.dw) {                                     // p.weight [bit][t]
+        const int bit = i >> 2, t = i & 3;
+        const fpt_t s = frap_sigmoid_once(w[o.p + i]);
+        for (int u = 0; u < FRAP_E; ++u) a.fma(gPE[bit * 16 + u], w[o.le + u * 8 + t]);
+        return (float)(a.get() * (s * (1.0 - s)));
+    } else if (i < o.db) entry = FG_DW + (i - o.dw);
+    else if (i < o.le) entry = FG_DB + (i - o.db);
+    else if (i < o.leb) {                               // lane_embedding.weight [u][q]
+        const int u = (i - o.le) >> 3, q = (i - o.le) & 7;
+        if (q >= 4) entry = FG_LE + u * 4 + (q - 4);
+        else {
+            for (int bit = 0; bit < 2; ++bit) a.fma(gPE[bit * 16 + u], frap_sigmoid_once(w[o.p + bit * 4 + q]));
+            return (float)a.get();
+        }
+    } else if (i < o.lc) return (float)(gPE[i - o.leb] + gPE[16 + i - o.leb]);       // lane_embedding.bias [u]
+    else if (i < o.lcb) entry = FG_LC + (i - o.lc);
+    else if (i < o.re) entry = FG_LCB + (i - o.lcb);
+    else if (i < o.h) {                                 // the relation branch: d loss / d (pre-activation of R[comp][c]) = gR where R > 0
+        if (i < o.rc) {                                 // relation_embedding.weight [comp][t]
+            const int comp = (i - o.re) >> 2, t = (i - o.re) & 3;
+            if (!(w[i] > 0.0)) return 0.0;
+            for (int c = 0; c < FRAP_C; ++c)
+                if (frap_prep_once(w, D, 32 + comp * FRAP_C + c) > 0.0) a.fma(gR[comp * FRAP_C + c], w[o.rc + c * 4 + t]);
+        } else {
+            const bool bias = i >= o.rcb;
+            const int c = bias ? i - o.rcb : (i - o.rc) >> 2, t = bias ? 0 : (i - o.rc) & 3;
+            for (int comp = 0; comp < 2; ++comp)
+                if (frap_prep_once(w, D, 32 + comp * FRAP_C + c) > 0.0) a.fma(gR[comp * FRAP_C + c], bias ? 1.0 : fpt_relu(w[o.re + comp * 4 + t]));
+        }
+        return (float)a.get();
+    } else if (i < o.hb) entry = FG_H + (i - o.h);
+    else if (i < o.bm) entry = FG_HB + (i - o.hb);
+    else if (i < o.bmb) entry = FG_BM + (i - o.bm);
+    else entry = FG_BMB;
+    return (float)frap_reduce_entry(part, tiles, entry);
+}
+// the mean loss of the minibatch
+RS_HD inline float frap_loss_mean(const fpt_t *part, int tiles, int B) {
+    return (float)(frap_reduce_entry(part, tiles, FG_LOSS) / (fpt_t)B);
+}
+
+#if defined(__HIPCC__)      // ------------------------------------------------------------------------------------------ the kernels
+struct FrapTrainTab {
+    float *par, *grad, *m, *v;              // the caller's flat vectors (packed layout, n floats); par, m, v updated in place
+    const float *tgt;                       // the target network, only read
+    const int32_t *pairs;                   // device [P][2]
+    int32_t P, D, S, n;                     // n = 1365 + 4 D
+    int32_t tiles_max;
+    double gamma;
+    fpt_t *part;                            // [tiles_max][FG_N]
+};
+
+struct FrapBatch {
+    const float *obs;                       // the ring: [T][N][S][W]
+    const int16_t *act;                     // [T][N][S]
+    const float *rew;                       // [T][N][S]
+    const uint8_t *done;                    // [T]
+    int32_t T, N, S, W;
+    const int32_t *idx;                     // [B][3]: (t, e, s)
+    int32_t B;
+};
+
+__global__ void __launch_bounds__(256) frap_dqn_sample_kernel(uint32_t seed, uint32_t u, int T, int N, int S, int head, int count, int B, int32_t *idx) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < B) frap_dqn_sample_index(seed, u, (uint32_t)i, T, N, S, head, count, idx + (size_t)i * 3);
+}
+
+__global__ void __launch_bounds__(FPT_T) frap_dqn_tile_kernel(FrapTrainTab T, FrapBatch D) {
+    __shared__ FrapStage L;
+    const int tid = threadIdx.x, r = tid / FPT_G, j = tid % FPT_G, row = blockIdx.x * FPT_TM + r;
+    const int P = T.P, Dm = T.D;
+    // wave-uniform reads of the weights, one output unit at a time (FPT_UNIT)
+    const float *w = T.par, *wt = T.tgt;
+    for (int k = tid; k < 144; k += FPT_T) fpt_prep(L, T.par, T.tgt, Dm, k);
+    {   // the row and its successor, held inside the ring whatever idx says; an episode end cuts the bootstrap: nothing is read
+        const bool ok = row < D.B;
+        int t = 0, e = 0, s = 0;
+        if (ok) {
+            const int32_t *p = D.idx + (size_t)row * 3;
+            t = min(max(p[0], 0), D.T - 1); e = min(max(p[1], 0), D.N - 1); s = min(max(p[2], 0), D.S - 1);
+        }
+        const bool boot = ok && !D.done[t];
+        const size_t cur = ((size_t)t * D.N + e) * D.S + s, nxt = ((size_t)(t + 1 == D.T ? 0 : t + 1) * D.N + e) * D.S + s;
+        for (int q = j; q < FPT_W; q += FPT_G) {
+            L.obs[r][q] = ok && q < D.W ? D.obs[cur * D.W + q] : 0.0f;
+            L.nxt[r][q] = boot && q < D.W ? D.obs[nxt * D.W + q] : 0.0f;
+        }
+        if (j == 0) {
+            const int a = ok ? (int)D.act[cur] : 0;
+            L.ok[r] = ok; L.boot[r] = boot;
+            L.g[r] = a < 0 ? 0 : (a >= P ? P - 1 : a);
+            L.rew[r] = ok ? D.rew[cur] : 0.0f;
+        }
+    }
+    __syncthreads();
+    fpt_target_ab(L, wt, Dm, P, T.pairs, r, j);
+    __syncthreads();
+    fpt_target_q(L, wt, Dm, P, T.pairs, r, j);
+    __syncthreads();
+    if (j == 0) fpt_target_value(L, P, T.gamma, r);
+    if (j < FRAP_MV) fpt_mv_forward(L, w, Dm, P, T.pairs, r, j);
+    __syncthreads();
+    fpt_pair_forward(L, w, Dm, P, T.pairs, r, j);
+    __syncthreads();
+    fpt_item_forward(L, w, Dm, P, T.pairs, r, j);
+    __syncthreads();
+    if (j == 0) fpt_row_loss(L, P, D.B, r);
+    __syncthreads();
+    fpt_item_backward(L, w, Dm, P, r, j);
+    __syncthreads();
+    if (j == L.g[r]) fpt_row_backward(L, w, Dm, P, r);
+    __syncthreads();
+    if (j < FRAP_MV) fpt_mv_backward(L, w, Dm, P, T.pairs, r, j);
+    __syncthreads();
+    fpt_t *part = T.part + (size_t)blockIdx.x * FG_N;
+    for (int e = tid; e < FG_N; e += FPT_T) part[e] = frap_tile_entry(L, P, Dm, e);
+}
+
+// grid ceil(n / 256): every workgroup reduces the 72 chain entries for itself, then a thread its own element of the gradient
+__global__ void __launch_bounds__(256) frap_dqn_reduce_kernel(FrapTrainTab T, int B, float *loss_out) {
+    __shared__ fpt_t gPE[32], gR[2 * FRAP_C];
+    const int tid = threadIdx.x, tiles = (B + FPT_TM - 1) / FPT_TM;
+    if (tid < 32) gPE[tid] = frap_reduce_entry(T.part, tiles, FG_PE + tid);
+    else if (tid < 72) gR[tid - 32] = frap_reduce_entry(T.part, tiles, FG_DR + tid - 32);
+    __syncthreads();
+    const int i = blockIdx.x * 256 + tid;
+    if (i < T.n) T.grad[i] = frap_grad_element(T.par, T.D, i, T.part, tiles, gPE, gR);
+    if (loss_out && i == 0) *loss_out = frap_loss_mean(T.part, tiles, B);
+}
+
+__global__ void __launch_bounds__(256) frap_dqn_adam_kernel(FrapTrainTab T, PpoStepConsts K) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < T.n) ppo_adam_element(&T.par[i], &T.m[i], &T.v[i], T.grad[i], PpoPair{1.0f, 0.0f}, K);
+}
+#endif

@@ -113,6 +113,7 @@ __device__ unsigned long long *g_sec_prof;
 #include "resco_ppo.h"
 #include "resco_ppo_train.h"
 #include "resco_dqn_train.h"
+#include "resco_frap_train.h"
 
 // ------------------------------------------------------------------------------------------------ kernels
 // The tables / state / output descriptors live in ONE constant block in device memory (StepArgs): passed by value they
@@ -1143,6 +1144,136 @@ extern "C" int rs_mplight_set_device_weights(rs_policy_handle p, const float *we
     p->F.w = weights;
     return RS_OK;
 }
+
+// ---- MPLight: the shared-DQN update (resco_frap_train.h), five flat vectors and the caller's ring; the library owns the per-tile
+// partials, the pair table and the index array of rs_mplight_dqn_update
+struct rs_mplight_dqn : TrainHandle {
+    FrapTrainTab T{};
+    rs_dqn_config cfg{};
+    int32_t *idx = nullptr;     // [max_batch][3]: the minibatch rs_mplight_dqn_update draws
+    const void *ring_ok[4] = {nullptr, nullptr, nullptr, nullptr};     // the ring arrays last found on this handle's device
+};
+
+extern "C" void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p) { train_destroy(p); }
+
+extern "C" int rs_mplight_dqn_create(int32_t device_id, int32_t demand_shape, int32_t n_pairs, const int32_t *pairs, int32_t n_signals,
+                                     const rs_dqn_config *cfg, float *params, const float *target, float *grads, float *m, float *v, int32_t max_batch,
+                                     rs_mplight_dqn_handle *out) {
+    if (!out) return RS_EINVAL;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_err = "no HIP device visible (this library has no CPU fallback)"; return RS_EHIP; }
+    if (device_id < 0 || device_id >= ndev || (demand_shape != 1 && demand_shape != 4) || n_pairs < 2 || n_pairs > FRAP_PMAX || n_signals < 1 || !pairs ||
+        !cfg || max_batch < 1) {
+        g_create_err = "rs_mplight_dqn_create: bad argument (a visible device, demand_shape 1 or 4, 2 <= n_pairs <= 16, 1 <= n_signals, 1 <= max_batch)";
+        return RS_EINVAL;
+    }
+    if (!params || !target || !grads || !m || !v) { g_create_err = "rs_mplight_dqn_create: a vector pointer is NULL"; return RS_EINVAL; }
+    for (int i = 0; i < 2 * n_pairs; ++i)
+        if (pairs[i] < 0 || pairs[i] >= FRAP_MV) { g_create_err = "rs_mplight_dqn_create: a phase pair names a movement outside 0..11"; return RS_EINVAL; }
+    if (hipSetDevice(device_id) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RS_EHIP; }
+    rs_mplight_dqn *p = new (std::nothrow) rs_mplight_dqn();
+    if (!p) return RS_ENOMEM;
+    p->device = device_id; p->max_batch = max_batch; p->cfg = *cfg;
+    FrapTrainTab &T = p->T;
+    T.par = params; T.tgt = target; T.grad = grads; T.m = m; T.v = v;
+    T.P = n_pairs; T.D = demand_shape; T.S = n_signals; T.n = FrapOff(demand_shape).n;
+    T.tiles_max = (max_batch + FPT_TM - 1) / FPT_TM;
+    T.gamma = cfg->gamma;
+    void *d_pairs = nullptr;
+    if (!p->alloc(&d_pairs, (size_t)n_pairs * 2 * 4) || !p->alloc((void **)&T.part, (size_t)T.tiles_max * FG_N * sizeof(fpt_t)) ||
+        !p->alloc((void **)&p->idx, (size_t)max_batch * 3 * sizeof(int32_t)) ||
+        hipMemcpy(d_pairs, pairs, (size_t)n_pairs * 2 * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        g_create_err = "rs_mplight_dqn_create: device allocation / upload failed";
+        (void)hipGetLastError();
+        train_destroy(p);
+        return RS_ENOMEM;
+    }
+    T.pairs = (const int32_t *)d_pairs;
+    *out = p;
+    return RS_OK;
+}
+
+// what every call that reads the ring checks before it launches anything; `name` goes into the message
+static int mplight_dqn_check(rs_mplight_dqn *p, const rs_mplight_ring *r, int32_t batch, const char *name) {
+    auto refuse = [&](const char *why) { g_create_err = std::string(name) + ": " + why; return RS_EINVAL; };
+    if (!p) return refuse("NULL handle");
+    if (!r || !r->obs || !r->act || !r->rew || !r->done) return refuse("a ring pointer is NULL");
+    if (batch < 1 || batch > p->max_batch) return refuse("need 1 <= batch <= max_batch of rs_mplight_dqn_create");
+    if (r->capacity < 2 || r->n_envs < 1) return refuse("the ring needs capacity >= 2 and n_envs >= 1");
+    if (r->n_signals != p->T.S) return refuse("the ring's n_signals is not the handle's");
+    if (r->width != 1 + FRAP_MV * p->T.D) return refuse("the ring's width is not the handle's 1 + 12 demand_shape");
+    if (r->count < 2) return refuse("the ring needs count >= 2: a transition is a slot and its written successor");
+    if (r->count > r->capacity || r->head < 0 || r->head >= r->capacity) return refuse("head or count outside the ring");
+    const void *ring[4] = {r->obs, r->act, r->rew, r->done};      // asked of the runtime once per ring: a ring keeps its storages
+    if (memcmp(ring, p->ring_ok, sizeof(ring)) != 0) {
+        for (const void *a : ring)
+            if (!dqn_on_device(a, p->device)) return refuse("a ring array is not device memory of this handle's device (another device, or host memory)");
+        memcpy(p->ring_ok, ring, sizeof(ring));
+    }
+    return RS_OK;
+}
+static FrapBatch mplight_dqn_batch(const rs_mplight_ring *r, const int32_t *idx, int32_t B) {
+    return FrapBatch{r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, r->n_signals, r->width, idx, B};
+}
+
+// the launches; the arguments have been checked
+static void mplight_dqn_sample_launch(const rs_mplight_ring *r, int B, uint32_t seed, uint32_t key, int32_t *idx, hipStream_t st) {
+    hipLaunchKernelGGL(frap_dqn_sample_kernel, dim3((B + 255) / 256), dim3(256), 0, st, seed, key, r->capacity, r->n_envs, r->n_signals, r->head, r->count, B,
+                       idx);
+}
+static void mplight_dqn_grad_launch(const rs_mplight_dqn *p, const FrapBatch &D, float *loss_out, hipStream_t st) {
+    const FrapTrainTab &T = p->T;
+    hipLaunchKernelGGL(frap_dqn_tile_kernel, dim3((D.B + FPT_TM - 1) / FPT_TM), dim3(FPT_T), 0, st, T, D);
+    hipLaunchKernelGGL(frap_dqn_reduce_kernel, dim3((T.n + 255) / 256), dim3(256), 0, st, T, D.B, loss_out);
+}
+static void mplight_dqn_step_launch(rs_mplight_dqn *p, hipStream_t st) {
+    const PpoStepConsts K = ppo_step_consts(p->cfg.lr, p->cfg.adam_eps, p->cfg.beta1, p->cfg.beta2, 0.0, p->t + 1);
+    hipLaunchKernelGGL(frap_dqn_adam_kernel, dim3((p->T.n + 255) / 256), dim3(256), 0, st, p->T, K);
+    if (hipPeekAtLastError() == hipSuccess) p->t += 1;      // a step that could not be launched is not counted
+}
+
+extern "C" int rs_mplight_dqn_sample(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key,
+                                     int32_t *idx_out, void *stream) {
+    if (int rc = mplight_dqn_check(p, ring, batch, "rs_mplight_dqn_sample")) return rc;
+    if (!idx_out) { g_create_err = "rs_mplight_dqn_sample: idx_out is NULL"; return RS_EINVAL; }
+    if (!dqn_on_device(idx_out, p->device)) { g_create_err = "rs_mplight_dqn_sample: idx_out is not device memory of this handle's device"; return RS_EINVAL; }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    mplight_dqn_sample_launch(ring, batch, seed, update_key, idx_out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_mplight_dqn_grad(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, const int32_t *idx, int32_t batch, float *loss_out, void *stream) {
+    if (int rc = mplight_dqn_check(p, ring, batch, "rs_mplight_dqn_grad")) return rc;
+    if (!idx) { g_create_err = "rs_mplight_dqn_grad: idx is NULL"; return RS_EINVAL; }
+    if (!dqn_on_device(idx, p->device)) { g_create_err = "rs_mplight_dqn_grad: idx is not device memory of this handle's device"; return RS_EINVAL; }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    mplight_dqn_grad_launch(p, mplight_dqn_batch(ring, idx, batch), loss_out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_mplight_dqn_step(rs_mplight_dqn_handle p, void *stream) {
+    if (!p) { g_create_err = "rs_mplight_dqn_step: NULL handle"; return RS_EINVAL; }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    mplight_dqn_step_launch(p, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_mplight_dqn_update(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out,
+                                     void *stream) {
+    if (int rc = mplight_dqn_check(p, ring, batch, "rs_mplight_dqn_update")) return rc;
+    if (n_updates < 1) { g_create_err = "rs_mplight_dqn_update: need 1 <= n_updates"; return RS_EINVAL; }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    for (int j = 0; j < n_updates; ++j) {       // the launches of a stream run in order: update j + 1 may overwrite idx and the workspace
+        mplight_dqn_sample_launch(ring, batch, seed, (uint32_t)p->t, p->idx, (hipStream_t)stream);
+        mplight_dqn_grad_launch(p, mplight_dqn_batch(ring, p->idx, batch), loss_out, (hipStream_t)stream);
+        mplight_dqn_step_launch(p, (hipStream_t)stream);
+        if (hipPeekAtLastError() != hipSuccess) break;      // nothing more is enqueued behind a launch that failed
+    }
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int64_t rs_mplight_dqn_steps(rs_mplight_dqn_handle p) { return p ? (int64_t)p->t : -1; }
 
 // ---- one env-step (or n of them) of a whole group of handles in ONE call (include/resco_sim.h: rs_group_step)
 extern "C" int rs_group_step(const rs_handle *hs, int32_t n_handles, const rs_group_agent *agent, int32_t n_steps) {

@@ -35,7 +35,9 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_default_block', 'rs_mplight_create', 'rs_mplight_act', 'rs_mplight_set_device_weights', 'rs_mplight_destroy',
                'rs_ippo_act', 'rs_group_rollout', 'rs_ppo_gae',
                'rs_ppo_create', 'rs_ppo_grad', 'rs_ppo_step', 'rs_ppo_fit', 'rs_ppo_steps', 'rs_ppo_destroy',
-               'rs_dqn_create', 'rs_dqn_sample', 'rs_dqn_grad', 'rs_dqn_step', 'rs_dqn_update', 'rs_dqn_steps', 'rs_dqn_destroy']
+               'rs_dqn_create', 'rs_dqn_sample', 'rs_dqn_grad', 'rs_dqn_step', 'rs_dqn_update', 'rs_dqn_steps', 'rs_dqn_destroy',
+               'rs_mplight_dqn_create', 'rs_mplight_dqn_sample', 'rs_mplight_dqn_grad', 'rs_mplight_dqn_step', 'rs_mplight_dqn_update',
+               'rs_mplight_dqn_steps', 'rs_mplight_dqn_destroy']
 
 _lib = None
 
@@ -106,6 +108,16 @@ def bind(L):
         L.rs_dqn_steps.restype = C.c_int64
         L.rs_dqn_destroy.argtypes = [vp]
         L.rs_dqn_destroy.restype = None
+    if hasattr(L, 'rs_mplight_dqn_create'):
+        L.rs_mplight_dqn_create.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)]
+        L.rs_mplight_dqn_sample.argtypes = [vp, vp, i32, u32, u32, vp, vp]
+        L.rs_mplight_dqn_grad.argtypes = [vp, vp, vp, i32, vp, vp]
+        L.rs_mplight_dqn_step.argtypes = [vp, vp]
+        L.rs_mplight_dqn_update.argtypes = [vp, vp, i32, u32, i32, vp, vp]
+        L.rs_mplight_dqn_steps.argtypes = [vp]
+        L.rs_mplight_dqn_steps.restype = C.c_int64
+        L.rs_mplight_dqn_destroy.argtypes = [vp]
+        L.rs_mplight_dqn_destroy.restype = None
     if hasattr(L, 'rs_default_block'):      # (the host emulation of the CPU tests exports only what it implements)
         L.rs_default_block.argtypes = [i32, i32, i32]
         L.rs_default_block.restype = i32
@@ -175,6 +187,12 @@ class DQNConfig(C.Structure):
 class DQNRing(C.Structure):
     """ctypes mirror of rs_dqn_ring (include/resco_sim.h): the device arrays of a DeviceReplay and its position"""
     _fields_ = [(k, C.c_void_p) for k in ('obs', 'act', 'rew', 'done')] + [(k, C.c_int32) for k in ('capacity', 'n_envs', 'head', 'count')]
+
+
+class MPLightRing(C.Structure):
+    """ctypes mirror of rs_mplight_ring (include/resco_sim.h): the device arrays of an MPLightReplay and its position"""
+    _fields_ = [(k, C.c_void_p) for k in ('obs', 'act', 'rew', 'done')] + \
+               [(k, C.c_int32) for k in ('capacity', 'n_envs', 'n_signals', 'width', 'head', 'count')]
 
 
 class SimGroup:

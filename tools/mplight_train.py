@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """MPLight training loop entirely on the GPU: HIP simulator -> states.mplight rows -> fused FRAP kernel (rs_mplight_act, global pair
-indices out) -> device replay ring -> shared-DQN update (PyTorch) -> weights re-packed on the device.  The analogue of
+indices out) -> device replay ring -> shared-DQN update (PyTorch, or with --device-update the fused HIP update of
+resco_amd/agents/mplight_learn_fused.py on the policy's own weight vector) -> weights re-packed on the device.  The analogue of
 tools/idqn_train.py for the reference's MPLight (agents/mplight.py, config/agent_config.py:101-113; batching:
 resco_amd/agents/mplight.py).
 
-    python tools/mplight_train.py [map] [n_envs] [episodes] [batch] [replay_steps] [seed] [full]
+    python tools/mplight_train.py [--device-update] [map] [n_envs] [episodes] [batch] [replay_steps] [seed] [full]
 
 Prints one JSON line per episode (mean episode return of rewards.pressure per signal, average trip delay as utils/readXML.py
 computes it, epsilon, env-steps/s including learning) and a final line with the best training episode and the on-device random
@@ -20,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from resco_amd.agents.idqn_learn import linear_epsilon                                      # noqa: E402
 from resco_amd.agents.mplight import FusedMPLight, MPLightLearner, MPLightReplay, frap_from_scenario      # noqa: E402
+from resco_amd.agents.mplight_learn_fused import FusedMPLightLearner                        # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                                           # noqa: E402
 
 
@@ -27,14 +29,19 @@ def delay(env):
     return float(env.sim.trip_delay().mean()), float(env.sim.stats()['arrived'].mean())
 
 
-def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, seed=0, full=False, quiet=False):
+def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, seed=0, full=False, quiet=False, device_update=False):
     state = 'mplight_full' if full else 'mplight'
     env = VecMultiSignal(map_name, n, states=(state,), rewards=('pressure',), seed=0, outputs=(state,))
     S, steps = env.n_signals, env.horizon_steps
     net = frap_from_scenario(env.scenario, 4 if full else 1).cuda()
     net.init_like_reference(seed)
-    learner = MPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch)
+    if device_update:
+        learner = FusedMPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed, n_signals=S)
+    else:
+        learner = MPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch)
     policy = FusedMPLight(net, env.scenario, seed=7 + seed)
+    if device_update:
+        policy.share_weights(learner.flat)      # the policy reads the vector the update writes: no re-pack per step
     replay = MPLightReplay(replay_steps, n, S, 1 + 12 * net.demand_shape, device='cuda')
     actions = env.tensor('actions')
     pair = torch.zeros(n, S, dtype=torch.int32, device='cuda')
@@ -63,7 +70,7 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
             rew = r['pressure'].float()
             replay.commit(pair, rew, done)
             ret += rew
-            if learner.observe_step(replay, gen) is not None:
+            if learner.observe_step(replay, gen) is not None and not device_update:
                 policy.refresh_on_device()
             obs = o[state]
         torch.cuda.synchronize()
@@ -77,12 +84,16 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
                  seed=seed, best_training_episode_delay_s=min(r['avg_delay_s'] for r in rows), random_avg_delay_s=round(rnd_delay, 2))
     if not quiet:
         print(json.dumps(final), flush=True)
+    if device_update:
+        learner.close()
     env.close()
     return rows, final
 
 
 if __name__ == '__main__':
     a = sys.argv[1:]
+    device_update = bool(a) and a[0] == '--device-update'
+    a = a[1:] if device_update else a
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 30,
          int(a[3]) if len(a) > 3 else 256, int(a[4]) if len(a) > 4 else 2048, int(a[5]) if len(a) > 5 else 0,
-         full=len(a) > 6 and a[6] == 'full')
+         full=len(a) > 6 and a[6] == 'full', device_update=device_update)
