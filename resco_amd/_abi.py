@@ -1,4 +1,4 @@
-"""ctypes mirror of the C-ABI structs in include/resco_sim.h (rs_scenario / rs_params)."""
+"""ctypes mirror of the C-ABI structs in include/resco_sim.h (rs_scenario / rs_params / rs_train)."""
 import ctypes as C
 
 import numpy as np
@@ -46,6 +46,16 @@ class ParamsStruct(C.Structure):
     _fields_ = [('seed', C.c_uint32), ('max_distance', C.c_float), ('sigma', C.c_float),
                 ('speed_dev', C.c_int32), ('fixed_program', C.c_int32), ('trip_log', C.c_int32), ('step_ratio', C.c_int32),
                 ('tls_hold', C.c_int32)]
+
+
+class TrainStruct(C.Structure):
+    """rs_train: what rs_group_train is told about the policy, the learner, the replay ring and the schedule (field order of the header)"""
+    _fields_ = [('kind', C.c_int32), ('n_envs', C.c_int32), ('policy', C.c_void_p), ('learner', C.c_void_p),
+                ('obs', C.c_void_p), ('act', C.c_void_p), ('rew', C.c_void_p), ('done', C.c_void_p), ('ret', C.c_void_p), ('loss_out', C.c_void_p),
+                ('t0', C.c_int64), ('eps_start', C.c_double), ('eps_end', C.c_double),
+                ('capacity', C.c_int32), ('head', C.c_int32), ('count', C.c_int32), ('done_step', C.c_int32),
+                ('batch', C.c_int32), ('updates_per_step', C.c_int32), ('target_update', C.c_int32), ('decay_steps', C.c_int32),
+                ('policy_seed', C.c_uint32), ('learner_seed', C.c_uint32)]
 
 
 def pack_scenario(sc, step_length=10, yellow_length=None):

@@ -1,0 +1,73 @@
+"""The DQN training loop of IDQN and MPLight in the library (include/resco_sim.h: rs_group_train; resco_amd/csrc/resco_group_train.h).
+
+`DeviceTrainer(envs, learner, policy, replay)` joins what the loops of tools/idqn_train.py and tools/mplight_train.py --device-update
+join in Python -- policy.act, replay.stage, env.step, replay.commit, ret += rew, learner.observe_step, policy.refresh_on_device --
+and `run(n_steps)` enqueues that many iterations with ONE call through the ABI.  It owns nothing new: the environments (one
+VecMultiSignal, or a list of them that split one batch over pipes with contiguous env_base values), the fused learner
+(FusedDQNLearner / FusedMPLightLearner), the fused policy (FusedIDQN / FusedMPLight) and the replay ring (DeviceReplay /
+MPLightReplay over ALL environments) stay the caller's and are advanced here exactly as the Python loop advances them, so the two
+can be mixed step by step and give the same bits.  The reset between episodes stays with the caller.  There is no CPU fallback.
+"""
+import torch
+
+from ..sim import DQNRing, MPLightRing, SimGroup
+from .idqn_learn import linear_epsilon
+from .idqn_learn_fused import FusedDQNLearner
+from .mplight_learn_fused import FusedMPLightLearner
+
+
+class DeviceTrainer:
+    def __init__(self, envs, learner, policy, replay, eps_start=1.0, eps_end=0.0, decay_steps=0, updates_per_step=1):
+        self.envs = list(envs.envs) if hasattr(envs, 'envs') else (list(envs) if isinstance(envs, (list, tuple)) else [envs])
+        self.learner, self.policy, self.replay = learner, policy, replay
+        self.eps_start, self.eps_end, self.decay_steps = float(eps_start), float(eps_end), int(decay_steps)
+        if isinstance(learner, FusedDQNLearner):
+            self.agent, self.updates_per_step = 'idqn', int(updates_per_step)
+            if not hasattr(policy, '_dev'):
+                policy.refresh_on_device()      # the library re-packs into the policy's own device buffers: they have to exist
+        elif isinstance(learner, FusedMPLightLearner):
+            if int(updates_per_step) != 1:
+                raise ValueError('MPLight runs one update per env-step (FusedMPLightLearner.observe_step)')
+            self.agent, self.updates_per_step = 'mplight', 1
+            learner._ring(replay)               # (creates the handle over the ring's signal count if it has none yet)
+        else:
+            raise TypeError('DeviceTrainer needs a FusedDQNLearner or a FusedMPLightLearner: the loop runs in the library (there is no CPU fallback)')
+        if sum(e.n_envs for e in self.envs) != replay.N:
+            raise ValueError('the environments (%d) are not the replay ring\'s (%d)' % (sum(e.n_envs for e in self.envs), replay.N))
+        self.group = SimGroup([e.sim for e in self.envs])
+
+    def epsilon(self, t):
+        """the exploration rate of agent step t, as the loop evaluates it"""
+        return linear_epsilon(t, self.eps_start, self.eps_end, self.decay_steps)
+
+    def run(self, n_steps, ret=None):
+        """n_steps env-steps of training, enqueued by one call; asynchronous.  ret: None or a float32 device tensor [N, S] that
+        accumulates the rewards (ret += rew per step).  Advances replay.head / replay.count, learner.t and the environments' step
+        counters and returns done (the episode's horizon is reached)."""
+        n, env0 = int(n_steps), self.envs[0]
+        if n < 1:
+            raise ValueError('need n_steps >= 1')
+        if any(e.steps != env0.steps or e.horizon_steps != env0.horizon_steps for e in self.envs):
+            raise RuntimeError('the pipes are not at the same step of the episode')
+        if env0.steps + n > env0.horizon_steps:
+            raise ValueError('%d steps from step %d would cross the horizon (%d): the reset between episodes is the caller\'s' %
+                             (n, env0.steps, env0.horizon_steps))
+        if torch.cuda.current_stream().cuda_stream != 0:
+            raise RuntimeError('DeviceTrainer needs PyTorch\'s default stream current: only that one is ordered with the pipes\' streams')
+        learner, replay = self.learner, self.replay
+        ring = learner._ring(replay)
+        assert isinstance(ring, DQNRing if self.agent == 'idqn' else MPLightRing)
+        if ret is not None:
+            assert ret.is_cuda and ret.dtype == torch.float32 and ret.is_contiguous() and tuple(ret.shape) == (replay.N, replay.S)
+        done_step = n - 1 if env0.steps + n == env0.horizon_steps else -1
+        self.group.train(n, self.agent, self.policy.handle, learner._h, ring, learner.t, done_step=done_step, batch=learner.batch_size,
+                         updates_per_step=self.updates_per_step, target_update=learner.target_update, eps_start=self.eps_start,
+                         eps_end=self.eps_end, decay_steps=self.decay_steps, policy_seed=self.policy.seed, learner_seed=learner.seed,
+                         ret=ret.data_ptr() if ret is not None else None, loss_out=learner.loss_out.data_ptr())
+        replay.head = (replay.head + n) % replay.T
+        replay.count = min(replay.count + n, replay.T)
+        if hasattr(replay, '_pos'):             # DeviceReplay mirrors its position on the device for the graph-captured PyTorch learner
+            replay._pos[0] = replay.head
+            replay._pos[1] = replay.count
+        learner.t += n
+        return [e.advance(n) for e in self.envs][0]

@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from ._abi import ParamsStruct, pack_scenario
+from ._abi import ParamsStruct, TrainStruct, pack_scenario
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RESCO_SIM_LIB: another build of the same HIP library (A/B variants compiled with different -D switches, tools/ab.py)
@@ -37,7 +37,8 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_ppo_create', 'rs_ppo_grad', 'rs_ppo_step', 'rs_ppo_fit', 'rs_ppo_steps', 'rs_ppo_destroy',
                'rs_dqn_create', 'rs_dqn_sample', 'rs_dqn_grad', 'rs_dqn_step', 'rs_dqn_update', 'rs_dqn_steps', 'rs_dqn_destroy',
                'rs_mplight_dqn_create', 'rs_mplight_dqn_sample', 'rs_mplight_dqn_grad', 'rs_mplight_dqn_step', 'rs_mplight_dqn_update',
-               'rs_mplight_dqn_steps', 'rs_mplight_dqn_destroy']
+               'rs_mplight_dqn_steps', 'rs_mplight_dqn_destroy',
+               'rs_idqn_pack_weights', 'rs_dqn_sync_target', 'rs_mplight_dqn_sync_target', 'rs_group_train']
 
 _lib = None
 
@@ -118,6 +119,11 @@ def bind(L):
         L.rs_mplight_dqn_steps.restype = C.c_int64
         L.rs_mplight_dqn_destroy.argtypes = [vp]
         L.rs_mplight_dqn_destroy.restype = None
+    if hasattr(L, 'rs_group_train'):
+        L.rs_idqn_pack_weights.argtypes = [vp, vp, vp]
+        L.rs_dqn_sync_target.argtypes = [vp, vp]
+        L.rs_mplight_dqn_sync_target.argtypes = [vp, vp]
+        L.rs_group_train.argtypes = [vp, i32, vp, i32]
     if hasattr(L, 'rs_default_block'):      # (the host emulation of the CPU tests exports only what it implements)
         L.rs_default_block.argtypes = [i32, i32, i32]
         L.rs_default_block.restype = i32
@@ -231,6 +237,23 @@ class SimGroup:
         if rc != 0:
             msgs = [m.decode() for m in (self._lib.rs_last_error(s._h) for s in self.sims) if m]
             raise RuntimeError('rs_group_rollout failed (%d): %s' % (rc, '; '.join(msgs)))
+
+    def train(self, n_steps, agent, policy, learner, ring, t0, done_step=-1, batch=32, updates_per_step=1, target_update=500, eps_start=1.0,
+              eps_end=0.0, decay_steps=0, policy_seed=0, learner_seed=0, ret=None, loss_out=None):
+        """rs_group_train: n_steps iterations of the --device-update training loop (record, act, step, record on every pipe's own
+        stream; target sync, updates and the IDQN re-pack on the legacy default stream), enqueued by one call.  agent: 'idqn' | 'mplight';
+        policy / learner: the library handles (FusedIDQN.handle / FusedMPLight.handle; the fused learner's); ring: a DQNRing or an
+        MPLightRing at the position BEFORE the call; ret / loss_out: device pointers or None.  Nothing is advanced on the Python side:
+        agents/train_fused.py: DeviceTrainer does that."""
+        if not hasattr(self._lib, 'rs_group_train'):
+            raise RuntimeError('the loaded library has no rs_group_train: rebuild it (there is no CPU fallback)')
+        t = TrainStruct(AGENT[agent], ring.n_envs, policy, learner, ring.obs, ring.act, ring.rew, ring.done, ret, loss_out, int(t0), float(eps_start),
+                        float(eps_end), ring.capacity, ring.head, ring.count, int(done_step), int(batch), int(updates_per_step), int(target_update),
+                        int(decay_steps), int(policy_seed) & 0xFFFFFFFF, int(learner_seed) & 0xFFFFFFFF)
+        rc = self._lib.rs_group_train(self._hs, len(self.sims), C.byref(t), int(n_steps))
+        if rc != 0:
+            msgs = [m.decode() for m in [self._lib.rs_last_error(s._h) for s in self.sims] + [self._lib.rs_last_error(None)] if m]
+            raise RuntimeError('rs_group_train failed (%d): %s' % (rc, '; '.join(dict.fromkeys(msgs))))
 
     def sync(self):
         for s in self.sims:

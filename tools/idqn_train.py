@@ -2,10 +2,11 @@
 """IDQN training loop entirely on the GPU: HIP simulator -> fp16 observations -> fused HIP policy kernel
 (rs_idqn_act) -> device replay ring -> batched DQN update (PyTorch, or HIP with --device-update) -> weights re-packed on the device.  Nothing crosses PCIe per step except the launch calls.
 
-    python tools/idqn_train.py [--device-update] [map] [n_envs] [episodes] [batch] [updates_per_step] [graph|nograph] [replay_steps] [eps_end] [seed]
+    python tools/idqn_train.py [--device-update | --device-loop] [map] [n_envs] [episodes] [batch] [updates_per_step] [graph|nograph] [replay_steps] [eps_end] [seed]
 
 --device-update: the update itself in HIP kernels as well (FusedDQNLearner, rs_dqn_update: sampling, target, backward and Adam of all
-updates of a step in one call; no HIP graph is captured).  Without it: the batched PyTorch learner, graph-captured unless `nograph`.
+updates of a step in one call; no HIP graph is captured).  --device-loop (implies --device-update): the loop itself in the library
+as well (agents/train_fused.py: DeviceTrainer, rs_group_train), one call per episode; the same rows.  Without either: the batched PyTorch learner, graph-captured unless `nograph`.
 
 Prints one JSON line per episode (mean episode return of rewards.wait_norm per signal, average trip delay as
 utils/readXML.py computes it, epsilon, env-steps/s including learning) and a final line comparing with the
@@ -23,6 +24,7 @@ from resco_amd.agents.idqn_learn import BatchedDQNLearner, DeviceReplay, linear_
 from resco_amd.agents.idqn_learn_fused import FusedDQNLearner                               # noqa: E402
 from resco_amd.agents.idqn_fused import FusedIDQN                                           # noqa: E402
 from resco_amd.agents.idqn_rollout import BatchedIDQN                                       # noqa: E402
+from resco_amd.agents.train_fused import DeviceTrainer                                      # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                                           # noqa: E402
 
 
@@ -32,7 +34,9 @@ def delay(env):
 
 
 def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_graph=True, replay_steps=0, eps_end=0.0, evaluate=True, quiet=False, seed=0, tls_expiry=True,
-         device_update=False):
+         device_update=False, device_loop=False, chunk=0):
+    """device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one)"""
+    device_update = device_update or device_loop
     rows = []
     env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0, tls_expiry=tls_expiry)
     S, steps = env.n_signals, env.horizon_steps
@@ -51,6 +55,7 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
     replay = DeviceReplay(replay_steps if replay_steps > 0 else min(2048, 4 * steps), n, S, net.lmax, device='cuda')
     gen = torch.Generator(device='cuda').manual_seed(seed)
     decay = int(0.8 * episodes * steps)                 # the reference decays over config['steps'] agent steps
+    trainer = DeviceTrainer(env, learner, policy, replay, 1.0, eps_end, decay, updates) if device_loop else None
 
     env.sim.set_seed(12345)                             # baseline: random policy on an evaluation demand seed
     env.reset()
@@ -65,7 +70,10 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
         ret = torch.zeros(n, S, device='cuda')
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for k in range(steps):
+        while trainer is not None and env.steps < steps:
+            trainer.run(min(chunk, steps - env.steps) if chunk > 0 else steps - env.steps, ret)
+            eps = trainer.epsilon(learner.t - 1)
+        for k in range(steps if trainer is None else 0):
             eps = linear_epsilon(learner.t, 1.0, eps_end, decay)
             policy.act(obs, epsilon=eps, step_key=learner.t, out=actions)
             replay.stage(obs)
@@ -113,8 +121,9 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
 
 if __name__ == '__main__':
     a = sys.argv[1:]
-    dev = a[:1] == ['--device-update']
+    loop = a[:1] == ['--device-loop']
+    dev = loop or a[:1] == ['--device-update']
     a = a[1:] if dev else a
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 12,
          int(a[3]) if len(a) > 3 else 256, int(a[4]) if len(a) > 4 else 1, (a[5] != 'nograph') if len(a) > 5 else True,
-         int(a[6]) if len(a) > 6 else 0, float(a[7]) if len(a) > 7 else 0.0, seed=int(a[8]) if len(a) > 8 else 0, device_update=dev)
+         int(a[6]) if len(a) > 6 else 0, float(a[7]) if len(a) > 7 else 0.0, seed=int(a[8]) if len(a) > 8 else 0, device_update=dev, device_loop=loop)

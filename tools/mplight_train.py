@@ -5,11 +5,12 @@ resco_amd/agents/mplight_learn_fused.py on the policy's own weight vector) -> we
 tools/idqn_train.py for the reference's MPLight (agents/mplight.py, config/agent_config.py:101-113; batching:
 resco_amd/agents/mplight.py).
 
-    python tools/mplight_train.py [--device-update] [map] [n_envs] [episodes] [batch] [replay_steps] [seed] [full]
+    python tools/mplight_train.py [--device-update | --device-loop] [map] [n_envs] [episodes] [batch] [replay_steps] [seed] [full]
 
 Prints one JSON line per episode (mean episode return of rewards.pressure per signal, average trip delay as utils/readXML.py
 computes it, epsilon, env-steps/s including learning) and a final line with the best training episode and the on-device random
-policy on the same demand.  `full`: MPLightFULL (states.mplight_full, demand_shape 4)."""
+policy on the same demand.  --device-loop (implies --device-update): the loop itself in the library as well
+(agents/train_fused.py: DeviceTrainer, rs_group_train), one call per episode; the same rows.  `full`: MPLightFULL (states.mplight_full, demand_shape 4)."""
 import json
 import os
 import sys
@@ -22,6 +23,7 @@ sys.path.insert(0, ROOT)
 from resco_amd.agents.idqn_learn import linear_epsilon                                      # noqa: E402
 from resco_amd.agents.mplight import FusedMPLight, MPLightLearner, MPLightReplay, frap_from_scenario      # noqa: E402
 from resco_amd.agents.mplight_learn_fused import FusedMPLightLearner                        # noqa: E402
+from resco_amd.agents.train_fused import DeviceTrainer                                      # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                                           # noqa: E402
 
 
@@ -29,7 +31,9 @@ def delay(env):
     return float(env.sim.trip_delay().mean()), float(env.sim.stats()['arrived'].mean())
 
 
-def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, seed=0, full=False, quiet=False, device_update=False):
+def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, seed=0, full=False, quiet=False, device_update=False, device_loop=False, chunk=0):
+    """device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one)"""
+    device_update = device_update or device_loop
     state = 'mplight_full' if full else 'mplight'
     env = VecMultiSignal(map_name, n, states=(state,), rewards=('pressure',), seed=0, outputs=(state,))
     S, steps = env.n_signals, env.horizon_steps
@@ -47,6 +51,7 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
     pair = torch.zeros(n, S, dtype=torch.int32, device='cuda')
     gen = torch.Generator(device='cuda').manual_seed(seed)
     decay = int(0.8 * episodes * steps)     # the reference decays over config['steps'] env-steps
+    trainer = DeviceTrainer(env, learner, policy, replay, 1.0, 0.0, decay) if device_loop else None
 
     env.sim.set_seed(12345)
     env.reset()
@@ -62,7 +67,10 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
         ret = torch.zeros(n, S, device='cuda')
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for k in range(steps):
+        while trainer is not None and env.steps < steps:
+            trainer.run(min(chunk, steps - env.steps) if chunk > 0 else steps - env.steps, ret)
+            eps = trainer.epsilon(learner.t - 1)
+        for k in range(steps if trainer is None else 0):
             eps = linear_epsilon(learner.t, 1.0, 0.0, decay)
             policy.act(obs, epsilon=eps, step_key=learner.t, out=actions, pair_out=pair)
             replay.stage(obs)
@@ -92,8 +100,9 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
 
 if __name__ == '__main__':
     a = sys.argv[1:]
-    device_update = bool(a) and a[0] == '--device-update'
+    device_loop = bool(a) and a[0] == '--device-loop'
+    device_update = device_loop or (bool(a) and a[0] == '--device-update')
     a = a[1:] if device_update else a
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 30,
          int(a[3]) if len(a) > 3 else 256, int(a[4]) if len(a) > 4 else 2048, int(a[5]) if len(a) > 5 else 0,
-         full=len(a) > 6 and a[6] == 'full', device_update=device_update)
+         full=len(a) > 6 and a[6] == 'full', device_update=device_update, device_loop=device_loop)

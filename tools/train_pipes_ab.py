@@ -10,7 +10,11 @@ all pipes are enqueued by ONE rs_group_step call, each pipe on its own stream; t
 concatenation of the pipes (pipe i owns rows sum(n[:i]) ..), and MPLight's global pair index is looked up from the local action
 taken.  That is the single handle's training bit for bit (tests/test_gpu_train_pipes.py), so the rates compare like with like.  The
 variants alternate inside the process, `runs` rounds; the first episode of a run warms up.  Prints one line per run and a JSON
-summary.  A measurement script: the tools themselves keep one handle."""
+summary.  A measurement script: the tools themselves keep one handle.
+
+Variants loop1, loop2 and loop4 are the same training again with the loop inside the library (agents/train_fused.py: DeviceTrainer,
+rs_group_train: one call per episode) on 1, 2 and 4 pipes -- the same bits once more (tests/test_gpu_group_train.py); their ratios
+are to variant 1, the Python-driven loop of the same process (profiles/r13_group_train.txt)."""
 import json
 import os
 import sys
@@ -27,6 +31,7 @@ from resco_amd.agents.idqn_learn_fused import FusedDQNLearner                   
 from resco_amd.agents.idqn_rollout import BatchedIDQN                                       # noqa: E402
 from resco_amd.agents.mplight import FusedMPLight, MPLightReplay, frap_from_scenario        # noqa: E402
 from resco_amd.agents.mplight_learn_fused import FusedMPLightLearner                        # noqa: E402
+from resco_amd.agents.train_fused import DeviceTrainer                                      # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal, load_scenario, map_configs               # noqa: E402
 from resco_amd.sim import SimGroup, load_library                                            # noqa: E402
 from tools import idqn_train, mplight_train                                                 # noqa: E402
@@ -152,6 +157,49 @@ def train_piped(agent, map_name='cologne1', n=256, episodes=4, batch=256, pipes=
     return rows
 
 
+def train_device_loop(agent, map_name='cologne1', n=256, episodes=4, batch=256, pipes=1, seed=0, full=False, chunks=None):
+    """train_piped's training with the loop in the library: DeviceTrainer.run, one call per episode, or one per entry of `chunks`
+    (step counts that add up to the horizon).  Returns the rows."""
+    idqn = agent == 'idqn'
+    state = 'drq_norm_f16' if idqn else ('mplight_full' if full else 'mplight')
+    kw = dict(states=(state,), rewards=('wait_norm' if idqn else 'pressure',), seed=0)
+    if not idqn:
+        kw['outputs'] = (state,)
+    pe = PipedEnvs(map_name, n, pipes, **kw)
+    S, steps = pe.n_signals, pe.horizon_steps
+    if idqn:
+        net = BatchedIDQN.from_scenario(pe.scenario, dtype=torch.float32, device='cuda')
+        net.init_like_reference(seed=seed)
+        learner = FusedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed)
+        policy = FusedIDQN(net, seed=7 + seed)
+        replay = DeviceReplay(min(2048, 4 * steps), n, S, net.lmax, device='cuda')
+    else:
+        net = frap_from_scenario(pe.scenario, 4 if full else 1).cuda()
+        net.init_like_reference(seed)
+        learner = FusedMPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed, n_signals=S)
+        policy = FusedMPLight(net, pe.scenario, seed=7 + seed)
+        policy.share_weights(learner.flat)
+        replay = MPLightReplay(2048, n, S, 1 + 12 * net.demand_shape, device='cuda')
+    trainer = DeviceTrainer(pe, learner, policy, replay, 1.0, 0.0, int(0.8 * episodes * steps))
+    rows = []
+    for ep in range(episodes):
+        pe.set_seed(1000 + ep + 7919 * seed)
+        pe.reset()
+        ret = torch.zeros(n, S, device='cuda')
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for c in (chunks or (steps,)):
+            trainer.run(c, ret)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        d, arrived = pe.delay()
+        rows.append(dict(episode=ep, epsilon=round(trainer.epsilon(learner.t - 1), 3), mean_return=float(ret.sum(1).mean()) / S, avg_delay_s=round(d, 2),
+                         arrived_per_env=round(arrived, 1), updates=learner.n_updates, env_steps_per_s=round(n * steps / dt)))
+    learner.close()
+    pe.close()
+    return rows
+
+
 def train_one_handle(agent, map_name, n, episodes, batch=256, seed=0, full=False):
     """the tools' own loop with --device-update: the rows"""
     if agent == 'idqn':
@@ -162,11 +210,14 @@ def train_one_handle(agent, map_name, n, episodes, batch=256, seed=0, full=False
 def main(agent='idqn', map_name='ingolstadt21', n=1024, episodes=4, runs=2):
     res = {}
     for run in range(runs):
-        for pipes in (1, 2, 4):
-            rows = train_one_handle(agent, map_name, n, episodes) if pipes == 1 else train_piped(agent, map_name, n, episodes, pipes=pipes)
+        for pipes in (1, 2, 4, 'loop1', 'loop2', 'loop4'):
+            if isinstance(pipes, str):
+                rows = train_device_loop(agent, map_name, n, episodes, pipes=int(pipes[4:]))
+            else:
+                rows = train_one_handle(agent, map_name, n, episodes) if pipes == 1 else train_piped(agent, map_name, n, episodes, pipes=pipes)
             rates = [r['env_steps_per_s'] for r in rows[1:]]
             res.setdefault(pipes, []).append(rates)
-            print('%s %s x %d pipes %d run %d: %s env-steps/s, last delay %.2f s' % (agent, map_name, n, pipes, run, rates, rows[-1]['avg_delay_s']),
+            print('%s %s x %d pipes %s run %d: %s env-steps/s, last delay %.2f s' % (agent, map_name, n, pipes, run, rates, rows[-1]['avg_delay_s']),
                   flush=True)
     base = np.mean(res[1])
     print(json.dumps(dict(agent=agent, map=map_name, envs=n, episodes=episodes, runs=runs, env_steps_per_s={str(k): v for k, v in res.items()},
