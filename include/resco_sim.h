@@ -545,7 +545,7 @@ void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p);
  * caller's (rs_idqn_set_device_weights, as after a first refresh_on_device()): a policy that still reads a create-time copy is refused
  * with RS_EINVAL.  fc3_w is read as [S][64][amax] and fc3_b as [S][amax] with amax = the largest n_actions[s] of rs_idqn_create, which
  * is a BatchedIDQN's layout.  ONLY IDQN packs are served: the ABI carries no shapes, so an IPPO pack (pack_ippo_weights: the value
- * head in column 8 of w3 and b3) cannot be told apart and would lose its value head to zeros -- do not call this on one.
+ * head in column 8 of w3 and b3) cannot be told apart and would lose its value head to zeros -- that one is rs_ippo_pack_weights'.
  *
  * rs_dqn_sync_target / rs_mplight_dqn_sync_target: target <- params for the tensors the learner handle borrows, as ONE copy kernel
  * (16-byte words where source and destination are aligned, element by element otherwise and for the tail), not a runtime memcpy.
@@ -606,6 +606,61 @@ int rs_idqn_pack_weights(rs_policy_handle p, const rs_dqn_tensors *params, void 
 int rs_dqn_sync_target(rs_dqn_handle p, void *stream);
 int rs_mplight_dqn_sync_target(rs_mplight_dqn_handle p, void *stream);
 int rs_group_train(const rs_handle *handles, int32_t n_handles, const rs_train *train, int32_t n_steps);
+
+/* ---- the PPO training loop of IPPO in one call (resco_amd/csrc/resco_ppo_loop.h) -----------------------------------------------
+ * What the loop of tools/ippo_train.py --device-update does per segment in Python (two host synchronisations, the dataset glue,
+ * `epochs` torch.randperm calls, FusedIPPO.refresh_on_device) enqueued by the library; the reference's loop is main.py:104-108 with
+ * pfrl's PPO (agents/pfrl_ppo.py:38-75).  Two entry points that also stand alone, and the loop.
+ *
+ * rs_ppo_perm: perm (device int32 [epochs][n]) <- `epochs` permutations of 0 .. n - 1, the shuffles of one update.  Row e is a pure
+ * function of (seed, update_key, e, n): a four-round Feistel network over 2 h bits (h = max(1, ceil(bits(n - 1) / 2))) whose round
+ * function is the simulator's counter hash, walked along its cycle until the value is below n.  Every element is computed by its own
+ * thread -- no sort, no atomics, no workspace --, so two runs give the same bits.  Unlike torch.randperm it can be restated anywhere
+ * (resco_ppo_loop.h compiles for the host).  Refusals (RS_EINVAL, text in rs_last_error(NULL)): n < 1, epochs outside 1 .. 65535, a
+ * NULL perm.
+ *
+ * rs_ippo_pack_weights: rs_idqn_pack_weights for an actor-critic pack (resco_amd/agents/ippo_fused.py: pack_ippo_weights): w3 is
+ * gathered from the virtual [64][9] matrix of fc3_with_value -- columns 0 .. amax - 1 are fc3_w, columns up to 7 zero, column 8 is v_w
+ * --, b3[s][a < amax] = fc3_b, b3[s][8] = v_b, the rest zero: the bytes of FusedIPPO.refresh_on_device(), in one launch.  A policy that
+ * still reads a create-time copy is refused, as there.
+ *
+ * rs_group_ppo_train: for k < n_steps, with slot i = (slot0 + k) mod T, everything on the LEGACY default stream (hipStreamLegacy:
+ * PyTorch's default stream):
+ *   1. one step of rs_group_rollout into slot i -- recorder, actor-critic kernel with key t0 + k, step kernel, recorder -- and
+ *      done[i] = (k == done_step), written by a kernel (one launch for the slots a call fills up to the segment's end);
+ *   2. when i == T - 1, the update: rs_ippo_act in value-only mode on the handle's RS_BUF_DRQ_NORM_F16 -> last_value; rs_ppo_gae;
+ *      rs_ppo_perm(T * n_envs, epochs, learner_seed, update0 + u) for the u-th update of this call; the launches of rs_ppo_fit on the
+ *      segment in place (n = T * n_envs rows); rs_ippo_pack_weights from the learner's parameter set.
+ * One call may complete several segments, and a segment may span calls (and the caller's reset between episodes).  ONE handle only:
+ * rs_rollout has no row stride, so several pipes cannot share one dataset, and pipes in training were measured below one handle
+ * (profiles/r12_train_pipes.txt, profiles/r13_group_train.txt).  The call creates no stream, no event and no wait and uses no
+ * asynchronous memcpy; the library keeps no loop state beyond the learner's step counter: the caller advances slot0 to (slot0 +
+ * n_steps) mod T, t0 by n_steps and update0 by (slot0 + n_steps) / T afterwards.  Asynchronous.  NOT checked: the sizes of the buffers.
+ * Refusals (RS_EINVAL, text in rs_last_error of the handle and of NULL, nothing launched): n_handles != 1; n_steps < 1; slot0 outside
+ * 0 .. T - 1; done_step outside -1 .. n_steps - 1; a NULL buffer (loss_out may be NULL); T * n_envs outside 1 .. 2^31 - 1; minibatch
+ * outside 1 .. max_minibatch of rs_ppo_create; epochs outside 1 .. 65535; negative t0 or update0; a policy or learner that does not fit
+ * the scenario (n_signals, lmax, amax) or lives on another device; a policy on its create-time weights; a switched-off
+ * RS_BUF_DRQ_NORM_F16; a non-blocking handle stream (its other launches would not be ordered with the loop's); rs_timing enabled. */
+typedef struct rs_ppo_train {
+    rs_policy_handle policy;
+    rs_ppo_handle learner;
+    rs_rollout seg;              /* the handle's segment, T slots */
+    uint8_t *done;               /* device [T] */
+    float *last_value;           /* device [n_envs][S] */
+    float *adv, *ret;            /* device [T][n_envs][S] */
+    void *gae_scratch;           /* n_envs * S floats */
+    int32_t *perm;               /* device [epochs][T * n_envs] */
+    float *loss_out;             /* device [S][3] or NULL */
+    int64_t t0;                  /* env-steps before this call: key of the first step */
+    int64_t update0;             /* updates finished before this call: key of the first shuffle */
+    int32_t slot0, done_step;    /* filled slots at entry (0 .. T-1); -1 or the k at which the horizon is reached */
+    int32_t epochs, minibatch;
+    float gamma, lambda;
+    uint32_t policy_seed, learner_seed;
+} rs_ppo_train;
+int rs_ppo_perm(int32_t n, int32_t epochs, uint32_t seed, uint32_t update_key, int32_t *perm /* device [epochs][n] */, void *stream);
+int rs_ippo_pack_weights(rs_policy_handle p, const rs_ppo_tensors *params, void *stream);
+int rs_group_ppo_train(const rs_handle *handles, int32_t n_handles, const rs_ppo_train *tr, int32_t n_steps);
 
 /* static facts */
 int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal);

@@ -1,4 +1,4 @@
-"""ctypes mirror of the C-ABI structs in include/resco_sim.h (rs_scenario / rs_params / rs_train)."""
+"""ctypes mirror of the C-ABI structs in include/resco_sim.h (rs_scenario / rs_params / rs_train / rs_rollout / rs_ppo_train)."""
 import ctypes as C
 
 import numpy as np
@@ -56,6 +56,20 @@ class TrainStruct(C.Structure):
                 ('capacity', C.c_int32), ('head', C.c_int32), ('count', C.c_int32), ('done_step', C.c_int32),
                 ('batch', C.c_int32), ('updates_per_step', C.c_int32), ('target_update', C.c_int32), ('decay_steps', C.c_int32),
                 ('policy_seed', C.c_uint32), ('learner_seed', C.c_uint32)]
+
+
+class RolloutStruct(C.Structure):
+    """rs_rollout: the device buffers of one handle's trajectory segment"""
+    _fields_ = [('obs', C.c_void_p), ('act', C.c_void_p), ('logp', C.c_void_p), ('value', C.c_void_p), ('rew', C.c_void_p), ('T', C.c_int32)]
+
+
+class PPOTrainStruct(C.Structure):
+    """rs_ppo_train: what rs_group_ppo_train is told about the policy, the learner, the segment, the update's buffers and the position
+    (field order of the header; `lambda` is a Python keyword: fill the struct positionally)"""
+    _fields_ = [('policy', C.c_void_p), ('learner', C.c_void_p), ('seg', RolloutStruct), ('done', C.c_void_p), ('last_value', C.c_void_p),
+                ('adv', C.c_void_p), ('ret', C.c_void_p), ('gae_scratch', C.c_void_p), ('perm', C.c_void_p), ('loss_out', C.c_void_p),
+                ('t0', C.c_int64), ('update0', C.c_int64), ('slot0', C.c_int32), ('done_step', C.c_int32), ('epochs', C.c_int32),
+                ('minibatch', C.c_int32), ('gamma', C.c_float), ('lambda', C.c_float), ('policy_seed', C.c_uint32), ('learner_seed', C.c_uint32)]
 
 
 def pack_scenario(sc, step_length=10, yellow_length=None):

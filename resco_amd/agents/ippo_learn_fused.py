@@ -20,9 +20,10 @@ class FusedPPOLearner(FusedLearnerBase):
     NAME, PREFIX, TENSORS, TENSOR_SET, LOSS_SHAPE = 'FusedPPOLearner', 'rs_ppo', PPO_TENSORS, PPOTensors, (3,)
 
     def __init__(self, net, lr=2.5e-4, adam_eps=1e-5, gamma=0.99, lambd=0.95, clip_eps=0.1, epochs=4, minibatch=256,
-                 entropy_coef=0.001, value_coef=1.0, max_grad_norm=0.5):
+                 entropy_coef=0.001, value_coef=1.0, max_grad_norm=0.5, seed=0):
         assert isinstance(net, BatchedIPPO)
         super().__init__(net)
+        self.seed = int(seed) & 0xFFFFFFFF      # of device_perm's shuffles (torch.randperm draws from its own generator)
         self.lr, self.adam_eps = lr, adam_eps
         self.gamma, self.lambd, self.clip_eps, self.epochs, self.minibatch = gamma, lambd, clip_eps, int(epochs), int(minibatch)
         self.entropy_coef, self.value_coef, self.max_grad_norm = entropy_coef, value_coef, max_grad_norm
@@ -86,13 +87,29 @@ class FusedPPOLearner(FusedLearnerBase):
             self._fail('rs_ppo_fit', rc)
         return self.loss_out
 
-    def update_from_rollout(self, rollout, last_value, done, generator=None):
+    def device_perm(self, n, update_key, out=None):
+        """The shuffles of update `update_key` over n rows, int32 [epochs, n] on the device (rs_ppo_perm): row e is a permutation of
+        0 .. n - 1 that is a function of (self.seed, update_key, e, n) alone -- what the library's own loop (rs_group_ppo_train)
+        draws, where torch.randperm's generator cannot be restated.  out: a tensor of that shape to write into."""
+        self._need_handle()
+        if not hasattr(self._lib, 'rs_ppo_perm'):
+            raise RuntimeError('the loaded library has no rs_ppo_perm: rebuild it (there is no CPU fallback)')
+        perm = out if out is not None else torch.empty(self.epochs, int(n), dtype=torch.int32, device=self.device)
+        assert perm.is_cuda and perm.dtype == torch.int32 and perm.is_contiguous() and tuple(perm.shape) == (self.epochs, int(n))
+        rc = self._lib.rs_ppo_perm(int(n), self.epochs, self.seed, int(update_key) & 0xFFFFFFFF, perm.data_ptr(), torch_stream(self.device.index))
+        if rc != 0:
+            self._fail('rs_ppo_perm', rc)
+        return perm
+
+    def update_from_rollout(self, rollout, last_value, done, generator=None, perm=None):
         """BatchedPPOLearner.update_from_rollout with the fused update: the same dataset (dataset_from_rollout: the recording and
-        rs_ppo_gae), one torch.randperm per epoch on the device, one rs_ppo_fit.  CPU tensors raise.  Returns the last minibatch's
-        loss as .loss() forms it (a device scalar)."""
+        rs_ppo_gae), one torch.randperm per epoch on the device, one rs_ppo_fit.  perm: None, or the shuffles to use as they are
+        (an integer device tensor [epochs, n], e.g. device_perm's); the generator is then not drawn from.  CPU tensors raise.
+        Returns the last minibatch's loss as .loss() forms it (a device scalar)."""
         ds = self._dataset_from_rollout(rollout, last_value, done)
         n, dev = ds['act'].shape[0], ds['act'].device
         ds['act'] = rollout.cat('act').reshape(n, -1)       # the recorded int32 itself (the dataset's copy is int64 for torch's gather)
-        perm = torch.stack([torch.randperm(n, device=dev, generator=generator) for _ in range(self.epochs)])
+        if perm is None:
+            perm = torch.stack([torch.randperm(n, device=dev, generator=generator) for _ in range(self.epochs)])
         lo = self.fit(ds, perm)
         return (lo[:, 0] + self.value_coef * lo[:, 1] - self.entropy_coef * lo[:, 2]).sum()

@@ -1,4 +1,5 @@
-"""The DQN training loop of IDQN and MPLight in the library (include/resco_sim.h: rs_group_train; resco_amd/csrc/resco_group_train.h).
+"""The training loops in the library: the DQN loop of IDQN and MPLight (include/resco_sim.h: rs_group_train;
+resco_amd/csrc/resco_group_train.h) and the PPO loop of IPPO (rs_group_ppo_train; resco_amd/csrc/resco_ppo_loop.h).
 
 `DeviceTrainer(envs, learner, policy, replay)` joins what the loops of tools/idqn_train.py and tools/mplight_train.py --device-update
 join in Python -- policy.act, replay.stage, env.step, replay.commit, ret += rew, learner.observe_step, policy.refresh_on_device --
@@ -7,12 +8,19 @@ VecMultiSignal, or a list of them that split one batch over pipes with contiguou
 (FusedDQNLearner / FusedMPLightLearner), the fused policy (FusedIDQN / FusedMPLight) and the replay ring (DeviceReplay /
 MPLightReplay over ALL environments) stay the caller's and are advanced here exactly as the Python loop advances them, so the two
 can be mixed step by step and give the same bits.  The reset between episodes stays with the caller.  There is no CPU fallback.
+
+`DevicePPOTrainer(env, learner, policy, rollout)` does the same for the loop of tools/ippo_train.py --device-update: grp.rollout,
+policy.value, learner.update_from_rollout with the learner's device_perm shuffles, policy.refresh_on_device.  One environment (one
+handle), a FusedPPOLearner, a FusedIPPO and a DeviceRollout over that handle; the trainer owns the update's buffers (done bytes,
+bootstrap value, advantages, returns, shuffles).
 """
 import torch
 
 from ..sim import DQNRing, MPLightRing, SimGroup
 from .idqn_learn import linear_epsilon
 from .idqn_learn_fused import FusedDQNLearner
+from .ippo_fused import FusedIPPO
+from .ippo_learn_fused import FusedPPOLearner
 from .mplight_learn_fused import FusedMPLightLearner
 
 
@@ -71,3 +79,45 @@ class DeviceTrainer:
             replay._pos[1] = replay.count
         learner.t += n
         return [e.advance(n) for e in self.envs][0]
+
+
+class DevicePPOTrainer:
+    def __init__(self, env, learner, policy, rollout):
+        if not isinstance(learner, FusedPPOLearner) or not isinstance(policy, FusedIPPO):
+            raise TypeError('DevicePPOTrainer needs a FusedPPOLearner and a FusedIPPO: the loop runs in the library (there is no CPU fallback)')
+        if len(rollout.sims) != 1 or rollout.sims[0] is not env.sim:
+            raise ValueError('the rollout must be this one environment\'s: a segment has no row stride, pipes cannot share one dataset')
+        self.env, self.learner, self.policy, self.rollout = env, learner, policy, rollout
+        learner._need_handle()
+        if not hasattr(policy, '_dev'):
+            policy.refresh_on_device()          # the library re-packs into the policy's own device buffers: they have to exist
+        self.group = SimGroup([env.sim])
+        T, N, S, dev = rollout.T, env.sim.n_envs, env.sim.S, learner.device
+        f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        self.done = torch.zeros(T, dtype=torch.uint8, device=dev)
+        self.last_value, self.adv, self.ret, self._scratch = f(N, S), f(T, N, S), f(T, N, S), f(N, S)
+        self.perm = torch.zeros(learner.epochs, T * N, dtype=torch.int32, device=dev)
+        self.slot, self.t, self.updates = 0, 0, 0       # filled slots of the segment, env-steps and updates so far
+
+    def run(self, n_steps):
+        """n_steps env-steps of training, enqueued by one call; asynchronous.  Advances the slot, the step and the update counter and
+        the environment's step counter and returns done (the episode's horizon is reached)."""
+        n, env = int(n_steps), self.env
+        if n < 1:
+            raise ValueError('need n_steps >= 1')
+        if env.steps + n > env.horizon_steps:
+            raise ValueError('%d steps from step %d would cross the horizon (%d): the reset between episodes is the caller\'s' %
+                             (n, env.steps, env.horizon_steps))
+        if torch.cuda.current_stream().cuda_stream != 0:
+            raise RuntimeError('DevicePPOTrainer needs PyTorch\'s default stream current: the loop is launched on the legacy stream')
+        L, T = self.learner, self.rollout.T
+        done_step = n - 1 if env.steps + n == env.horizon_steps else -1
+        ptr = lambda t: t.data_ptr()
+        self.group.ppo_train(n, self.policy.handle, L._h, self.rollout.segments([env.sim])[0], ptr(self.done), ptr(self.last_value), ptr(self.adv),
+                             ptr(self.ret), ptr(self._scratch), ptr(self.perm), self.t, self.updates, self.slot, done_step=done_step,
+                             epochs=L.epochs, minibatch=L.minibatch, gamma=L.gamma, lambd=L.lambd, policy_seed=self.policy.seed,
+                             learner_seed=L.seed, loss_out=ptr(L.loss_out))
+        self.updates += (self.slot + n) // T
+        self.slot = (self.slot + n) % T
+        self.t += n
+        return env.advance(n)

@@ -33,7 +33,11 @@ struct alignas(16) GtVec16 { uint32_t x, y, z, w; };       // one 16-byte word o
 // element is padding -- idqn_fused.repack_index(lmax, amax)[w1 / w2 / w3][o] for every lmax in 2 .. 17 and amax in 1 .. 8
 // (tests/test_group_train_cpu.py).  No gather table is read.
 GT_HD int gt_pack_count(int which, int lmax) { return which == 0 ? 64 * (lmax / 2) * 512 : (which == 1 ? 4096 : 2048); }
-GT_HD int gt_pack_src(int which, int o, int lmax, int amax) {
+// VALUE: the actor-critic pack (rs_ippo_pack_weights).  Its w3 is gathered from the virtual [64][9] matrix of
+// resco_amd/agents/ippo_fused.py: fc3_with_value -- columns 0 .. amax - 1 fc3_w, zeros up to 7, the value head v_w in column 8 -- and the
+// index is ippo_repack_index(lmax, amax)['w3'] (amax does not enter it); w1 and w2 are the same.  Without VALUE: an IDQN pack, as ever.
+#define GT_VALUE_COL 8      // POL_QMAX: the value head's column of the fc3 tile, its bias in b3[s][8]
+template <bool VALUE> GT_HD int gt_pack_src_t(int which, int o, int lmax, int amax) {
     const int j = o & 3, lane = (o >> 2) & 63;
     const int krow = (lane >> 5) * 4 + j, col = lane & 31;
     if (which == 0) {
@@ -43,8 +47,11 @@ GT_HD int gt_pack_src(int which, int o, int lmax, int amax) {
         return k < H4 ? (c * H4 + k) * 64 + n : -1;
     }
     if (which == 1) return ((o >> 9) * 8 + krow) * 64 + ((o >> 8) & 1) * 32 + col;
+    if (VALUE) return col <= GT_VALUE_COL ? ((o >> 8) * 8 + krow) * (GT_VALUE_COL + 1) + col : -1;
     return col < amax ? ((o >> 8) * 8 + krow) * amax + col : -1;
 }
+GT_HD int gt_pack_src(int which, int o, int lmax, int amax) { return gt_pack_src_t<false>(which, o, lmax, amax); }
+GT_HD int gt_pack_src_value(int which, int o, int lmax, int amax) { return gt_pack_src_t<true>(which, o, lmax, amax); }
 
 // fp32 -> fp16 bits, round to nearest even, overflow to infinity, denormals kept: what a casting copy_ and numpy's astype do.  On the
 // device this is one v_cvt_f16_f32 (the default rounding mode is nearest-even and the kernels here never change it).
@@ -76,13 +83,17 @@ struct GtPack {
     float *b3;                                      // [S][32]
     int32_t lmax, amax;
 };
+struct GtPackValue : GtPack {                       // the actor-critic pack: also the value head [S][64][1], [S][1].  (A struct of its own:
+    const float *v_w, *v_b;                         // the IDQN kernel keeps its argument layout and with it its instructions)
+};
 GT_HD int gt_pack_units(int lmax) { return (gt_pack_count(0, lmax) + 4096 + 2048) / 4 + 32; }
-GT_HD void gt_pack_unit(const GtPack &P, int s, int u) {
+template <bool VALUE, class Pack> GT_HD void gt_pack_unit_t(const Pack &P, int s, int u) {
     const int n1 = gt_pack_count(0, P.lmax) / 4, n2 = 1024, n3 = 512;
     int which = 0;
-    if (u >= n1 + n2 + n3) {                        // b3: zero beyond the signal set's amax columns
+    if (u >= n1 + n2 + n3) {                        // b3: zero beyond the signal set's amax columns (VALUE: but for v_b in column 8)
         const int a = u - (n1 + n2 + n3);
-        P.b3[(size_t)s * 32 + a] = a < P.amax ? P.fc3_b[(size_t)s * P.amax + a] : 0.0f;
+        if constexpr (VALUE) P.b3[(size_t)s * 32 + a] = a < P.amax ? P.fc3_b[(size_t)s * P.amax + a] : (a == GT_VALUE_COL ? P.v_b[s] : 0.0f);
+        else P.b3[(size_t)s * 32 + a] = a < P.amax ? P.fc3_b[(size_t)s * P.amax + a] : 0.0f;
         return;
     }
     if (u >= n1 + n2) { which = 2; u -= n1 + n2; } else if (u >= n1) { which = 1; u -= n1; }
@@ -91,13 +102,22 @@ GT_HD void gt_pack_unit(const GtPack &P, int s, int u) {
     uint16_t *dst = (which == 0 ? P.w1 : (which == 1 ? P.w2 : P.w3)) + (size_t)s * gt_pack_count(which, P.lmax) + (size_t)u * 4;
     uint16_t h[4];
     for (int j = 0; j < 4; ++j) {
-        const int i = gt_pack_src(which, u * 4 + j, P.lmax, P.amax);
+        const int i = gt_pack_src_t<VALUE>(which, u * 4 + j, P.lmax, P.amax);
+        if constexpr (VALUE) {
+            if (which == 2) {                       // element (k, c) of the virtual [64][9] matrix: fc3_w, zeros, v_w
+                const int k = i / (GT_VALUE_COL + 1), c = i - k * (GT_VALUE_COL + 1);
+                h[j] = i < 0 ? (uint16_t)0 : (c < P.amax ? gt_f2h(src[k * P.amax + c]) : (c == GT_VALUE_COL ? gt_f2h(P.v_w[(size_t)s * 64 + k]) : (uint16_t)0));
+                continue;
+            }
+        }
         h[j] = i >= 0 ? gt_f2h(src[i]) : (uint16_t)0;
     }
     uint32_t lo = (uint32_t)h[0] | ((uint32_t)h[1] << 16), hi = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
     ((uint32_t *)dst)[0] = lo;                      // (a fragment buffer is a torch allocation: its elements 4 u .. 4 u + 3 are 8-byte aligned)
     ((uint32_t *)dst)[1] = hi;
 }
+GT_HD void gt_pack_unit(const GtPack &P, int s, int u) { gt_pack_unit_t<false, GtPack>(P, s, u); }
+GT_HD void gt_pack_unit_value(const GtPackValue &P, int s, int u) { gt_pack_unit_t<true, GtPackValue>(P, s, u); }
 
 // ------------------------------------------------------------------------------------------------ copies
 // n elements of 2 or 4 bytes from src to dst for the "threads" i0, i0 + stride, ..: 16-byte words where `vec` (the caller found both
@@ -216,6 +236,11 @@ __global__ void __launch_bounds__(256) rs_train_record_kernel(GtRec R) { gt_reco
 __global__ void __launch_bounds__(256) rs_idqn_pack_kernel(GtPack P) {
     const int n = gt_pack_units(P.lmax);
     for (int u = blockIdx.x * 256 + threadIdx.x; u < n; u += gridDim.x * 256) gt_pack_unit(P, (int)blockIdx.y, u);
+}
+// the same grid for the actor-critic pack (rs_ippo_pack_weights)
+__global__ void __launch_bounds__(256) rs_ippo_pack_kernel(GtPackValue P) {
+    const int n = gt_pack_units(P.lmax);
+    for (int u = blockIdx.x * 256 + threadIdx.x; u < n; u += gridDim.x * 256) gt_pack_unit_value(P, (int)blockIdx.y, u);
 }
 // grid (x, tensors)
 __global__ void __launch_bounds__(256) rs_sync_target_kernel(GtSync Y) { gt_sync_tensor(Y, (int)blockIdx.y, (int)(blockIdx.x * 256 + threadIdx.x), (int)(gridDim.x * 256)); }

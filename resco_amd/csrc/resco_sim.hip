@@ -115,6 +115,7 @@ __device__ unsigned long long *g_sec_prof;
 #include "resco_dqn_train.h"
 #include "resco_frap_train.h"
 #include "resco_group_train.h"
+#include "resco_ppo_loop.h"
 
 // ------------------------------------------------------------------------------------------------ kernels
 // The tables / state / output descriptors live in ONE constant block in device memory (StepArgs): passed by value they
@@ -802,13 +803,15 @@ extern "C" int rs_ippo_act(rs_policy_handle p, const void *obs, int32_t n_envs, 
 }
 
 // ---- PPO: GAE + per-signal standardisation (resco_ppo.h)
+static void gae_launch(const PpoArgs &A, hipStream_t st) {
+    const int C = A.N * A.S;
+    hipLaunchKernelGGL(rs_ppo_gae_columns_kernel, dim3((C + 255) / 256), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(rs_ppo_standardise_kernel, dim3(A.S), dim3(PPO_B), 0, st, A);
+}
 extern "C" int rs_ppo_gae(const float *rew, const float *value, const float *last_value, const uint8_t *done, int32_t T, int32_t n_envs,
                           int32_t n_signals, float gamma, float lambda, float *adv, float *ret, void *scratch, void *stream) {
     if (!rew || !value || !last_value || !done || !adv || !ret || !scratch || T <= 0 || n_envs <= 0 || n_signals <= 0) return RS_EINVAL;
-    const PpoArgs A{rew, value, last_value, done, T, n_envs, n_signals, gamma, lambda, adv, ret, (float *)scratch};
-    const int C = n_envs * n_signals;
-    hipLaunchKernelGGL(rs_ppo_gae_columns_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, A);
-    hipLaunchKernelGGL(rs_ppo_standardise_kernel, dim3(n_signals), dim3(PPO_B), 0, (hipStream_t)stream, A);
+    gae_launch(PpoArgs{rew, value, last_value, done, T, n_envs, n_signals, gamma, lambda, adv, ret, (float *)scratch}, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
 }
 
@@ -951,6 +954,17 @@ extern "C" int rs_ppo_step(rs_ppo_handle p, void *stream) {
     return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
 }
 
+// the launches of a whole update: every epoch's minibatches of perm[e], the last of them short when minibatch does not divide n
+static void ppo_fit_launch(rs_ppo *p, const void *obs, const int32_t *act, const float *logp, const float *adv, const float *ret, int n,
+                           const int32_t *perm, int epochs, int minibatch, float *loss_out, hipStream_t st) {
+    for (int e = 0; e < epochs; ++e)
+        for (int i = 0; i < n; i += minibatch) {
+            const int B = n - i < minibatch ? n - i : minibatch;
+            ppo_grad_launch(p, PpoBatch{(const __half *)obs, act, logp, adv, ret, perm + (size_t)e * n + i, B}, loss_out, st);
+            ppo_step_launch(p, st);
+        }
+}
+
 extern "C" int rs_ppo_fit(rs_ppo_handle p, const void *obs, const int32_t *act, const float *logp, const float *adv, const float *ret, int32_t n,
                           const int32_t *perm, int32_t epochs, int32_t minibatch, float *loss_out, void *stream) {
     if (!p) { g_create_err = "rs_ppo_fit: NULL handle"; return RS_EINVAL; }
@@ -959,12 +973,19 @@ extern "C" int rs_ppo_fit(rs_ppo_handle p, const void *obs, const int32_t *act, 
         g_create_err = "rs_ppo_fit: need 1 <= n, 1 <= epochs, 1 <= minibatch <= max_minibatch of rs_ppo_create"; return RS_EINVAL;
     }
     if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    for (int e = 0; e < epochs; ++e)
-        for (int i = 0; i < n; i += minibatch) {
-            const int B = n - i < minibatch ? n - i : minibatch;
-            ppo_grad_launch(p, PpoBatch{(const __half *)obs, act, logp, adv, ret, perm + (size_t)e * n + i, B}, loss_out, (hipStream_t)stream);
-            ppo_step_launch(p, (hipStream_t)stream);
-        }
+    ppo_fit_launch(p, obs, act, logp, adv, ret, n, perm, epochs, minibatch, loss_out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+// ---- the shuffle of an update (resco_ppo_loop.h): one launch, every element by its own thread
+static void ppo_perm_launch(int32_t n, int32_t epochs, uint32_t seed, uint32_t key, int32_t *perm, hipStream_t st) {
+    const int64_t blocks = ((int64_t)n + 255) / 256;
+    hipLaunchKernelGGL(rs_ppo_perm_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536), epochs), dim3(256), 0, st, seed, key, n, perm);
+}
+extern "C" int rs_ppo_perm(int32_t n, int32_t epochs, uint32_t seed, uint32_t update_key, int32_t *perm, void *stream) {
+    if (n < 1 || epochs < 1 || epochs > 65535) { g_create_err = "rs_ppo_perm: need 1 <= n and 1 <= epochs <= 65535"; return RS_EINVAL; }
+    if (!perm) { g_create_err = "rs_ppo_perm: perm is NULL"; return RS_EINVAL; }
+    ppo_perm_launch(n, epochs, seed, update_key, perm, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
 }
 
@@ -1363,6 +1384,27 @@ rs_rollout_record_kernel(const float *__restrict__ rew_src, float *__restrict__ 
     }
 }
 
+// One recorded env-step of one handle into slot t of its segment, on st.  first: the observation the policy is about to see is not
+// in slot t yet (the step before did not record it); next: the observation after the step goes into slot t + 1.
+static int rollout_step_launch(rs_sim *h, const rs_rollout &R, const rs_policy *pol, uint32_t seed, uint32_t key, int t_slot, bool first, bool next,
+                               hipStream_t st) {
+    const size_t ns = (size_t)h->n_envs * h->K.n_signals, no = ns * h->K.lmax * 5, t = (size_t)t_slot;
+    const uint16_t *obs = h->O.drq_f16();
+    uint16_t *obs_t = (uint16_t *)R.obs + t * no;
+    const int vec = (((uintptr_t)obs | (uintptr_t)obs_t | (no * 2)) & 15) == 0;      // (no * 2: the next slot is aligned as well)
+    const size_t items = vec ? (no / 8 > ns ? no / 8 : ns) : no;
+    const int grid = (int)((items + 255) / 256);
+    if (first) hipLaunchKernelGGL(rs_rollout_record_kernel, dim3(grid), dim3(256), 0, st, nullptr, nullptr, 0, obs, obs_t, (int)no, vec);
+    ippo_launch(pol->W, obs, h->n_envs, h->P.env_base, seed, key, nullptr, h->actions, R.act + t * ns, R.logp + t * ns, R.value + t * ns, nullptr, st);
+    HIPCHK(h, hipGetLastError());
+    const int rc = launch_step(h, st, h->K.step_length * h->ratio, 1);
+    if (rc != RS_OK) return rc;
+    hipLaunchKernelGGL(rs_rollout_record_kernel, dim3(grid), dim3(256), 0, st, (const float *)h->O.wait_norm(), R.rew + t * ns, (int)ns,
+                       next ? obs : nullptr, obs_t + no, (int)no, vec);
+    HIPCHK(h, hipGetLastError());
+    return RS_OK;
+}
+
 extern "C" int rs_group_rollout(const rs_handle *hs, int32_t n_handles, const rs_group_agent *agent, const rs_rollout *segs, int32_t t0, int32_t n_steps) {
     if (!hs || n_handles <= 0 || n_steps <= 0 || t0 < 0 || !segs) return RS_EINVAL;
     for (int i = 0; i < n_handles; ++i) {
@@ -1379,26 +1421,9 @@ extern "C" int rs_group_rollout(const rs_handle *hs, int32_t n_handles, const rs
     }
     for (int k = 0; k < n_steps; ++k)
         for (int i = 0; i < n_handles; ++i) {
-            rs_sim *h = hs[i];
-            const rs_rollout &R = segs[i];
             hipStream_t st;
-            if (int rc = enter(h, nullptr, &st)) return rc;
-            const size_t ns = (size_t)h->n_envs * h->K.n_signals, no = ns * h->K.lmax * 5, t = (size_t)(t0 + k);
-            const uint16_t *obs = h->O.drq_f16();
-            uint16_t *obs_t = (uint16_t *)R.obs + t * no;
-            const int vec = (((uintptr_t)obs | (uintptr_t)obs_t | (no * 2)) & 15) == 0;      // (no * 2: the next slot is aligned as well)
-            const size_t items = vec ? (no / 8 > ns ? no / 8 : ns) : no;
-            const int grid = (int)((items + 255) / 256);
-            if (k == 0) hipLaunchKernelGGL(rs_rollout_record_kernel, dim3(grid), dim3(256), 0, st, nullptr, nullptr, 0, obs, obs_t, (int)no, vec);
-            ippo_launch(agent->policy->W, obs, h->n_envs, h->P.env_base, agent->seed, agent->step_key + (uint32_t)k, nullptr, h->actions,
-                        R.act + t * ns, R.logp + t * ns, R.value + t * ns, nullptr, st);
-            HIPCHK(h, hipGetLastError());
-            const int rc = launch_step(h, st, h->K.step_length * h->ratio, 1);
-            if (rc != RS_OK) return rc;
-            const bool next = k + 1 < n_steps;
-            hipLaunchKernelGGL(rs_rollout_record_kernel, dim3(grid), dim3(256), 0, st, (const float *)h->O.wait_norm(), R.rew + t * ns, (int)ns,
-                               next ? obs : nullptr, obs_t + no, (int)no, vec);
-            HIPCHK(h, hipGetLastError());
+            if (int rc = enter(hs[i], nullptr, &st)) return rc;
+            if (int rc = rollout_step_launch(hs[i], segs[i], agent->policy, agent->seed, agent->step_key + (uint32_t)k, t0 + k, k == 0, k + 1 < n_steps, st)) return rc;
         }
     return RS_OK;
 }
@@ -1580,6 +1605,80 @@ extern "C" int rs_group_train(const rs_handle *hs, int32_t n_handles, const rs_t
             }
         }
         if (P.sync || P.update) HIPCHK(h0, hipGetLastError());
+    }
+    return RS_OK;
+}
+
+// ---- rs_ippo_pack_weights: the actor-critic pack (resco_group_train.h: gt_pack_unit_value), one launch
+static void ippo_pack_launch(const rs_policy *p, const PptTensors &par, hipStream_t st) {
+    const GtPackValue P{{par.p[PT_FC1_W], par.p[PT_FC2_W], par.p[PT_FC3_W], par.p[PT_FC3_B], (uint16_t *)p->W.w1, (uint16_t *)p->W.w2, (uint16_t *)p->W.w3,
+                         (float *)p->W.b3, p->W.lmax, p->amax}, par.p[PT_V_W], par.p[PT_V_B]};
+    hipLaunchKernelGGL(rs_ippo_pack_kernel, dim3((gt_pack_units(p->W.lmax) + 255) / 256, p->W.S), dim3(256), 0, st, P);
+}
+extern "C" int rs_ippo_pack_weights(rs_policy_handle p, const rs_ppo_tensors *params, void *stream) {
+    if (const char *why = idqn_pack_refusal(p)) { g_create_err = std::string("rs_ippo_pack_weights: ") + why; return RS_EINVAL; }
+    if (!params || !params->fc1_w || !params->fc2_w || !params->fc3_w || !params->fc3_b || !params->v_w || !params->v_b) {
+        g_create_err = "rs_ippo_pack_weights: a parameter pointer is NULL"; return RS_EINVAL;
+    }
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    ippo_pack_launch(p, train_tensors(params, PPT_NT), (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+// ---- rs_group_ppo_train: the --device-update loop of tools/ippo_train.py, n_steps iterations enqueued by one call (include/resco_sim.h).
+// Everything goes to the legacy stream, in the tool's order: per step the recorded env-step of rs_group_rollout (with the done bytes of
+// the slots ahead written once per segment and call); after the step that fills the last slot the bootstrap value, GAE, the shuffle, the
+// update's launches and the pack.  No stream, event, wait or asynchronous memcpy is made here.
+extern "C" int rs_group_ppo_train(const rs_handle *hs, int32_t n_handles, const rs_ppo_train *tr, int32_t n_steps) {
+    if (!hs || n_handles < 1 || !hs[0]) { g_create_err = "rs_group_ppo_train: NULL handles"; return RS_EINVAL; }
+    rs_sim *h = hs[0];
+    auto refuse = [&](const std::string &why) { h->err = "rs_group_ppo_train: " + why; g_create_err = h->err; return RS_EINVAL; };
+    if (n_handles != 1) return refuse("one handle only: a segment has no row stride, and pipes in training were measured below one handle");
+    if (!tr) return refuse("NULL arguments");
+    if (n_steps < 1) return refuse("need n_steps >= 1");
+    const rs_rollout &R = tr->seg;
+    const int T = R.T;
+    if (T < 1 || (long long)T * h->n_envs < 1 || (long long)T * h->n_envs > 0x7FFFFFFFll) return refuse("need 1 <= T * n_envs < 2^31 rows in the segment");
+    if (tr->slot0 < 0 || tr->slot0 > T - 1) return refuse("slot0 must be one of the segment's slots, 0 .. T - 1");
+    if (tr->done_step < -1 || tr->done_step > n_steps - 1) return refuse("done_step must be -1 (no episode ends in this call) or a step of this call, 0 .. n_steps - 1");
+    if (tr->t0 < 0 || tr->update0 < 0) return refuse("need t0 >= 0 and update0 >= 0");
+    if (tr->epochs < 1 || tr->epochs > 65535) return refuse("need 1 <= epochs <= 65535");
+    if (!tr->policy || !tr->learner) return refuse("the policy or the learner handle is NULL");
+    if (!R.obs || !R.act || !R.logp || !R.value || !R.rew || !tr->done || !tr->last_value || !tr->adv || !tr->ret || !tr->gae_scratch || !tr->perm)
+        return refuse("a buffer pointer is NULL (segment, done, last_value, adv, ret, gae_scratch, perm)");
+    rs_policy *pol = tr->policy;
+    rs_ppo *pp = tr->learner;
+    const int S = h->K.n_signals, N = h->n_envs;
+    if (pol->kind != POLICY_IDQN || pol->W.S != S || pol->W.lmax != h->K.lmax) return refuse("needs an rs_idqn_create policy built for this scenario (n_signals, lmax)");
+    if (pp->T.S != S || pp->T.lmax != h->K.lmax || pp->T.amax != pol->amax) return refuse("the learner does not fit the policy and the scenario (n_signals, lmax, amax)");
+    if (const char *why = idqn_pack_refusal(pol)) return refuse(why);
+    if (pol->device != h->device) return refuse("the policy's weights live on another device than the handle");
+    if (pp->device != h->device) return refuse("the learner lives on another device than the handle");
+    if (tr->minibatch < 1 || tr->minibatch > pp->max_batch) return refuse("need 1 <= minibatch <= max_minibatch of rs_ppo_create");
+    if (!h->blocking) return refuse("this handle's stream is a non-blocking stream (RESCO_PLAIN_STREAMS, or hipExtStreamCreateWithCUMask failed at rs_create): "
+                                    "nothing would order its other launches with this loop's on the legacy stream");
+    if (h->timing) return refuse("rs_timing is enabled on this handle: its events are not part of this loop");
+    if (!(h->out_mask & OUT_DRQ_F16)) return refuse("RS_AGENT_IPPO reads RS_BUF_DRQ_NORM_F16, which rs_set_outputs has switched off");
+
+    const GpLoop L{T, tr->slot0, tr->done_step, tr->t0, tr->update0};
+    const int n = T * N;
+    for (int k = 0; k < n_steps; ++k) {
+        const GpStep P = gp_plan(L, k);
+        hipStream_t st;
+        if (int rc = enter(h, (void *)hipStreamLegacy, &st)) return rc;
+        const bool first = k == 0 || P.slot == 0, next = k + 1 < n_steps && P.slot + 1 < T;
+        if (first) {        // the done bytes of the slots this call fills from here to the segment's end
+            const int m = T - P.slot < n_steps - k ? T - P.slot : n_steps - k;
+            hipLaunchKernelGGL(rs_ppo_done_kernel, dim3((m + 255) / 256), dim3(256), 0, st, tr->done + P.slot, m, tr->done_step - k);
+        }
+        if (int rc = rollout_step_launch(h, R, pol, tr->policy_seed, P.key, P.slot, first, next, st)) return rc;
+        if (!P.update) continue;
+        ippo_launch(pol->W, h->O.drq_f16(), N, 0, tr->policy_seed, 0u, nullptr, nullptr, nullptr, nullptr, tr->last_value, nullptr, st);
+        gae_launch(PpoArgs{R.rew, R.value, tr->last_value, tr->done, T, N, S, tr->gamma, tr->lambda, tr->adv, tr->ret, (float *)tr->gae_scratch}, st);
+        ppo_perm_launch(n, tr->epochs, tr->learner_seed, P.update_key, tr->perm, st);
+        ppo_fit_launch(pp, R.obs, R.act, R.logp, tr->adv, tr->ret, n, tr->perm, tr->epochs, tr->minibatch, tr->loss_out, st);
+        ippo_pack_launch(pol, pp->T.par, st);
+        HIPCHK(h, hipGetLastError());
     }
     return RS_OK;
 }

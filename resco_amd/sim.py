@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from ._abi import ParamsStruct, TrainStruct, pack_scenario
+from ._abi import ParamsStruct, PPOTrainStruct, RolloutStruct, TrainStruct, pack_scenario
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RESCO_SIM_LIB: another build of the same HIP library (A/B variants compiled with different -D switches, tools/ab.py)
@@ -38,7 +38,8 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_dqn_create', 'rs_dqn_sample', 'rs_dqn_grad', 'rs_dqn_step', 'rs_dqn_update', 'rs_dqn_steps', 'rs_dqn_destroy',
                'rs_mplight_dqn_create', 'rs_mplight_dqn_sample', 'rs_mplight_dqn_grad', 'rs_mplight_dqn_step', 'rs_mplight_dqn_update',
                'rs_mplight_dqn_steps', 'rs_mplight_dqn_destroy',
-               'rs_idqn_pack_weights', 'rs_dqn_sync_target', 'rs_mplight_dqn_sync_target', 'rs_group_train']
+               'rs_idqn_pack_weights', 'rs_dqn_sync_target', 'rs_mplight_dqn_sync_target', 'rs_group_train',
+               'rs_ppo_perm', 'rs_ippo_pack_weights', 'rs_group_ppo_train']
 
 _lib = None
 
@@ -124,6 +125,10 @@ def bind(L):
         L.rs_dqn_sync_target.argtypes = [vp, vp]
         L.rs_mplight_dqn_sync_target.argtypes = [vp, vp]
         L.rs_group_train.argtypes = [vp, i32, vp, i32]
+    if hasattr(L, 'rs_group_ppo_train'):
+        L.rs_ppo_perm.argtypes = [i32, i32, u32, u32, vp, vp]
+        L.rs_ippo_pack_weights.argtypes = [vp, vp, vp]
+        L.rs_group_ppo_train.argtypes = [vp, i32, vp, i32]
     if hasattr(L, 'rs_default_block'):      # (the host emulation of the CPU tests exports only what it implements)
         L.rs_default_block.argtypes = [i32, i32, i32]
         L.rs_default_block.restype = i32
@@ -159,9 +164,7 @@ class GroupAgent(C.Structure):
                 ('epsilon', C.c_float), ('epsilon_step', C.c_float), ('seed', C.c_uint32)]
 
 
-class Rollout(C.Structure):
-    """ctypes mirror of rs_rollout (include/resco_sim.h): the device buffers of one handle's trajectory segment"""
-    _fields_ = [('obs', C.c_void_p), ('act', C.c_void_p), ('logp', C.c_void_p), ('value', C.c_void_p), ('rew', C.c_void_p), ('T', C.c_int32)]
+Rollout = RolloutStruct     # ctypes mirror of rs_rollout (include/resco_sim.h): the device buffers of one handle's trajectory segment
 
 
 PPO_TENSORS = ('conv_w', 'conv_b', 'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b', 'fc3_w', 'fc3_b', 'v_w', 'v_b')
@@ -254,6 +257,23 @@ class SimGroup:
         if rc != 0:
             msgs = [m.decode() for m in [self._lib.rs_last_error(s._h) for s in self.sims] + [self._lib.rs_last_error(None)] if m]
             raise RuntimeError('rs_group_train failed (%d): %s' % (rc, '; '.join(dict.fromkeys(msgs))))
+
+    def ppo_train(self, n_steps, policy, learner, seg, done, last_value, adv, ret, gae_scratch, perm, t0, update0, slot0, done_step=-1, epochs=4,
+                  minibatch=256, gamma=0.99, lambd=0.95, policy_seed=0, learner_seed=0, loss_out=None):
+        """rs_group_ppo_train: n_steps iterations of the --device-update loop of tools/ippo_train.py (recorded env-steps; after the
+        step that fills the segment's last slot the bootstrap value, GAE, the shuffle, the PPO update and the actor-critic re-pack),
+        all on the legacy default stream, enqueued by one call.  A group of ONE handle.  policy / learner: the library handles
+        (FusedIPPO.handle, the FusedPPOLearner's); seg: the handle's Rollout; the others: device pointers; the position (t0, update0,
+        slot0) BEFORE the call.  Nothing is advanced on the Python side: agents/train_fused.py: DevicePPOTrainer does that."""
+        if not hasattr(self._lib, 'rs_group_ppo_train'):
+            raise RuntimeError('the loaded library has no rs_group_ppo_train: rebuild it (there is no CPU fallback)')
+        t = PPOTrainStruct(policy, learner, seg, done, last_value, adv, ret, gae_scratch, perm, loss_out, int(t0), int(update0), int(slot0),
+                           int(done_step), int(epochs), int(minibatch), float(gamma), float(lambd), int(policy_seed) & 0xFFFFFFFF,
+                           int(learner_seed) & 0xFFFFFFFF)
+        rc = self._lib.rs_group_ppo_train(self._hs, len(self.sims), C.byref(t), int(n_steps))
+        if rc != 0:
+            msgs = [m.decode() for m in [self._lib.rs_last_error(s._h) for s in self.sims] + [self._lib.rs_last_error(None)] if m]
+            raise RuntimeError('rs_group_ppo_train failed (%d): %s' % (rc, '; '.join(dict.fromkeys(msgs))))
 
     def sync(self):
         for s in self.sims:

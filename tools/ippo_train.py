@@ -2,7 +2,7 @@
 """IPPO training loop on the GPU: HIP simulator -> fp16 observations -> fused HIP policy kernel in sampling mode
 (rs_idqn_act, mode 1) -> rollout segment in HBM -> batched PPO update (PyTorch) -> weights re-packed on the device.
 
-    python tools/ippo_train.py [--device-rollout] [--device-update] [map] [n_envs] [episodes] [segment_steps] [minibatches_per_epoch]
+    python tools/ippo_train.py [--device-rollout] [--device-update] [--device-shuffle] [--device-loop] [map] [n_envs] [episodes] [segment_steps] [minibatches_per_epoch]
 
 --device-rollout: the segment is recorded on the device by the group path (rs_group_rollout: actor-critic kernel, step kernel and
 recorder, `segment_steps` env-steps per call through the ABI), the update takes logp / value from the recording and GAE from the
@@ -11,6 +11,11 @@ fused kernel (BatchedPPOLearner.update_from_rollout) -- no Python work per env-s
 --device-update (implies --device-rollout): the PPO update itself runs on the device too (FusedPPOLearner: loss, backward,
 per-signal clipping and Adam in HIP kernels, rs_ppo_fit -- one call through the ABI per update instead of ~200 launches per Adam
 step).
+
+--device-loop: the loop itself runs in the library (agents/train_fused.py: DevicePPOTrainer, rs_group_ppo_train): rollout, bootstrap
+value, GAE, shuffle, update and re-pack of a whole episode are ONE call through the ABI; the shuffles are the learner's counter-hash
+permutations (FusedPPOLearner.device_perm) instead of torch.randperm's.  --device-shuffle (implies --device-update) is the same loop
+driven from Python, shuffle included, and gives the same bits.  Opt-in.
 
 Prints one JSON line per episode (average trip delay as utils/readXML.py computes it, env-steps/s including
 learning).  The reference's IPPO learns far more slowly than its IDQN (1400 published episodes); this tool shows the
@@ -28,6 +33,7 @@ from resco_amd.agents.idqn_fused import FusedIDQN                   # noqa: E402
 from resco_amd.agents.ippo import BatchedIPPO, BatchedPPOLearner      # noqa: E402
 from resco_amd.agents.ippo_fused import DeviceRollout, FusedIPPO      # noqa: E402
 from resco_amd.agents.ippo_learn_fused import FusedPPOLearner         # noqa: E402
+from resco_amd.agents.train_fused import DevicePPOTrainer             # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                     # noqa: E402
 from resco_amd.sim import SimGroup                                    # noqa: E402
 
@@ -38,7 +44,7 @@ def report(env, learner, ep, n, steps, dt):
                           env_steps_per_s=round(n * steps / dt), ms_per_step=round(dt / steps * 1e3, 3))), flush=True)
 
 
-def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, device_update=False):
+def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, device_update=False, device_shuffle=False):
     env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0)
     steps = env.horizon_steps
     net = BatchedIPPO.from_scenario(env.scenario, dtype=torch.float32, device='cuda')
@@ -50,7 +56,7 @@ def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, 
     obs = env.tensor('drq_norm_f16')
     done = [False] * seg
     gen = torch.Generator(device='cuda').manual_seed(0)
-    t_global, i = 0, 0
+    t_global, i, updates = 0, 0, 0
     for ep in range(episodes):
         env.sim.set_seed(1000 + ep)
         env.reset()
@@ -64,7 +70,9 @@ def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, 
             done[i - 1] = env.advance(m)
             if i == seg:
                 grp.sync()
-                learner.update_from_rollout(rec, policy.value(obs), torch.as_tensor(done, device='cuda'), generator=gen)
+                kw = dict(perm=learner.device_perm(seg * n, updates)) if device_shuffle else dict(generator=gen)
+                learner.update_from_rollout(rec, policy.value(obs), torch.as_tensor(done, device='cuda'), **kw)
+                updates += 1
                 policy.refresh_on_device()
                 torch.cuda.current_stream().synchronize()       # the next rollout reads the re-packed weights on another stream
                 done, i = [False] * seg, 0
@@ -72,6 +80,27 @@ def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, 
         torch.cuda.synchronize()
         report(env, learner, ep, n, steps, time.perf_counter() - t0)
     env.close()
+
+
+def main_device_loop(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
+    env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0)
+    steps = env.horizon_steps
+    net = BatchedIPPO.from_scenario(env.scenario, dtype=torch.float32, device='cuda')
+    net.init_like_reference(seed=0)
+    learner = FusedPPOLearner(net, minibatch=max(256, seg * n // mbs))
+    policy = FusedIPPO(net, seed=3)
+    policy.refresh_on_device()
+    trainer = DevicePPOTrainer(env, learner, policy, DeviceRollout(seg, [env.sim]))
+    for ep in range(episodes):
+        env.sim.set_seed(1000 + ep)
+        env.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        assert trainer.run(steps)               # the whole episode; a segment may span the reset
+        torch.cuda.synchronize()
+        report(env, learner, ep, n, steps, time.perf_counter() - t0)
+    env.close()
+    return trainer
 
 
 def main(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
@@ -114,9 +143,11 @@ def main(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
 
 
 if __name__ == '__main__':
-    flags = ('--device-rollout', '--device-update')
+    flags = ('--device-rollout', '--device-update', '--device-shuffle', '--device-loop')
     a = [x for x in sys.argv[1:] if x not in flags]
-    run = main_device_rollout if any(f in sys.argv[1:] for f in flags) else main
-    kw = dict(device_update=True) if '--device-update' in sys.argv[1:] else {}
+    run = main_device_loop if '--device-loop' in sys.argv[1:] else (main_device_rollout if any(f in sys.argv[1:] for f in flags) else main)
+    kw = dict(device_update=True) if '--device-update' in sys.argv[1:] and run is main_device_rollout else {}
+    if '--device-shuffle' in sys.argv[1:] and run is main_device_rollout:       # (--device-update with the library loop's shuffles)
+        kw = dict(device_update=True, device_shuffle=True)
     run(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 20,
         int(a[3]) if len(a) > 3 else 30, int(a[4]) if len(a) > 4 else 4, **kw)
