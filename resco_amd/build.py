@@ -46,5 +46,20 @@ def build_check_library(force=False):
     return CHECK_LIB
 
 
+FIELDLOADS_LIB = os.path.join(HERE, 'csrc', 'libresco_sim_fieldloads.so')
+
+
+def build_fieldloads_library(force=False):
+    """The FIELD-LOADS build: -DRS_FIELD_LOADS turns the whole-record loads of the table records (resco_tables.h: rec_load16, link_load,
+    rec_load8) back into plain struct copies, which the compiler reads field by field -- the step kernel as it was before the helpers,
+    instruction for instruction.  One capacity (256 slots) so that it compiles in seconds.  The other side of
+    tests/test_gpu_record_loads.py (both builds must give the same bits) -- never loaded by the package.  Rebuilt when a source is
+    newer than it, or with force=True."""
+    if not force and os.path.exists(FIELDLOADS_LIB) and all(os.path.getmtime(FIELDLOADS_LIB) >= os.path.getmtime(d) for d in _DEPS):
+        return FIELDLOADS_LIB
+    subprocess.check_call([HIPCC] + FLAGS + ['-DRS_FIELD_LOADS', '-DRS_ONE_CAP=256', SRC, '-o', FIELDLOADS_LIB])
+    return FIELDLOADS_LIB
+
+
 if __name__ == '__main__':
     print(build_library(force=True, verbose=True))

@@ -91,6 +91,7 @@ __device__ __forceinline__ float rs_div_unscaled(float a, float b) {
 #define RS_OPAQUE_S(x) asm volatile("" : "+s"(x));
 #ifndef RS_NARROW_NODE
 #define RS_KEEP4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+#define RS_KEEP2(a, b) asm volatile("" : "+v"(a), "+v"(b));       // (the 8-byte table records: resco_tables.h, rec_load8)
 #endif
 extern __shared__ __attribute__((aligned(16))) char rs_smem[];      // THE working memory of a workgroup (dynamic LDS)
 #define RS_SMEM rs_smem

@@ -617,7 +617,7 @@ RS_DEV uint16_t cache_link(const KTab &T, const LaneRec &LR, int lane, int rq, i
 }
 template <class LT> RS_DEV bool foe_blocked(const KTab &T, const LT &L, const Grid &grid, const LinkRec &K) {
     for (int i = K.foe_start; i < K.foe_start + K.foe_cnt; ++i) {
-        const FoeRec F = T.foes()[i];
+        const FoeRec F = rec_load16(T.foes(), i);
         if (F.tls != 0xFF && tls_state(T, L, F.tls, F.tls_pos) == TLS_R) continue;
         if (F.arr_idx >= 0 && L.arr[F.arr_idx] < RM_FOE_GAP_Q) return true;
         if (F.via1_cell0 != 0xFFFF && cells_have_mover(grid, F.via1_cell0, F.via1_nc)) return true;   // a moving vehicle on
@@ -838,7 +838,7 @@ template <bool LONG, class LT> RS_DEV void phase_plan(const KTab &T, const LT &L
     const float a = vt[VT_ACCEL], b = vt[VT_DECEL], tau = vt[VT_TAU], mingap = vt[VT_MINGAP];
     const float v = me.speed, x = me.pos;
     const float sf = sf_of(me.sfq);
-    const LaneRec LR0 = T.lanes()[lane];
+    const LaneRec LR0 = rec_load16(T.lanes(), lane);
     LaneRec LR = LR0;
     float vsafe = RM_BIGF;
     // The look-ahead only FINDS what limits the vehicle (a leader, or a stop line = a standing leader of zero length):
@@ -886,7 +886,7 @@ template <bool LONG, class LT> RS_DEV void phase_plan(const KTab &T, const LT &L
                 if (!cur_int && T.rsteps()[rq].next_edge == 0xFFFF) break;
                 stop_here = true;
             } else {
-                K = T.links()[link];
+                K = link_load(T.links(), link);
                 const int st = tls_state(T, L, K.tls, K.tls_pos);
                 if (K.tls != 0xFF && (st == TLS_R || st == TLS_Y) && seen >= bgv) stop_here = true;
                 if (!stop_here && !(K.flags & KF_CONT) && ((K.flags & KF_MINOR) || (K.tls != 0xFF && st == TLS_g))) {
@@ -969,13 +969,20 @@ template <bool LONG, class LT> RS_DEV void phase_move(const KTab &T, const LT &L
         moved_at[s] = t + 1;
     }
 #endif
-    LaneRec LR = T.lanes()[lane];
+#ifdef RS_FIELD_LOADS       // (the field-loads build keeps the order its kernels were compiled from)
+    LaneRec LR = rec_load16(T.lanes(), lane);
+#endif
     // what the end of the move needs from the tables is requested now (the common case: the vehicle stays on its lane)
     uint32_t nb = T.notbest()[ax.rq];       // (which lanes of my route step are not its best ones: what classify() needs of the continuation row)
     uint32_t kw = 0;
     if (more && (ax.nlink & NLINK_ARR)) kw = link_reg_word(T, ax.nlink);
     const float sfv = sf_of(me.sfq);
     float tl = G.tloss()[eo + s];
+    // (the lane record LAST: rec_load16 ends in the wait for its four dwords, and the loads above are in flight by then -- requested
+    //  after it they would start only when the record has arrived, a second round trip on the short path of every vehicle)
+#ifndef RS_FIELD_LOADS
+    LaneRec LR = rec_load16(T.lanes(), lane);
+#endif
     const int sw = ax.swait;
     int swn = sw;
     const float vn = L.vnx[s];
@@ -993,7 +1000,7 @@ template <bool LONG, class LT> RS_DEV void phase_move(const KTab &T, const LT &L
     }
     if (LONG && side) {
         lane += side;
-        LR = T.lanes()[lane];
+        LR = rec_load16(T.lanes(), lane);
         nlink = cache_link(T, LR, lane, rq, k);
         link = (int)(nlink & 0x7FFF);
         relink = true;
@@ -1018,7 +1025,7 @@ template <bool LONG, class LT> RS_DEV void phase_move(const KTab &T, const LT &L
         x -= LR.len;
         if (!li) rq += 1;
         {
-            const LinkRec Km = T.links()[link];
+            const LinkRec Km = link_load(T.links(), link);
             lane = Km.to_lane;
             LR = Km.dest;
         }
@@ -1081,8 +1088,13 @@ template <class LT> RS_DEV int overlapping(const LT &L, const Grid &grid, int ce
 template <class LT> RS_DEV int phase_lc_decide(const KTab &T, const LT &L, const Grid &grid, const State &G, size_t eo, int t, int s, const Aux &ax, const Node &me) {
     const int lane = ax.lane;
     // (everything the decision may need from global memory is requested at once)
-    const LaneRec LR = T.lanes()[lane];
+#ifdef RS_FIELD_LOADS
+    const LaneRec LR = rec_load16(T.lanes(), lane);
     const ContRow R = cont_row(T, ax.rq);
+#else
+    const ContRow R = cont_row(T, ax.rq);
+    const LaneRec LR = rec_load16(T.lanes(), lane);     // (after the row: the record's wait covers both, see phase_move)
+#endif
     const int my_wait = (int)ax.swait;
     const int n = LR.flags >> 2;
     if ((LR.flags & LF_INTERNAL) || n < 2) return 0;
@@ -1178,7 +1190,7 @@ template <class LT> RS_DEV bool phase_insert_decide(const KTab &T, const LT &L, 
     if ((int)L.dep_t[d] > t) return false;           // nothing due on this lane (the common case: no global access)
     const int k = L.dep[d];
     // (one 8-byte record per departure lane instead of lane id -> lane record: the two loads of this check are independent)
-    const DepInfo LR = T.cold.dep_info[d];
+    const DepInfo LR = rec_load8(T.cold.dep_info, d);
     const float *vt = L.vtp + T.trip_vtype()[k] * VT_COLS;
     const float mypos = vt[VT_LENGTH] < LR.len ? vt[VT_LENGTH] : LR.len;
     // only vehicles with pos - length < mypos + minGap can be in the way
@@ -1266,7 +1278,7 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
             if (ln == LANE_NONE) { L.aux[s] = ax; L.node[s].trip = TRIP_NONE; continue; }
             const float sp = G.speed()[eo + s], x = G.pos()[eo + s];
             const int rq = (int)T.routes()[T.trip_route()[tr]].start + (int)G.cursor()[eo + s];
-            const LaneRec LR0 = T.lanes()[ln];
+            const LaneRec LR0 = rec_load16(T.lanes(), ln);
             ax.rq = (uint16_t)rq;
             ax.nlink = cache_link(T, LR0, ln, rq, tr);
             ax.swait = G.swait()[eo + s];
@@ -1426,8 +1438,8 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
                         const int k = L.dep[d];
                         const int v = T.trip_vtype()[k];
                         const float *vt = L.vtp + v * VT_COLS;
-                        const RouteRec RR = T.routes()[T.trip_route()[k]];
-                        const LaneRec LRd = T.lanes()[RR.depart_lane];
+                        const RouteRec RR = rec_load16(T.routes(), T.trip_route()[k]);
+                        const LaneRec LRd = rec_load16(T.lanes(), RR.depart_lane);
                         const int sfq = speed_factor_q(P, genv, k, vt);
                         const float sfn = sf_of(sfq);
                         Node nn; nn.pos = vt[VT_LENGTH] < RR.depart_len ? vt[VT_LENGTH] : RR.depart_len;
@@ -1494,7 +1506,7 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
             G.cursor()[eo + s] = (uint16_t)(rq - (int)T.routes()[T.trip_route()[L.node[s].trip]].start);
             if (!obs) continue;
             const int prev_owner = G.owner()[eo + s];
-            const LaneRec LR = T.lanes()[lane];
+            const LaneRec LR = T.lanes()[lane];         // (only its length is used: one dword)
             const int oi = T.cold.lane_obs[lane];
             bool detect = false;
             if (oi >= 0) {

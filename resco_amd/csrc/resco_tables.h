@@ -48,7 +48,10 @@ enum { ST_INSERTED, ST_ARRIVED, ST_DURATION, ST_DEPDELAY, ST_WAITING, ST_TLOSS, 
 #define RS_LDS_3WG_LIMIT 53760
 #define RS_LDS_4WG_LIMIT 40960
 
-// ---- 16-byte records: one global_load_dwordx4 fetches everything about a lane / foe / route
+// ---- 16-byte records: everything about a lane / foe / route in one aligned 16-byte block.  A plain struct copy does NOT fetch it
+// with one global_load_dwordx4 -- the compiler narrows the copy to the fields that are used, one load each, and sinks some of them
+// behind the first wait --: the per-vehicle gathers of the step kernel read the records through rec_load16 / link_load below
+// (tools/isa_loads.py counts what the ISA holds; profiles/r15_record_loads_isa.txt)
 struct __attribute__((aligned(16))) LaneRec {
     float len, vmax;
     uint16_t link_start;
@@ -89,7 +92,7 @@ struct __attribute__((aligned(16))) RouteRec {
 #define NLINK_NONE 0x7FFF       // L.nlink value: link index (0x7FFF none), bit 15 = the link owns an approach register
 #define NLINK_ARR 0x8000
 
-struct DepInfo { float len; uint16_t cell0, lane; };
+struct __attribute__((aligned(8))) DepInfo { float len; uint16_t cell0, lane; };
 // tables used rarely (per signal, per departure lane, at load / observe): reached through one pointer
 struct KCold {
     const int32_t *trip_depart;
@@ -115,6 +118,63 @@ struct KCold {
 #ifndef RS_MEM
 #define RS_MEM inline
 #endif
+// ---- a table record with ONE round trip to global memory.  Left to itself the compiler reads a record field by field, each load as
+// narrow as the field (nine loads for a LinkRec), and sinks a field's load into the branch that uses it, behind the wait that ends the
+// others: a second dependent round trip for a record it has already touched.  The helpers copy the whole record as dwords and declare
+// all of them used (RS_KEEP4: an empty asm in the device build, nothing on the host), so that the read is one global_load_dwordx4 per
+// 16 bytes (dwordx2 for the 8-byte records), issued together; the fields are then taken out of registers.  They read exactly
+// sizeof(record) bytes.  -DRS_FIELD_LOADS: plain struct copies, what the compiler made of the tables before the helpers existed (the
+// A/B's other side, libresco_sim_fieldloads.so).
+#ifndef RS_KEEP4
+#define RS_KEEP4(a, b, c, d)
+#endif
+#ifndef RS_KEEP2
+#define RS_KEEP2(a, b)
+#endif
+static_assert(sizeof(LaneRec) == 16 && alignof(LaneRec) == 16, "LaneRec: one 16-byte load");
+static_assert(sizeof(FoeRec) == 16 && alignof(FoeRec) == 16, "FoeRec: one 16-byte load");
+static_assert(sizeof(RouteRec) == 16 && alignof(RouteRec) == 16, "RouteRec: one 16-byte load");
+static_assert(sizeof(LinkRec) == 32 && alignof(LinkRec) == 16, "LinkRec: two 16-byte loads");
+static_assert(sizeof(RStep) == 8 && alignof(RStep) == 8, "RStep: one 8-byte load");
+static_assert(sizeof(DepInfo) == 8 && alignof(DepInfo) == 8, "DepInfo: one 8-byte load");
+#ifdef RS_FIELD_LOADS
+// (macros, not functions: the very expressions the phases held before the helpers, so that this build's step kernels equal the earlier
+//  ones instruction for instruction -- an inline function that returns tab[i] changes the register allocation of the kernel)
+#define rec_load16(tab, i) ((tab)[i])
+#define rec_load8(tab, i) ((tab)[i])
+#define link_load(tab, i) ((tab)[i])
+#else
+struct alignas(16) RecRaw16 { uint32_t a, b, c, d; };
+template <class R, class I> RS_MEM R rec_load16(const R *tab, I i) {
+    static_assert(sizeof(R) == 16 && alignof(R) == 16, "rec_load16: a 16-byte record");
+    RecRaw16 r;
+    __builtin_memcpy(&r, &tab[i], 16);
+    RS_KEEP4(r.a, r.b, r.c, r.d)
+    R out;
+    __builtin_memcpy(&out, &r, 16);
+    return out;
+}
+template <class R, class I> RS_MEM R rec_load8(const R *tab, I i) {
+    static_assert(sizeof(R) == 8 && alignof(R) == 8, "rec_load8: an 8-byte record");
+    struct alignas(8) Raw { uint32_t a, b; } r;
+    __builtin_memcpy(&r, &tab[i], 8);
+    RS_KEEP2(r.a, r.b)
+    R out;
+    __builtin_memcpy(&out, &r, 8);
+    return out;
+}
+// both halves of a link record are requested before either is used
+template <class I> RS_MEM LinkRec link_load(const LinkRec *tab, I i) {
+    RecRaw16 r[2];
+    __builtin_memcpy(r, &tab[i], 32);
+    RS_KEEP4(r[0].a, r[0].b, r[0].c, r[0].d)
+    RS_KEEP4(r[1].a, r[1].b, r[1].c, r[1].d)
+    LinkRec out;
+    __builtin_memcpy(&out, r, 32);
+    return out;
+}
+#endif
+
 struct KTab {
     const LaneRec *lanes_;
     const LinkRec *links_;
