@@ -335,12 +335,14 @@ void rs_mplight_destroy(rs_policy_handle p);
  *   RS_AGENT_MPLIGHT      rs_mplight_act(policy, h's RS_BUF_MPLIGHT (demand_shape 1) or RS_BUF_MPLIGHT_FULL (4), epsilon + k * epsilon_step
  *                         (>= 0), seed, step_key + k), keyed by the global environment index as IDQN; mode must be 0, and the buffer the
  *                         policy reads must not be switched off (rs_set_outputs)
+ *   RS_AGENT_FMA2C        rs_fma2c_act(policy, h's RS_BUF_LANE_AGG, n_envs, env_base, seed, step_key + k) into RS_BUF_ACTIONS (the FMA2C
+ *                         section below); mode and epsilon are not read
  * Returns the first error (codes as everywhere; rs_last_error of the handle it occurred on). */
-enum rs_agent { RS_AGENT_NONE = 0, RS_AGENT_RANDOM = 1, RS_AGENT_MAXWAVE = 2, RS_AGENT_MAXPRESSURE = 3, RS_AGENT_IDQN = 4, RS_AGENT_MPLIGHT = 5, RS_AGENT_IPPO = 6 };
+enum rs_agent { RS_AGENT_NONE = 0, RS_AGENT_RANDOM = 1, RS_AGENT_MAXWAVE = 2, RS_AGENT_MAXPRESSURE = 3, RS_AGENT_IDQN = 4, RS_AGENT_MPLIGHT = 5, RS_AGENT_IPPO = 6, RS_AGENT_FMA2C = 7 };
 typedef struct rs_group_agent {
     int32_t kind;               /* enum rs_agent */
     uint32_t step_key;          /* RANDOM, IDQN, MPLIGHT: key of the call's first step */
-    rs_policy_handle policy;    /* IDQN, MPLIGHT */
+    rs_policy_handle policy;    /* IDQN, MPLIGHT, FMA2C */
     int32_t mode;               /* IDQN: 0 epsilon-greedy, 1 softmax sampling (rs_idqn_act); MPLIGHT: 0 */
     float epsilon, epsilon_step;
     uint32_t seed;
@@ -661,6 +663,61 @@ typedef struct rs_ppo_train {
 int rs_ppo_perm(int32_t n, int32_t epochs, uint32_t seed, uint32_t update_key, int32_t *perm /* device [epochs][n] */, void *stream);
 int rs_ippo_pack_weights(rs_policy_handle p, const rs_ppo_tensors *params, void *stream);
 int rs_group_ppo_train(const rs_handle *handles, int32_t n_handles, const rs_ppo_train *tr, int32_t n_steps);
+
+/* ---- FMA2C: the fused LSTM actor-critic acting step (resco_amd/csrc/resco_fma2c.h) ---------------------------------------------
+ * Replaces FMA2C.act / MA2CAgent.act and the bootstrap forward of the reference (resco_benchmark/agents/fma2c.py:103-132,
+ * agents/ma2c.py:124-147, 411-456, 482-532) for all K = M managers + S workers (managers first, fma2c.py:41-70) of N environments:
+ * the input rows are assembled from RS_BUF_LANE_AGG (states.fma2c / fma2c_full, states.py:162-305: gather, clip, scale), the
+ * managers' actions of this step and the agents' previous pi (fingerprints); both nets of every agent run in fp32 on the f32-input
+ * MFMA; the action is drawn by inverse CDF over pi from the counter hash over (seed; env_base + env, agent, step_key).  The library
+ * owns, for max_envs environments: the LSTM state float [max_envs][K][4][64] (pi c, pi h, v c, v h), two fingerprint buffers float
+ * [2][max_envs][K][8], the managers' last actions int32 [max_envs][M], a parity word int32 [max_envs][K] (which fingerprint buffer
+ * the agent's next act reads; it writes the other one and flips), and a device copy of the packed weights.  Calls use rows env_base ..
+ * env_base + n_envs - 1 of that state, so the pipes of a split batch share one policy and draw what the single batch draws.
+ *
+ * rs_fma2c_desc (host pointers, copied): per agent the widths n_a (1 .. 8), n_s (1 .. 256), n_w (0 .. 32), n_f (0 .. 32), n_s + n_w +
+ * n_f <= 320; CSR tables over the agents: gather (index into the feature vector F, scale) of the states row -- F = blocks of n_obs:
+ * clip((queue + approach) / norm_wave, clip_wave), [full: clip(total_wait / 28 / norm_wave), clip(speed_sum / 20 / 28 / norm_wave)],
+ * clip(max_wait / norm_wait, clip_wait) --, fp_src (the agents whose fingerprints are appended, n_f = the sum of their n_a), mgr_src
+ * (the managers, < M, whose actions lead a worker's row; none for a manager).  A row is [mgr_src actions | gather | fingerprints],
+ * so len(mgr_src) + len(gather) = n_s + n_w.  Worker k - M is signal k - M of the scenario.
+ * weights (host f32): eleven tensors in this order, row-major, padded to NS = max n_s, NW = max n_w, NF = max n_f, [k][net] first
+ * (net 0: pi, net 1: v): fcw_w [K][2][NS][128], fcw_b [K][2][128], fcf_w [K][2][NF][64], fcf_b [K][2][64], fct_w [K][2][NW][32], fct_b
+ * [K][2][32], wx [K][2][224][256], wh [K][2][64][256], lb [K][2][256] (gate columns i, f, o, u), head_w [K][2][64][8], head_b [K][2][8].
+ *
+ * rs_fma2c_act: lane_agg = device f32 [n_envs][n_obs][5] (a handle's RS_BUF_LANE_AGG).  Two launches on `stream`: the managers, then
+ * the workers, which read the managers' actions.  Outputs (device pointers, each may be NULL): actions int32 [n_envs][S] the workers'
+ * local actions; pi_out f32 [n_envs][K][8] (0 beyond n_a); value_out f32 [n_envs][K]; rows_out f32 [n_envs][K][W] the assembled
+ * input rows, zero padded to W = max(n_s + n_w + n_f).  dyn: NULL or a device {uint32 unused; uint32 step_key} (graph replay).
+ * rs_fma2c_value: the bootstrap call (ma2c.py:141): the value net on the rows built with the managers' LAST actions and the current
+ * fingerprints; state, fingerprints, parity and manager actions are not written.  The bits equal those of a full call on that input.
+ * rs_fma2c_reset: model.reset() (ma2c.py:144-146) for environments env_base .. + n_envs: the state is zeroed.  The reference never
+ * clears a fingerprint at an episode end; clear_fingerprints != 0 does (both buffers and the parity words).
+ * rs_fma2c_set_device_weights: point the policy at a caller-owned DEVICE vector in the packed layout (borrowed, read in stream order).
+ * rs_fma2c_buffer: lends the library's device buffers: which = 0 state, 1 fingerprints, 2 manager actions, 3 parity.
+ * Refusals (RS_EINVAL, text in rs_last_error(NULL), nothing launched): a NULL policy, desc, weights, lane_agg or (rs_fma2c_value)
+ * value_out; a handle of rs_idqn_create / rs_mplight_create (and an FMA2C handle given to rs_idqn_* / rs_ippo_act / rs_mplight_*); n_envs
+ * < 1, env_base < 0 or env_base + n_envs > max_envs; widths outside the limits above or tables that do not add up; a device that is
+ * not there.  rs_group_step with RS_AGENT_FMA2C: per step and handle rs_fma2c_act on the handle's RS_BUF_LANE_AGG (rows env_base .. of
+ * the policy, key step_key + k) into RS_BUF_ACTIONS, then the step kernel; mode and epsilon are not read; refused (text in the
+ * handle's rs_last_error) for a policy of another kind, device or scenario (n_obs, n_signals), env_base + n_envs > max_envs, and a
+ * lane_agg that rs_set_outputs has switched off. */
+typedef struct rs_fma2c_desc {
+    int32_t K, M, S, n_obs, full;
+    float norm_wave, clip_wave, norm_wait, clip_wait;
+    const int32_t *n_a, *n_s, *n_w, *n_f;                  /* [K] */
+    const int32_t *gather_off, *gather_idx;                 /* [K + 1], [gather_off[K]] */
+    const float *gather_scale;
+    const int32_t *fp_off, *fp_src, *mgr_off, *mgr_src;     /* [K + 1] and the lists */
+} rs_fma2c_desc;
+int rs_fma2c_create(int32_t device_id, const rs_fma2c_desc *desc, const float *weights, int32_t max_envs, rs_policy_handle *out);
+int rs_fma2c_act(rs_policy_handle p, const float *lane_agg, int32_t n_envs, int32_t env_base, uint32_t seed, uint32_t step_key,
+                 const void *dyn, int32_t *actions, float *pi_out, float *value_out, float *rows_out, void *stream);
+int rs_fma2c_value(rs_policy_handle p, const float *lane_agg, int32_t n_envs, int32_t env_base, float *value_out, void *stream);
+int rs_fma2c_reset(rs_policy_handle p, int32_t env_base, int32_t n_envs, int32_t clear_fingerprints, void *stream);
+int rs_fma2c_set_device_weights(rs_policy_handle p, const float *weights);
+int rs_fma2c_buffer(rs_policy_handle p, int32_t which, void **dev_ptr);
+void rs_fma2c_destroy(rs_policy_handle p);
 
 /* static facts */
 int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal);

@@ -1,0 +1,515 @@
+"""FMA2C (feudal multi-agent A2C): the reference's agent (resco_benchmark/agents/fma2c.py, ma2c.py -- TF1) restated in PyTorch for
+all K = M managers + S workers of a map and N lock-step environments, and the binding of the fused HIP acting kernel
+(resco_amd/csrc/resco_fma2c.h).
+
+Agents (fma2c.py:41-70): managers in `management` dict order, then workers in all_ts_ids order.  A manager has n_a = 4 goals,
+n_w = 0 and n_f = 4 per neighbouring manager; a worker has n_a = its green phases, n_w = its lanes and n_f = the action counts of
+its downstream neighbours under the same manager (downstream dict order).  An agent's policy input row (fma2c.py:103-132) is
+    [own manager's action, the manager's neighbours' actions (workers only)] ++ states.fma2c row ++ fingerprints
+and, because the states row already ends with the n_w waits, splits as [0, n_s) waves (+ manager actions), [n_s, n_s + n_w) waits,
+[n_s + n_w, ..) fingerprints.  A fingerprint is an agent's own pi of the previous act (zeros before the first); the reference never
+clears it at an episode end (ma2c.py:112,129: only MA2CAgent.__init__ zeroes it) -- kept; reset(clear_fingerprints=True) is the
+explicit clear.
+
+Net (ma2c.py:411-456, 482-532): pi and v are two separate nets per agent, each concat(relu(fcw 128), relu(fcf 64), relu(fct 32) if
+n_w > 0) -> LSTM(64) (z = x wx + h wh + b, gates i, f, o, u; c = f c + i u; h = o tanh(c)) -> softmax(n_a) or a scalar.  An agent
+with n_f = 0 still has fcf: its 64 units are relu(bias) and the bias trains.
+
+Learning (ma2c.py:133-147, 286-306, 383-398, 566-612): A2CLearner."""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+N_FW, N_FP, N_FT, N_LSTM, A_MAX, MGR_ACTS = 128, 64, 32, 64, 8, 4       # agent_config.py:39-63: num_fw, num_fp, num_ft, num_lstm
+N_HID = N_FW + N_FP + N_FT                                               # 224: the LSTM's input (192 of it for a manager)
+
+
+class FMA2CLayout:
+    """Agent order, per-agent widths and the source tables of the input rows (fma2c.py:41-70, 75-132), from the scenario and the
+    ACTIVE mdp_configs['FMA2C' | 'FMA2CFull'] (config.mdp_config.activate(...) first, as the reference's main.py:48-72)."""
+
+    def __init__(self, scenario, full=False):
+        from ..config.mdp_config import mdp_configs
+        from ..multi_signal import fma2c_state_tables
+        cfg = mdp_configs['FMA2CFull' if full else 'FMA2C']
+        if 'supervisors' not in cfg:
+            raise RuntimeError("FMA2CLayout: call config.mdp_config.activate('%s', map) first" % ('FMA2CFull' if full else 'FMA2C'))
+        sc = self.scenario = scenario
+        self.full, self.cfg = bool(full), cfg
+        sup, mn = cfg['supervisors'], cfg['management_neighbors']
+        self.managers, self.workers = list(cfg['management'].keys()), list(sc.signal_ids)
+        self.agents = self.managers + self.workers
+        self.M, self.S, self.K = len(self.managers), len(self.workers), len(self.agents)
+        self.O, self.n_blocks = int(sc.n_obs), (4 if full else 2)          # feature blocks of F: wave, [total_wait, speed], max_wait
+        pos = {a: i for i, a in enumerate(self.agents)}
+        keys, s_idx, s_scale, lanes, _, _, same_region = fma2c_state_tables(sc, cfg, full)
+        ngreen = {sid: int(g) for sid, g in zip(sc.signal_ids, sc.tls_ngreen)}
+        self.n_a, self.n_s, self.n_w, self.n_f, self.n_m = [], [], [], [], []
+        self.gather_idx, self.gather_scale, self.fp_src, self.mgr_src = [], [], [], []
+        for a in self.agents:
+            if a in cfg['management']:
+                self.n_a.append(MGR_ACTS); self.n_w.append(0); self.mgr_src.append([])
+                self.fp_src.append([pos[n] for n in mn[a]])
+            else:
+                self.n_a.append(ngreen[a]); self.n_w.append(len(lanes[a]))
+                self.mgr_src.append([pos[sup[a]]] + [pos[n] for n in mn[sup[a]]])
+                self.fp_src.append([pos[nb] for nb in same_region[a]])
+            self.gather_idx.append([int(i) for i in s_idx[a]]); self.gather_scale.append([float(x) for x in s_scale[a]])
+            self.n_m.append(len(self.mgr_src[-1]))
+            self.n_s.append(self.n_m[-1] + len(self.gather_idx[-1]) - self.n_w[-1])
+        for k in range(self.K):
+            self.n_f.append(sum(self.n_a[j] for j in self.fp_src[k]))
+        self.width = [self.n_s[k] + self.n_w[k] + self.n_f[k] for k in range(self.K)]
+        self.NS, self.NW, self.NF, self.W = max(self.n_s), max(self.n_w), max(self.n_f), max(self.width)
+        self.G = max(len(g) for g in self.gather_idx)
+
+    def sizes(self, k):
+        return self.n_a[k], self.n_s[k], self.n_w[k], self.n_f[k]
+
+    # ---- tensors for the PyTorch path
+    def features(self, lane_agg):
+        """F [N, n_blocks * O] of VecMultiSignal.fma2c_states from lane_agg [N, O, 5] (queue, approach, total_wait, max_wait, speed_sum)"""
+        cfg, agg = self.cfg, lane_agg
+        nw, cw = cfg['norm_wave'], cfg['clip_wave']
+        blocks = [torch.clamp((agg[..., 0] + agg[..., 1]) / nw, 0, cw)]
+        if self.full:
+            blocks += [torch.clamp(agg[..., 2] / 28 / nw, 0, cw), torch.clamp(agg[..., 4] / 20 / 28 / nw, 0, cw)]
+        blocks.append(torch.clamp(agg[..., 3] / cfg['norm_wait'], 0, cfg['clip_wait']))
+        return torch.cat(blocks, dim=1)
+
+    def _tables(self, device):
+        t = getattr(self, '_tab', {}).get(str(device))
+        if t is None:
+            gi, gs = np.zeros((self.K, self.G), np.int64), np.zeros((self.K, self.G), np.float32)
+            for k in range(self.K):
+                gi[k, :len(self.gather_idx[k])], gs[k, :len(self.gather_idx[k])] = self.gather_idx[k], self.gather_scale[k]
+            # a row's element j comes from the per-environment source vector [manager actions (M) | obs rows (K * G) | fingerprints
+            # (K * 8) | one zero]
+            zero = self.M + self.K * self.G + self.K * A_MAX
+            src = np.full((self.K, self.W), zero, np.int64)
+            for k in range(self.K):
+                row = [pos for pos in self.mgr_src[k]]
+                row += [self.M + k * self.G + j for j in range(len(self.gather_idx[k]))]
+                for j in self.fp_src[k]:
+                    row += [self.M + self.K * self.G + j * A_MAX + a for a in range(self.n_a[j])]
+                src[k, :len(row)] = row
+            t = dict(gi=torch.as_tensor(gi, device=device), gs=torch.as_tensor(gs, device=device), src=torch.as_tensor(src, device=device))
+            if not hasattr(self, '_tab'):
+                self._tab = {}
+            self._tab[str(device)] = t
+        return t
+
+    def obs_rows(self, lane_agg):
+        """the states.fma2c rows of every agent, zero padded: [N, K, G]"""
+        t = self._tables(lane_agg.device)
+        return self.features(lane_agg)[:, t['gi']] * t['gs']
+
+    def obs_rows_from_dict(self, observation, device='cpu'):
+        rows = torch.zeros(1, self.K, self.G, device=device)
+        for k, a in enumerate(self.agents):
+            o = torch.as_tensor(np.asarray(observation[a], np.float32))
+            rows[0, k, :len(o)] = o
+        return rows
+
+    def assemble(self, obs_rows, mgr_actions, fingerprints):
+        """the policy input rows [N, K, W] (fma2c.py:103-132): manager actions as floats, the states row, the fingerprints of the
+        neighbours in order, zero padded"""
+        t = self._tables(obs_rows.device)
+        N = obs_rows.shape[0]
+        src = torch.cat([mgr_actions.to(obs_rows.dtype).reshape(N, self.M), obs_rows.reshape(N, -1), fingerprints.reshape(N, -1),
+                         obs_rows.new_zeros(N, 1)], dim=1)
+        return src[:, t['src']]
+
+    # ---- the descriptor of rs_fma2c_create (include/resco_sim.h: rs_fma2c_desc)
+    def desc_arrays(self):
+        off = lambda lists: np.cumsum([0] + [len(l) for l in lists]).astype(np.int32)
+        flat = lambda lists, dt: np.asarray([x for l in lists for x in l], dt)
+        return dict(n_a=np.asarray(self.n_a, np.int32), n_s=np.asarray(self.n_s, np.int32), n_w=np.asarray(self.n_w, np.int32),
+                    n_f=np.asarray(self.n_f, np.int32), gather_off=off(self.gather_idx), gather_idx=flat(self.gather_idx, np.int32),
+                    gather_scale=flat(self.gather_scale, np.float32), fp_off=off(self.fp_src), fp_src=flat(self.fp_src, np.int32),
+                    mgr_off=off(self.mgr_src), mgr_src=flat(self.mgr_src, np.int32))
+
+
+def ortho_init(rng, n_in, n_out, scale=math.sqrt(2.0)):
+    """ma2c.py:463-476 (lasagne's orthogonal init) for a [n_in, n_out] matrix"""
+    a = rng.standard_normal((n_in, n_out))
+    u, _, v = np.linalg.svd(a, full_matrices=False)
+    q = u if u.shape == (n_in, n_out) else v
+    return (scale * q).astype(np.float32)
+
+
+PARAMS = ('fcw_w', 'fcw_b', 'fcf_w', 'fcf_b', 'fct_w', 'fct_b', 'wx', 'wh', 'lb', 'head_w', 'head_b')    # the packed order
+
+
+class BatchedFMA2C(nn.Module):
+    """All K agents' two nets (index 0: pi, 1: v), stacked and zero-padded to the largest widths.  Padding stays zero under
+    training by construction: padded input columns are zero (no gradient reaches their weight rows), a manager's fct block is
+    multiplied by 0 (so fct_b and rows 192.. of wx get none), head columns beyond n_a are -inf before the softmax (pi = 0 there) and
+    only column 0 of the v net's head is read."""
+
+    def __init__(self, layout):
+        super().__init__()
+        L = self.layout = layout
+        K = L.K
+        shapes = dict(fcw_w=(K, 2, L.NS, N_FW), fcw_b=(K, 2, N_FW), fcf_w=(K, 2, L.NF, N_FP), fcf_b=(K, 2, N_FP), fct_w=(K, 2, L.NW, N_FT),
+                      fct_b=(K, 2, N_FT), wx=(K, 2, N_HID, 4 * N_LSTM), wh=(K, 2, N_LSTM, 4 * N_LSTM), lb=(K, 2, 4 * N_LSTM),
+                      head_w=(K, 2, N_LSTM, A_MAX), head_b=(K, 2, A_MAX))
+        for n in PARAMS:
+            setattr(self, n, nn.Parameter(torch.zeros(shapes[n])))
+        W = L.W
+        seg = lambda start, n, width: [[start[k] + j if j < n[k] else W for j in range(width)] for k in range(K)]
+        self.register_buffer('idx_s', torch.as_tensor(seg([0] * K, L.n_s, L.NS), dtype=torch.long).reshape(K, L.NS))
+        self.register_buffer('idx_w', torch.as_tensor(seg(L.n_s, L.n_w, L.NW), dtype=torch.long).reshape(K, L.NW))
+        self.register_buffer('idx_f', torch.as_tensor(seg([L.n_s[k] + L.n_w[k] for k in range(K)], L.n_f, L.NF), dtype=torch.long).reshape(K, L.NF))
+        self.register_buffer('has_w', torch.as_tensor([1.0 if w > 0 else 0.0 for w in L.n_w]))
+        self.register_buffer('act_mask', torch.as_tensor([[a < L.n_a[k] for a in range(A_MAX)] for k in range(K)]))
+
+    @torch.no_grad()
+    def init_like_reference(self, seed):
+        """every matrix orthogonal with scale sqrt(2) (ma2c.py:459-490, 504-516), biases zero; drawn per agent in the reference's
+        creation order (pi net then v net: fcw, fcf, fct, wx, wh, head) from numpy's RandomState(seed)"""
+        rng, L = np.random.RandomState(seed), self.layout
+        for p in self.parameters():
+            p.zero_()
+        for k in range(L.K):
+            n_a, n_s, n_w, n_f = L.sizes(k)
+            for net in range(2):
+                self.fcw_w[k, net, :n_s] = torch.as_tensor(ortho_init(rng, n_s, N_FW))
+                if n_f:
+                    self.fcf_w[k, net, :n_f] = torch.as_tensor(ortho_init(rng, n_f, N_FP))
+                if n_w:
+                    self.fct_w[k, net, :n_w] = torch.as_tensor(ortho_init(rng, n_w, N_FT))
+                n_in = N_HID if n_w else N_FW + N_FP
+                self.wx[k, net, :n_in] = torch.as_tensor(ortho_init(rng, n_in, 4 * N_LSTM))
+                self.wh[k, net] = torch.as_tensor(ortho_init(rng, N_LSTM, 4 * N_LSTM))
+                n_out = n_a if net == 0 else 1
+                self.head_w[k, net, :, :n_out] = torch.as_tensor(ortho_init(rng, N_LSTM, n_out))
+        return self
+
+    def packed(self):
+        """the flat float32 weight vector of rs_fma2c_create / rs_fma2c_set_device_weights: the tensors of PARAMS in order, each
+        row-major in its padded shape (resco_fma2c.h: Fma2cOff)"""
+        return torch.cat([getattr(self, n).detach().reshape(-1).float() for n in PARAMS])
+
+    def forward(self, rows, state, sl=slice(None)):
+        """rows [N, k, W] and state [N, k, 4, 64] (pi c, pi h, v c, v h) of the agents `sl` -> pi [N, k, 8] (0 beyond n_a), value
+        [N, k], new state.  The forward pass of ma2c.py:436-456 with done = False."""
+        N = rows.shape[0]
+        rp = torch.cat([rows, rows.new_zeros(N, rows.shape[1], 1)], dim=2)
+        take = lambda idx: torch.gather(rp, 2, idx[sl][None].expand(N, -1, -1))
+        xs, xw, xf = take(self.idx_s), take(self.idx_w), take(self.idx_f)
+        outs, new_state = [], []
+        for net in range(2):
+            h0 = torch.relu(torch.einsum('nki,kio->nko', xs, self.fcw_w[sl, net]) + self.fcw_b[sl, net])
+            h1 = torch.relu(torch.einsum('nki,kio->nko', xf, self.fcf_w[sl, net]) + self.fcf_b[sl, net])
+            h2 = torch.relu(torch.einsum('nki,kio->nko', xw, self.fct_w[sl, net]) + self.fct_b[sl, net]) * self.has_w[sl][None, :, None]
+            x = torch.cat([h0, h1, h2], dim=2)
+            c, h = state[:, :, 2 * net], state[:, :, 2 * net + 1]
+            z = torch.einsum('nki,kio->nko', x, self.wx[sl, net]) + torch.einsum('nki,kio->nko', h, self.wh[sl, net]) + self.lb[sl, net]
+            i, f, o, u = z.split(N_LSTM, dim=2)
+            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(u)
+            h = torch.sigmoid(o) * torch.tanh(c)
+            new_state += [c, h]
+            outs.append(torch.einsum('nki,kio->nko', h, self.head_w[sl, net]) + self.head_b[sl, net])
+        pi = torch.softmax(outs[0].masked_fill(~self.act_mask[sl][None], float('-inf')), dim=2)
+        return pi, outs[1][..., 0], torch.stack(new_state, dim=2)
+
+    @staticmethod
+    def draw(pi, u):
+        """inverse CDF over pi with the given uniforms u [N, k]: the first action whose running sum exceeds u (the last one with a
+        positive probability when rounding leaves the sum below u)"""
+        cdf = torch.cumsum(pi, dim=2)
+        a = (u[..., None] >= cdf).sum(dim=2)
+        last = (pi > 0).long().cumsum(dim=2).argmax(dim=2)
+        return torch.minimum(a, last)
+
+    def act(self, obs_rows, state, fingerprints, u):
+        """One acting step for all agents (fma2c.py:103-132): fingerprints [N, K, 8] are read once, managers act first, workers see
+        the managers' actions of this step.  Returns dict(actions [N, K], pi, value, state, rows [N, K, W], fingerprints = pi)."""
+        L, M = self.layout, self.layout.M
+        N = obs_rows.shape[0]
+        macts = torch.zeros(N, M, dtype=torch.long, device=obs_rows.device)
+        rows_m = L.assemble(obs_rows, macts, fingerprints)[:, :M]
+        pi_m, v_m, st_m = self.forward(rows_m, state[:, :M], slice(0, M))
+        a_m = self.draw(pi_m, u[:, :M])
+        rows_w = L.assemble(obs_rows, a_m, fingerprints)[:, M:]
+        pi_w, v_w, st_w = self.forward(rows_w, state[:, M:], slice(M, L.K))
+        a_w = self.draw(pi_w, u[:, M:])
+        pi = torch.cat([pi_m, pi_w], dim=1)
+        return dict(actions=torch.cat([a_m, a_w], dim=1), pi=pi, value=torch.cat([v_m, v_w], dim=1), state=torch.cat([st_m, st_w], dim=1),
+                    rows=torch.cat([rows_m, rows_w], dim=1), fingerprints=pi)
+
+    def value(self, obs_rows, state, fingerprints, mgr_actions):
+        """the bootstrap call (ma2c.py:141, out_type 'v'): the value of the rows built with the managers' last actions and the
+        current fingerprints; the state is read and left alone"""
+        rows = self.layout.assemble(obs_rows, mgr_actions, fingerprints)
+        return self.forward(rows, state)[1]
+
+    def evaluate_segment(self, rows, dones, state0):
+        """the re-run of a segment for BPTT (ma2c.py:504-532 over ob_bw): rows [T, N, K, W], dones [T] or [T, N] = the PRE-step done
+        of every step (the state is zeroed where it is set), state0 = the acting state at the segment's start -> pi [T, N, K, 8],
+        value [T, N, K]"""
+        state, pis, vs = state0, [], []
+        for t in range(rows.shape[0]):
+            d = dones[t].to(rows.dtype)
+            state = state * (1.0 - (d.reshape(-1, 1, 1, 1) if d.dim() else d))
+            pi, v, state = self.forward(rows[t], state)
+            pis.append(pi); vs.append(v)
+        return torch.stack(pis), torch.stack(vs)
+
+
+class A2CLearner:
+    """The on-policy learner of ma2c.py (MA2CAgent.observe :133-147, OnPolicyBuffer :566-612, ACPolicy.prepare_loss :286-306,
+    LstmACPolicy.backward :383-398) for all agents and N environments at once: an agent's batch is N sequences of the segment and
+    every mean is over N x T.  The optimiser is TF1's RMSPropOptimizer written out: ms starts at ONE, epsilon sits INSIDE the root,
+    no momentum -- ms = alpha ms + (1 - alpha) g^2; w -= lr g / sqrt(ms + eps)."""
+
+    def __init__(self, net, n_envs, batch_size=120, gamma=0.96, lr=2.5e-4, alpha=0.99, eps=1e-5, max_grad_norm=40.0, value_coef=0.5,
+                 entropy_coef=0.001, reward_norm=2000.0, reward_clip=2.0):
+        self.net, self.N, self.T = net, int(n_envs), int(batch_size)
+        self.gamma, self.lr, self.alpha, self.eps, self.max_grad_norm = gamma, lr, alpha, eps, max_grad_norm
+        self.value_coef, self.entropy_coef, self.reward_norm, self.reward_clip = value_coef, entropy_coef, reward_norm, reward_clip
+        dev, K, W = net.fcw_w.device, net.layout.K, net.layout.W
+        self.rows = torch.zeros(self.T, self.N, K, W, device=dev)
+        self.acts = torch.zeros(self.T, self.N, K, dtype=torch.long, device=dev)
+        self.rews, self.vals = torch.zeros(self.T, self.N, K, device=dev), torch.zeros(self.T, self.N, K, device=dev)
+        self.dones = [False]                # pre-step done of every stored step, then the post-step done of the last (OnPolicyBuffer.dones)
+        self.n, self.steps_done, self.updates = 0, 0, 0
+        self.states_bw = torch.zeros(self.N, K, 4, N_LSTM, device=dev)
+        self.ms = [torch.ones_like(p) for p in net.parameters()]
+        self.last_loss = None
+
+    def add(self, rows, actions, rewards, values, done):
+        """MA2CImplementation.add_transition (ma2c.py:220-225): rewards r / reward_norm clipped to +-reward_clip"""
+        r = rewards
+        if self.reward_norm:
+            r = r / self.reward_norm
+        if self.reward_clip:
+            r = torch.clamp(r, -self.reward_clip, self.reward_clip)
+        t = self.n
+        self.rows[t], self.acts[t], self.rews[t], self.vals[t] = rows, actions, r, values
+        self.dones.append(bool(done))
+        self.n += 1
+
+    def returns(self, R):
+        """OnPolicyBuffer._add_R_Adv (ma2c.py:586-598) with the POST-step dones: R_t = r_t + gamma R_{t+1} (1 - done_{t+1}); Adv = R - v"""
+        Rs = torch.zeros_like(self.rews[:self.n])
+        for t in range(self.n - 1, -1, -1):
+            R = self.rews[t] + self.gamma * R * (0.0 if self.dones[t + 1] else 1.0)
+            Rs[t] = R
+        return Rs, Rs - self.vals[:self.n]
+
+    def loss(self, rows, acts, dones, Rs, Advs, state0):
+        """per-agent losses [K] (ma2c.py:286-297) over the re-run of the segment from state0"""
+        pi, v = self.net.evaluate_segment(rows, dones, state0)
+        log_pi = torch.log(torch.clamp(pi, 1e-10, 1.0))
+        entropy = -(pi * log_pi).sum(dim=3)
+        policy_loss = -(torch.gather(log_pi, 3, acts[..., None])[..., 0] * Advs).mean(dim=(0, 1))
+        value_loss = ((Rs - v) ** 2).mean(dim=(0, 1)) * 0.5 * self.value_coef
+        return policy_loss + value_loss - entropy.mean(dim=(0, 1)) * self.entropy_coef
+
+    def clip_scales(self, grads):
+        """tf.clip_by_global_norm per agent over both of its nets (ma2c.py:299-302): g * clip / max(norm, clip)"""
+        K = self.net.layout.K
+        sq = sum((g.reshape(K, -1).double() ** 2).sum(dim=1) for g in grads)
+        norm = torch.sqrt(sq)
+        return (self.max_grad_norm / torch.clamp(norm, min=self.max_grad_norm)).float(), norm
+
+    @torch.no_grad()
+    def rmsprop_step(self, grads, scales=None):
+        for p, g, ms in zip(self.net.parameters(), grads, self.ms):
+            if scales is not None:
+                g = g * scales.reshape(-1, *([1] * (g.dim() - 1)))
+            ms.mul_(self.alpha).add_((1.0 - self.alpha) * g * g)
+            p.sub_(self.lr * g / torch.sqrt(ms + self.eps))
+
+    def update(self, R, states_fw):
+        """MA2CImplementation.backward (ma2c.py:208-212): R [N, K] = the bootstrap value (zeros at done); states_fw = the acting state
+        now, which becomes the next segment's start (ma2c.py:398)"""
+        Rs, Advs = self.returns(R)
+        n = self.n
+        dones = torch.as_tensor(self.dones[:n], device=self.rows.device)
+        params = list(self.net.parameters())
+        loss = self.loss(self.rows[:n], self.acts[:n], dones, Rs.detach(), Advs.detach(), self.states_bw)
+        grads = torch.autograd.grad(loss.sum(), params)
+        if self.max_grad_norm > 0:
+            scales, self.grad_norm = self.clip_scales(grads)
+        else:
+            scales = None
+        self.rmsprop_step(grads, scales)
+        self.states_bw = states_fw.detach().clone()
+        self.dones, self.n = [self.dones[-1]], 0
+        self.updates += 1
+        self.last_loss = loss.detach()
+        return self.last_loss
+
+    def observe(self, rows, actions, rewards, values, done, states_fw, bootstrap):
+        """MA2CAgent.observe (ma2c.py:133-147): store, and every batch_size steps or at done update with R = 0 (done) or
+        bootstrap() -> v [N, K] of the new observation.  At done the segment start state is zeroed (model.reset()); zeroing the
+        acting state is the caller's.  Returns the per-agent losses of the update or None."""
+        self.add(rows, actions, rewards, values, done)
+        self.steps_done += 1
+        out = None
+        if self.steps_done % self.T == 0 or done:
+            R = torch.zeros_like(values) if done else bootstrap()
+            out = self.update(R.detach(), states_fw)
+        if done:
+            self.steps_done = 0
+            self.states_bw.zero_()
+        return out
+
+
+class FusedFMA2C:
+    """The fused HIP acting path (rs_fma2c_*; resco_amd/csrc/resco_fma2c.h): input assembly from RS_BUF_LANE_AGG, both nets of all K
+    agents, the draw, with LSTM state, fingerprints and manager actions of max_envs environments kept on the device by the library."""
+
+    BUF = {'state': 0, 'fingerprints': 1, 'mgr_actions': 2, 'parity': 3}
+
+    def __init__(self, net, max_envs, device=0, seed=0):
+        from ..sim import Fma2cDesc, load_library
+        self.net, self.L, self.max_envs, self.device, self.seed = net, net.layout, int(max_envs), int(device), int(seed) & 0xFFFFFFFF
+        self._lib, L = load_library(), net.layout
+        self._keep = L.desc_arrays()
+        cfg = L.cfg
+        d = Fma2cDesc(L.K, L.M, L.S, L.O, 1 if L.full else 0, float(cfg['norm_wave']), float(cfg['clip_wave']), float(cfg['norm_wait']),
+                      float(cfg['clip_wait']), *[self._keep[n].ctypes.data for n in Fma2cDesc.ARRAYS])
+        w = np.ascontiguousarray(net.packed().cpu().numpy(), np.float32)
+        h = C.c_void_p()
+        rc = self._lib.rs_fma2c_create(self.device, C.byref(d), w.ctypes.data, self.max_envs, C.byref(h))
+        if rc != 0:
+            raise RuntimeError('rs_fma2c_create failed (%d): %s' % (rc, (self._lib.rs_last_error(None) or b'?').decode()))
+        self._h, self._wdev = h, None
+
+    @property
+    def handle(self):
+        return self._h.value if self._h is not None else None
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError('%s failed (%d): %s' % (what, rc, (self._lib.rs_last_error(None) or b'?').decode()))
+
+    def close(self):
+        if getattr(self, '_h', None) is not None:
+            self._lib.rs_fma2c_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @torch.no_grad()
+    def refresh_on_device(self):
+        """re-pack the network's weights on the GPU into a persistent buffer and point the kernel at it: after every update"""
+        flat = self.net.packed()
+        if self._wdev is None:
+            self._wdev = torch.empty_like(flat)
+        self._wdev.copy_(flat)
+        self._check(self._lib.rs_fma2c_set_device_weights(self._h, self._wdev.data_ptr()), 'rs_fma2c_set_device_weights')
+
+    def buffer(self, name):
+        """zero-copy tensor over the library's state [max_envs, K, 4, 64], fingerprints [2, max_envs, K, 8], mgr_actions [max_envs, M]
+        or parity [max_envs, K] (which fingerprint buffer an agent's NEXT act reads)"""
+        from ..sim import _DevArray
+        p = C.c_void_p()
+        self._check(self._lib.rs_fma2c_buffer(self._h, self.BUF[name], C.byref(p)), 'rs_fma2c_buffer')
+        E, K = self.max_envs, self.L.K
+        shape, dt = {'state': ((E, K, 4, N_LSTM), 0), 'fingerprints': ((2, E, K, A_MAX), 0), 'mgr_actions': ((E, self.L.M), 1), 'parity': ((E, K), 1)}[name]
+        return torch.as_tensor(_DevArray(p.value, shape, dt, self), device='cuda:%d' % self.device)
+
+    def fingerprints(self):
+        """every agent's current fingerprint [max_envs, K, 8] (a copy): the buffer its next act reads"""
+        fp, par = self.buffer('fingerprints'), self.buffer('parity').long()
+        return torch.where(par[..., None] == 0, fp[0], fp[1])
+
+    def _args(self, lane_agg, env_base, stream):
+        from ..sim import torch_stream
+        assert lane_agg.is_cuda and lane_agg.dtype == torch.float32 and lane_agg.is_contiguous() and tuple(lane_agg.shape[1:]) == (self.L.O, 5)
+        return lane_agg.shape[0], int(env_base), (torch_stream(self.device) if stream is None else stream)
+
+    def act(self, lane_agg, step_key=0, env_base=0, actions=None, want=('pi', 'value', 'rows'), dyn=None, stream=None):
+        """one act of all agents on lane_agg [N, O, 5] (rows env_base .. of the library's state).  Returns dict(actions int32 [N, S]
+        = the workers' local actions, and pi [N, K, 8] / value [N, K] / rows [N, K, W] as asked in `want`)."""
+        N, eb, st = self._args(lane_agg, env_base, stream)
+        dev, L = lane_agg.device, self.L
+        out = {'actions': actions if actions is not None else torch.empty(N, L.S, dtype=torch.int32, device=dev)}
+        if 'pi' in want:
+            out['pi'] = torch.empty(N, L.K, A_MAX, device=dev)
+        if 'value' in want:
+            out['value'] = torch.empty(N, L.K, device=dev)
+        if 'rows' in want:
+            out['rows'] = torch.empty(N, L.K, L.W, device=dev)
+        ptr = lambda k: out[k].data_ptr() if k in out else None
+        self._check(self._lib.rs_fma2c_act(self._h, lane_agg.data_ptr(), N, eb, self.seed, int(step_key) & 0xFFFFFFFF,
+                                           dyn.data_ptr() if dyn is not None else None, ptr('actions'), ptr('pi'), ptr('value'), ptr('rows'), st),
+                    'rs_fma2c_act')
+        return out
+
+    def value(self, lane_agg, env_base=0, stream=None):
+        N, eb, st = self._args(lane_agg, env_base, stream)
+        v = torch.empty(N, self.L.K, device=lane_agg.device)
+        self._check(self._lib.rs_fma2c_value(self._h, lane_agg.data_ptr(), N, eb, v.data_ptr(), st), 'rs_fma2c_value')
+        return v
+
+    def reset(self, env_base=0, n_envs=None, clear_fingerprints=False, stream=None):
+        from ..sim import torch_stream
+        n = self.max_envs - int(env_base) if n_envs is None else int(n_envs)
+        self._check(self._lib.rs_fma2c_reset(self._h, int(env_base), n, 1 if clear_fingerprints else 0,
+                                             torch_stream(self.device) if stream is None else stream), 'rs_fma2c_reset')
+
+
+class FMA2C:
+    """The reference's agent interface (agents/fma2c.py:21-158): act(observation dict) -> dict of actions for every manager and
+    worker of ONE environment, observe(observation, reward, done, info).  The observation dicts arrive as states.fma2c rows, not
+    as the simulator's lane aggregates, so this interface runs BatchedFMA2C itself; the fused kernel is the batched path
+    (FusedFMA2C, tools/fma2c_train.py).  config: agent_configs['FMA2C' | 'FMA2CFULL' | 'FMA2CVAL'] (+ 'steps'); the matching
+    mdp_config.activate(...) must have been called."""
+
+    def __init__(self, config, obs_act, map_name, thread_number, scenario=None, device='cpu', seed=0):
+        from ..config.map_config import map_configs
+        from ..multi_signal import load_scenario
+        from .. import states
+        self.config = config
+        sc = scenario if scenario is not None else load_scenario(map_name, None, map_configs.get(map_name, {}).get('lights', ()), 3)
+        self.layout = FMA2CLayout(sc, full=config.get('state') is states.fma2c_full)
+        self.net = BatchedFMA2C(self.layout).init_like_reference(seed).to(device)
+        self.learner = A2CLearner(self.net, 1, batch_size=config['batch_size'], gamma=config['gamma'], lr=config['lr_init'],
+                                  alpha=config['rmsp_alpha'], eps=config['rmsp_epsilon'], max_grad_norm=config['max_grad_norm'],
+                                  value_coef=config['value_coef'], entropy_coef=config['entropy_coef_init'],
+                                  reward_norm=config['reward_norm'], reward_clip=config['reward_clip'])
+        self.device, L = device, self.layout
+        self.state = torch.zeros(1, L.K, 4, N_LSTM, device=device)
+        self.fp = torch.zeros(1, L.K, A_MAX, device=device)
+        self.gen = torch.Generator().manual_seed(seed)
+        self.last = None
+
+    def clear_fingerprints(self):
+        self.fp.zero_()
+
+    @torch.no_grad()
+    def act(self, observation):
+        L = self.layout
+        u = torch.rand(1, L.K, generator=self.gen).to(self.device)
+        self.last = out = self.net.act(L.obs_rows_from_dict(observation, self.device), self.state, self.fp, u)
+        self.state, self.fp = out['state'], out['fingerprints']
+        a = out['actions'][0].tolist()
+        return {name: int(a[k]) for k, name in enumerate(L.agents)}
+
+    def observe(self, observation, reward, done, info):
+        L, out = self.layout, self.last
+        rew = torch.tensor([[float(reward[a]) for a in L.agents]], device=self.device)
+        rows_new = L.obs_rows_from_dict(observation, self.device)
+
+        def boot():
+            with torch.no_grad():
+                return self.net.value(rows_new, self.state, self.fp, out['actions'][:, :L.M])
+        self.learner.observe(out['rows'], out['actions'], rew, out['value'], done, self.state, boot)
+        if done:
+            self.state = torch.zeros_like(self.state)       # model.reset(); the fingerprints stay (module docstring)
+
+    def save(self, path):
+        torch.save({'model_state_dict': self.net.state_dict()}, path + '.pt')

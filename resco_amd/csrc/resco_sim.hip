@@ -111,6 +111,7 @@ __device__ unsigned long long *g_sec_prof;
 #include "resco_host.h"
 #include "resco_policy.h"
 #include "resco_frap.h"
+#include "resco_fma2c.h"
 #include "resco_ppo.h"
 #include "resco_ppo_train.h"
 #include "resco_dqn_train.h"
@@ -698,7 +699,7 @@ extern "C" int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int
 
 
 // ------------------------------------------------------------------------------------------------ fused IDQN policy
-enum { POLICY_IDQN = 0, POLICY_MPLIGHT = 1 };
+enum { POLICY_IDQN = 0, POLICY_MPLIGHT = 1, POLICY_FMA2C = 2 };
 struct rs_policy {
     int device = 0;
     int kind = POLICY_IDQN;     // which rs_*_create made it: the entry points of the other kind refuse it
@@ -706,6 +707,8 @@ struct rs_policy {
     int amax = 0;               // IDQN: the widest signal's action count = the columns of the learner's fc3_w (rs_idqn_pack_weights)
     bool own_w1 = true, own_w2 = true, own_w3 = true, own_b3 = true;      // IDQN: the buffer is this handle's create-time copy, not the caller's
     FrapTab F{};                // MPLight
+    Fma2cTab A{};               // FMA2C
+    int fm_lds = 0;             // FMA2C: dynamic LDS of the kernel in bytes
     std::vector<void *> allocs;
 };
 
@@ -781,6 +784,7 @@ static void idqn_launch(const PolicyTab &W, const void *obs, int n_envs, int env
 
 extern "C" int rs_idqn_act(rs_policy_handle p, const void *obs, int32_t n_envs, int32_t env_base, int32_t mode, float epsilon, uint32_t seed, uint32_t step_key,
                            const void *dyn, int32_t *actions, float *q, void *stream) {
+    if (p && p->kind != POLICY_IDQN) g_create_err = "rs_idqn_act: the handle is not an rs_idqn_create policy";
     if (!p || p->kind != POLICY_IDQN || !obs || !actions || n_envs <= 0 || mode < 0 || mode > 1) return RS_EINVAL;
     if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
     idqn_launch(p->W, obs, n_envs, env_base, mode, epsilon, seed, step_key, dyn, actions, q, (hipStream_t)stream);
@@ -1166,6 +1170,7 @@ extern "C" int rs_mplight_create(int32_t device_id, int32_t demand_shape, int32_
 
 extern "C" int rs_mplight_act(rs_policy_handle p, const void *obs, int32_t n_envs, int32_t env_base, float epsilon, uint32_t seed, uint32_t step_key,
                               const void *dyn, int32_t *actions, int32_t *pair_index, float *q, void *stream) {
+    if (p && p->kind != POLICY_MPLIGHT) g_create_err = "rs_mplight_act: the handle is not an rs_mplight_create policy";
     if (!p || p->kind != POLICY_MPLIGHT || !obs || !actions || n_envs <= 0) return RS_EINVAL;
     if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
     mplight_launch(p->F, obs, n_envs, env_base, epsilon, seed, step_key, dyn, actions, pair_index, q, (hipStream_t)stream);
@@ -1175,6 +1180,141 @@ extern "C" int rs_mplight_act(rs_policy_handle p, const void *obs, int32_t n_env
 extern "C" int rs_mplight_set_device_weights(rs_policy_handle p, const float *weights) {
     if (!p || p->kind != POLICY_MPLIGHT || !weights) return RS_EINVAL;
     p->F.w = weights;
+    return RS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ fused FMA2C acting step (resco_fma2c.h)
+static int fma2c_refuse(const char *msg) { g_create_err = msg; return RS_EINVAL; }
+
+extern "C" void rs_fma2c_destroy(rs_policy_handle p) { policy_destroy(p); }
+
+extern "C" int rs_fma2c_create(int32_t device_id, const rs_fma2c_desc *d, const float *weights, int32_t max_envs, rs_policy_handle *out) {
+    int ndev = 0;
+    if (int rc = policy_devices(out, &ndev)) return rc;
+    if (device_id < 0 || device_id >= ndev) return fma2c_refuse("rs_fma2c_create: no such device");
+    if (!d || !weights) return fma2c_refuse("rs_fma2c_create: desc or weights is NULL");
+    if (!d->n_a || !d->n_s || !d->n_w || !d->n_f || !d->gather_off || !d->gather_idx || !d->gather_scale || !d->fp_off || !d->fp_src || !d->mgr_off || !d->mgr_src)
+        return fma2c_refuse("rs_fma2c_create: a table pointer of the descriptor is NULL");
+    const int K = d->K, M = d->M, S = d->S;
+    if (K < 1 || M < 1 || S < 1 || K != M + S || d->n_obs < 1 || max_envs < 1) return fma2c_refuse("rs_fma2c_create: need K = M + S, M >= 1, S >= 1, n_obs >= 1, max_envs >= 1");
+    const int blocks = d->full ? 4 : 2;
+    int NS = 0, NW = 0, NF = 0, W = 0;
+    for (int k = 0; k < K; ++k) {
+        const int na = d->n_a[k], ns = d->n_s[k], nw = d->n_w[k], nf = d->n_f[k];
+        if (na < 1 || na > FM_AMAX || ns < 1 || ns > FM_NS_MAX || nw < 0 || nw > FM_NW_MAX || nf < 0 || nf > FM_NF_MAX || ns + nw + nf > FM_W_MAX)
+            return fma2c_refuse("rs_fma2c_create: widths outside the limits (1 <= n_a <= 8, 1 <= n_s <= 256, 0 <= n_w <= 32, 0 <= n_f <= 32, n_s + n_w + n_f <= 320)");
+        const int nm = d->mgr_off[k + 1] - d->mgr_off[k], ng = d->gather_off[k + 1] - d->gather_off[k];
+        if (nm < 0 || ng < 0 || d->fp_off[k + 1] < d->fp_off[k] || nm + ng != ns + nw || (k < M && nm != 0))
+            return fma2c_refuse("rs_fma2c_create: the tables do not add up (len(mgr_src) + len(gather) = n_s + n_w; no mgr_src for a manager)");
+        int f = 0;
+        for (int q = d->fp_off[k]; q < d->fp_off[k + 1]; ++q) {
+            if (d->fp_src[q] < 0 || d->fp_src[q] >= K) return fma2c_refuse("rs_fma2c_create: fp_src names an agent outside 0 .. K - 1");
+            f += d->n_a[d->fp_src[q]];
+        }
+        if (f != nf) return fma2c_refuse("rs_fma2c_create: n_f is not the sum of the fingerprint sources' n_a");
+        for (int q = d->mgr_off[k]; q < d->mgr_off[k + 1]; ++q)
+            if (d->mgr_src[q] < 0 || d->mgr_src[q] >= M) return fma2c_refuse("rs_fma2c_create: mgr_src names a manager outside 0 .. M - 1");
+        for (int q = d->gather_off[k]; q < d->gather_off[k + 1]; ++q)
+            if (d->gather_idx[q] < 0 || d->gather_idx[q] >= blocks * d->n_obs) return fma2c_refuse("rs_fma2c_create: gather_idx outside the feature vector");
+        NS = ns > NS ? ns : NS; NW = nw > NW ? nw : NW; NF = nf > NF ? nf : NF; W = ns + nw + nf > W ? ns + nw + nf : W;
+    }
+    if (d->mgr_off[0] != 0 || d->gather_off[0] != 0 || d->fp_off[0] != 0) return fma2c_refuse("rs_fma2c_create: the offset tables start at 0");
+    rs_policy *p = nullptr;
+    int rc = policy_new(device_id, POLICY_FMA2C, &p);
+    if (rc) return rc;
+    Fma2cTab &A = p->A;
+    A.K = K; A.M = M; A.S = S; A.O = d->n_obs; A.full = d->full ? 1 : 0; A.NS = NS; A.NW = NW; A.NF = NF; A.W = W; A.max_envs = max_envs;
+    A.norm_wave = d->norm_wave; A.clip_wave = d->clip_wave; A.norm_wait = d->norm_wait; A.clip_wait = d->clip_wait;
+    p->fm_lds = (int)(sizeof(float) * ((size_t)FM_TM * (W + 1) + FM_TM * FM_HS + FM_TM * FM_ZS + FM_TM * FM_AMAX));
+    const size_t nw_ = Fma2cOff(K, NS, NW, NF).n, E = (size_t)max_envs;
+    const int32_t zero1 = 0;
+    const float zerof = 0.0f;
+    auto up_i = [&](const int32_t **dst, const int32_t *src, size_t n) { return n ? pol_upload<int32_t>(p, dst, src, n) : pol_upload<int32_t>(p, dst, &zero1, 1); };
+    auto zeros = [&](void **dst, size_t bytes) {
+        if (hipMalloc(dst, bytes) != hipSuccess) return (int)RS_ENOMEM;
+        p->allocs.push_back(*dst);
+        return hipMemset(*dst, 0, bytes) == hipSuccess ? (int)RS_OK : (int)RS_EHIP;
+    };
+    if ((rc = pol_upload<float>(p, &A.w, weights, nw_)) || (rc = up_i(&A.n_a, d->n_a, K)) || (rc = up_i(&A.n_s, d->n_s, K)) || (rc = up_i(&A.n_w, d->n_w, K)) ||
+        (rc = up_i(&A.n_f, d->n_f, K)) || (rc = up_i(&A.g_off, d->gather_off, K + 1)) || (rc = up_i(&A.g_idx, d->gather_idx, d->gather_off[K])) ||
+        (rc = d->gather_off[K] ? pol_upload<float>(p, &A.g_scale, d->gather_scale, d->gather_off[K]) : pol_upload<float>(p, &A.g_scale, &zerof, 1)) ||
+        (rc = up_i(&A.fp_off, d->fp_off, K + 1)) || (rc = up_i(&A.fp_src, d->fp_src, d->fp_off[K])) || (rc = up_i(&A.m_off, d->mgr_off, K + 1)) ||
+        (rc = up_i(&A.m_src, d->mgr_src, d->mgr_off[K])) || (rc = zeros((void **)&A.state, E * K * 4 * FM_L * sizeof(float))) ||
+        (rc = zeros((void **)&A.fp, 2 * E * K * FM_AMAX * sizeof(float))) || (rc = zeros((void **)&A.macts, E * M * sizeof(int32_t))) ||
+        (rc = zeros((void **)&A.parity, E * K * sizeof(int32_t)))) {
+        g_create_err = "rs_fma2c_create: device allocation / upload failed";
+        rs_fma2c_destroy(p);
+        return rc;
+    }
+    // the attribute belongs to the kernel, not to this policy: always the most any policy can ask for (W = FM_W_MAX: 112 KB)
+    const int lds_max = (int)(sizeof(float) * ((size_t)FM_TM * (FM_W_MAX + 1) + FM_TM * FM_HS + FM_TM * FM_ZS + FM_TM * FM_AMAX));
+    if (hipFuncSetAttribute((const void *)rs_fma2c_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess ||
+        hipFuncSetAttribute((const void *)rs_fma2c_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) {
+        g_create_err = "rs_fma2c_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
+        rs_fma2c_destroy(p);
+        return RS_EHIP;
+    }
+    *out = p;
+    return RS_OK;
+}
+
+// the two launches of one act: managers, then workers (the caller reads hipGetLastError)
+static void fma2c_act_launch(const rs_policy *p, const float *lane_agg, int n_envs, int env_base, uint32_t seed, uint32_t step_key, const void *dyn,
+                             const Fma2cOut &out, hipStream_t st) {
+    const Fma2cTab &A = p->A;
+    const int tiles = (n_envs + FM_TM - 1) / FM_TM;
+    hipLaunchKernelGGL(rs_fma2c_kernel<true>, dim3(tiles, A.M), dim3(256), p->fm_lds, st, A, lane_agg, n_envs, env_base, 0, seed, step_key, (const uint32_t *)dyn, out);
+    hipLaunchKernelGGL(rs_fma2c_kernel<true>, dim3(tiles, A.S), dim3(256), p->fm_lds, st, A, lane_agg, n_envs, env_base, A.M, seed, step_key, (const uint32_t *)dyn, out);
+}
+
+static int fma2c_check(rs_policy_handle p, int32_t n_envs, int32_t env_base, const char *kind_msg, const char *range_msg) {
+    if (!p) return fma2c_refuse("rs_fma2c: NULL policy handle");
+    if (p->kind != POLICY_FMA2C) return fma2c_refuse(kind_msg);
+    if (n_envs < 1 || env_base < 0 || (int64_t)env_base + n_envs > p->A.max_envs) return fma2c_refuse(range_msg);
+    return RS_OK;
+}
+
+extern "C" int rs_fma2c_act(rs_policy_handle p, const float *lane_agg, int32_t n_envs, int32_t env_base, uint32_t seed, uint32_t step_key,
+                            const void *dyn, int32_t *actions, float *pi_out, float *value_out, float *rows_out, void *stream) {
+    if (int rc = fma2c_check(p, n_envs, env_base, "rs_fma2c_act: the handle is not an rs_fma2c_create policy",
+                             "rs_fma2c_act: need 1 <= n_envs, 0 <= env_base, env_base + n_envs <= max_envs")) return rc;
+    if (!lane_agg) return fma2c_refuse("rs_fma2c_act: lane_agg is NULL");
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    fma2c_act_launch(p, lane_agg, n_envs, env_base, seed, step_key, dyn, Fma2cOut{actions, pi_out, value_out, rows_out}, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_fma2c_value(rs_policy_handle p, const float *lane_agg, int32_t n_envs, int32_t env_base, float *value_out, void *stream) {
+    if (int rc = fma2c_check(p, n_envs, env_base, "rs_fma2c_value: the handle is not an rs_fma2c_create policy",
+                             "rs_fma2c_value: need 1 <= n_envs, 0 <= env_base, env_base + n_envs <= max_envs")) return rc;
+    if (!lane_agg || !value_out) return fma2c_refuse("rs_fma2c_value: lane_agg or value_out is NULL");
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    hipLaunchKernelGGL(rs_fma2c_kernel<false>, dim3((n_envs + FM_TM - 1) / FM_TM, p->A.K), dim3(256), p->fm_lds, (hipStream_t)stream, p->A, lane_agg, n_envs,
+                       env_base, 0, 0u, 0u, (const uint32_t *)nullptr, Fma2cOut{nullptr, nullptr, value_out, nullptr});
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_fma2c_reset(rs_policy_handle p, int32_t env_base, int32_t n_envs, int32_t clear_fingerprints, void *stream) {
+    if (int rc = fma2c_check(p, n_envs, env_base, "rs_fma2c_reset: the handle is not an rs_fma2c_create policy",
+                             "rs_fma2c_reset: need 1 <= n_envs, 0 <= env_base, env_base + n_envs <= max_envs")) return rc;
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    const size_t n = (size_t)n_envs * p->A.K * 4 * FM_L;
+    hipLaunchKernelGGL(rs_fma2c_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->A, env_base, n_envs, clear_fingerprints ? 1 : 0);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_fma2c_set_device_weights(rs_policy_handle p, const float *weights) {
+    if (!p || !weights) return fma2c_refuse("rs_fma2c_set_device_weights: NULL handle or pointer");
+    if (p->kind != POLICY_FMA2C) return fma2c_refuse("rs_fma2c_set_device_weights: the handle is not an rs_fma2c_create policy");
+    p->A.w = weights;
+    return RS_OK;
+}
+
+extern "C" int rs_fma2c_buffer(rs_policy_handle p, int32_t which, void **dev_ptr) {
+    if (!p || !dev_ptr) return fma2c_refuse("rs_fma2c_buffer: NULL handle or pointer");
+    if (p->kind != POLICY_FMA2C) return fma2c_refuse("rs_fma2c_buffer: the handle is not an rs_fma2c_create policy");
+    if (which < 0 || which > 3) return fma2c_refuse("rs_fma2c_buffer: which = 0 state, 1 fingerprints, 2 manager actions, 3 parity");
+    *dev_ptr = which == 0 ? (void *)p->A.state : (which == 1 ? (void *)p->A.fp : (which == 2 ? (void *)p->A.macts : (void *)p->A.parity));
     return RS_OK;
 }
 
@@ -1338,6 +1478,15 @@ extern "C" int rs_group_step(const rs_handle *hs, int32_t n_handles, const rs_gr
                                                  : "rs_group_step: RS_AGENT_MPLIGHT reads RS_BUF_MPLIGHT_FULL, which rs_set_outputs has switched off";
                 return RS_EINVAL;
             }
+        } else if (kind == RS_AGENT_FMA2C) {
+            const rs_policy *pol = agent->policy;
+            if (!pol || pol->kind != POLICY_FMA2C) { h->err = "rs_group_step: RS_AGENT_FMA2C needs an rs_fma2c_create policy"; return RS_EINVAL; }
+            if (pol->A.S != h->K.n_signals || pol->A.O != h->K.n_obs) {
+                h->err = "rs_group_step: RS_AGENT_FMA2C needs a policy built for this scenario (n_signals, n_obs)"; return RS_EINVAL; }
+            if (pol->device != h->device) { h->err = "rs_group_step: the policy's weights live on another device than this handle"; return RS_EINVAL; }
+            if (h->P.env_base < 0 || (int64_t)h->P.env_base + h->n_envs > pol->A.max_envs) {
+                h->err = "rs_group_step: RS_AGENT_FMA2C: env_base + n_envs of the handle exceeds the policy's max_envs"; return RS_EINVAL; }
+            if (!(h->out_mask & OUT_LANE_AGG)) { h->err = "rs_group_step: RS_AGENT_FMA2C reads RS_BUF_LANE_AGG, which rs_set_outputs has switched off"; return RS_EINVAL; }
         } else if (kind != RS_AGENT_NONE && kind != RS_AGENT_RANDOM) { h->err = "rs_group_step: unknown agent kind"; return RS_EINVAL; }
     }
     for (int k = 0; k < n_steps; ++k)
@@ -1356,7 +1505,8 @@ extern "C" int rs_group_step(const rs_handle *hs, int32_t n_handles, const rs_gr
                 const FrapTab &F = agent->policy->F;
                 const void *obs = F.D == 1 ? (const void *)h->O.mplight() : (const void *)h->O.mplight_full();
                 mplight_launch(F, obs, h->n_envs, h->P.env_base, eps, agent->seed, key, nullptr, h->actions, nullptr, nullptr, st);
-            }
+            } else if (kind == RS_AGENT_FMA2C)
+                fma2c_act_launch(agent->policy, h->O.lane_agg(), h->n_envs, h->P.env_base, agent->seed, key, nullptr, Fma2cOut{h->actions, nullptr, nullptr, nullptr}, st);
             if (kind != RS_AGENT_NONE) HIPCHK(h, hipGetLastError());
             const int rc = launch_step(h, st, h->K.step_length * h->ratio, 1);
             if (rc != RS_OK) return rc;

@@ -384,6 +384,55 @@ class MultiSignal(_EnvBase):
         self.sim.close()
 
 
+def fma2c_state_tables(sc, cfg, full=False):
+    """The index tables of states.fma2c / fma2c_full (reference states.py:162-305) over the feature vector F of
+    VecMultiSignal.fma2c_states: per key (signals in all_ts_ids order, then managers) the gather (index, scale) lists, and the
+    lane / fringe / same-region maps the reward tables are built from.  Shared with agents/fma2c.py: FMA2CLayout."""
+    sup, alpha = cfg['supervisors'], float(cfg['alpha'])
+    ids = list(sc.signal_ids)
+    O = sc.n_obs
+    lane_pos = {l: i for i, l in enumerate(sc.obs_lane_ids)}
+    lanes = {sid: list(sc.obs_lane_ids[int(sc.sig_obs_start[i]):int(sc.sig_obs_start[i + 1])]) for i, sid in enumerate(ids)}
+    meta = sc.signal_meta
+    fringes = {mgr: [] for mgr in cfg['management']}           # states._fma2c_regions
+    for sid in ids:
+        for direction, nb in meta[sid]['downstream'].items():
+            if nb is None or sup[nb] != sup[sid]:
+                inbound = meta[sid]['inbounds_fr_direction'].get(direction)
+                if inbound is not None:
+                    fringes[sup[sid]] += inbound
+    same_region = {sid: [nb for nb in meta[sid]['downstream'].values() if nb is not None and sup[nb] == sup[sid]] for sid in ids}
+    keys = list(ids) + list(cfg['management'].keys())
+    # states: feature vector F = [clip(wave / norm_wave), clip(max_wait / norm_wait)] per observed lane
+    s_idx, s_scale = {}, {}
+    mgr_terms = {mgr: ([lane_pos[l] for l in fl], [1.0] * len(fl)) for mgr, fl in fringes.items()}
+    # feature blocks of F: wave (0), [full: total_wait / 28 (1), speed term (2)], max_wait (last)
+    nb_blocks = 3 if full else 1
+
+    def own_idx(sid_):      # fma2c_full interleaves wave, total_wait / 28 and the drq_norm speed term per lane (states.py:232-305)
+        out_ = []
+        for l in lanes[sid_]:
+            out_ += [b * O + lane_pos[l] for b in range(nb_blocks)]
+        return out_
+    for sid in ids:
+        idx = own_idx(sid)
+        sc_ = [1.0] * len(idx)
+        for nb in same_region[sid]:
+            ni = own_idx(nb)
+            idx += ni
+            sc_ += [alpha] * len(ni)
+        idx += [nb_blocks * O + lane_pos[l] for l in lanes[sid]]
+        sc_ += [1.0] * len(lanes[sid])
+        s_idx[sid], s_scale[sid] = idx, sc_
+    for mgr in cfg['management']:
+        idx, sc_ = list(mgr_terms[mgr][0]), list(mgr_terms[mgr][1])
+        for n in cfg['management_neighbors'][mgr]:
+            idx += mgr_terms[n][0]
+            sc_ += [alpha] * len(mgr_terms[n][0])
+        s_idx[mgr], s_scale[mgr] = idx, sc_
+    return keys, s_idx, s_scale, lanes, lane_pos, fringes, same_region
+
+
 class VecMultiSignal:
     """N lock-step environments on one GPU; observations / rewards are zero-copy torch tensors over the
     library-owned device buffers (the agent boundary), actions are an int32 [N, S] tensor or None (actions
@@ -456,45 +505,7 @@ class VecMultiSignal:
         sup, alpha = cfg['supervisors'], float(cfg['alpha'])
         ids = self.all_ts_ids
         O, S = sc.n_obs, self.n_signals
-        lane_pos = {l: i for i, l in enumerate(sc.obs_lane_ids)}
-        lanes = {sid: list(sc.obs_lane_ids[int(sc.sig_obs_start[i]):int(sc.sig_obs_start[i + 1])]) for i, sid in enumerate(ids)}
-        meta = sc.signal_meta
-        fringes = {mgr: [] for mgr in cfg['management']}           # states._fma2c_regions
-        for sid in ids:
-            for direction, nb in meta[sid]['downstream'].items():
-                if nb is None or sup[nb] != sup[sid]:
-                    inbound = meta[sid]['inbounds_fr_direction'].get(direction)
-                    if inbound is not None:
-                        fringes[sup[sid]] += inbound
-        same_region = {sid: [nb for nb in meta[sid]['downstream'].values() if nb is not None and sup[nb] == sup[sid]] for sid in ids}
-        keys = list(ids) + list(cfg['management'].keys())
-        # states: feature vector F = [clip(wave / norm_wave), clip(max_wait / norm_wait)] per observed lane
-        s_idx, s_scale = {}, {}
-        mgr_terms = {mgr: ([lane_pos[l] for l in fl], [1.0] * len(fl)) for mgr, fl in fringes.items()}
-        # feature blocks of F: wave (0), [full: total_wait / 28 (1), speed term (2)], max_wait (last)
-        nb_blocks = 3 if full else 1
-
-        def own_idx(sid_):      # fma2c_full interleaves wave, total_wait / 28 and the drq_norm speed term per lane (states.py:232-305)
-            out_ = []
-            for l in lanes[sid_]:
-                out_ += [b * O + lane_pos[l] for b in range(nb_blocks)]
-            return out_
-        for sid in ids:
-            idx = own_idx(sid)
-            sc_ = [1.0] * len(idx)
-            for nb in same_region[sid]:
-                ni = own_idx(nb)
-                idx += ni
-                sc_ += [alpha] * len(ni)
-            idx += [nb_blocks * O + lane_pos[l] for l in lanes[sid]]
-            sc_ += [1.0] * len(lanes[sid])
-            s_idx[sid], s_scale[sid] = idx, sc_
-        for mgr in cfg['management']:
-            idx, sc_ = list(mgr_terms[mgr][0]), list(mgr_terms[mgr][1])
-            for n in cfg['management_neighbors'][mgr]:
-                idx += mgr_terms[n][0]
-                sc_ += [alpha] * len(mgr_terms[n][0])
-            s_idx[mgr], s_scale[mgr] = idx, sc_
+        keys, s_idx, s_scale, lanes, lane_pos, fringes, same_region = fma2c_state_tables(sc, cfg, full)
         dev = self.tensor('lane_agg').device
         st = {k: (torch.as_tensor(s_idx[k], dtype=torch.long, device=dev), torch.as_tensor(s_scale[k], dtype=torch.float32, device=dev))
               for k in keys}

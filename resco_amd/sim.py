@@ -41,6 +41,10 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_idqn_pack_weights', 'rs_dqn_sync_target', 'rs_mplight_dqn_sync_target', 'rs_group_train',
                'rs_ppo_perm', 'rs_ippo_pack_weights', 'rs_group_ppo_train']
 
+# the FMA2C entry points (include/resco_sim.h: rs_fma2c_*)
+FMA2C_SYMBOLS = ['rs_fma2c_create', 'rs_fma2c_act', 'rs_fma2c_value', 'rs_fma2c_reset', 'rs_fma2c_set_device_weights', 'rs_fma2c_buffer',
+                 'rs_fma2c_destroy']
+
 _lib = None
 
 
@@ -129,6 +133,15 @@ def bind(L):
         L.rs_ppo_perm.argtypes = [i32, i32, u32, u32, vp, vp]
         L.rs_ippo_pack_weights.argtypes = [vp, vp, vp]
         L.rs_group_ppo_train.argtypes = [vp, i32, vp, i32]
+    if hasattr(L, 'rs_fma2c_create'):
+        L.rs_fma2c_create.argtypes = [i32, vp, vp, i32, C.POINTER(vp)]
+        L.rs_fma2c_act.argtypes = [vp, vp, i32, i32, u32, u32, vp, vp, vp, vp, vp, vp]
+        L.rs_fma2c_value.argtypes = [vp, vp, i32, i32, vp, vp]
+        L.rs_fma2c_reset.argtypes = [vp, i32, i32, i32, vp]
+        L.rs_fma2c_set_device_weights.argtypes = [vp, vp]
+        L.rs_fma2c_buffer.argtypes = [vp, i32, C.POINTER(vp)]
+        L.rs_fma2c_destroy.argtypes = [vp]
+        L.rs_fma2c_destroy.restype = None
     if hasattr(L, 'rs_default_block'):      # (the host emulation of the CPU tests exports only what it implements)
         L.rs_default_block.argtypes = [i32, i32, i32]
         L.rs_default_block.restype = i32
@@ -155,13 +168,20 @@ def load_library():
     return _lib
 
 
-AGENT = {'none': 0, 'random': 1, 'maxwave': 2, 'maxpressure': 3, 'idqn': 4, 'mplight': 5, 'ippo': 6}      # enum rs_agent
+AGENT = {'none': 0, 'random': 1, 'maxwave': 2, 'maxpressure': 3, 'idqn': 4, 'mplight': 5, 'ippo': 6, 'fma2c': 7}      # enum rs_agent
 
 
 class GroupAgent(C.Structure):
     """ctypes mirror of rs_group_agent (include/resco_sim.h)"""
     _fields_ = [('kind', C.c_int32), ('step_key', C.c_uint32), ('policy', C.c_void_p), ('mode', C.c_int32),
                 ('epsilon', C.c_float), ('epsilon_step', C.c_float), ('seed', C.c_uint32)]
+
+
+class Fma2cDesc(C.Structure):
+    """ctypes mirror of rs_fma2c_desc (include/resco_sim.h); ARRAYS: the pointer fields in header order"""
+    ARRAYS = ('n_a', 'n_s', 'n_w', 'n_f', 'gather_off', 'gather_idx', 'gather_scale', 'fp_off', 'fp_src', 'mgr_off', 'mgr_src')
+    _fields_ = [(k, C.c_int32) for k in ('K', 'M', 'S', 'n_obs', 'full')] + \
+               [(k, C.c_float) for k in ('norm_wave', 'clip_wave', 'norm_wait', 'clip_wait')] + [(k, C.c_void_p) for k in ARRAYS]
 
 
 Rollout = RolloutStruct     # ctypes mirror of rs_rollout (include/resco_sim.h): the device buffers of one handle's trajectory segment
@@ -207,7 +227,7 @@ class MPLightRing(C.Structure):
 class SimGroup:
     """The handles ("pipes") of one GPU stepped together by ONE call through the C ABI per env-step (rs_group_step): for every
     pipe the agent's kernel and the step kernel on the pipe's own stream.  agent: 'none' | 'random' | 'maxwave' | 'maxpressure' |
-    'idqn' | 'mplight' (policy = an rs_policy_handle: FusedIDQN.handle, FusedMPLight.handle)."""
+    'idqn' | 'mplight' | 'fma2c' (policy = an rs_policy_handle: FusedIDQN.handle, FusedMPLight.handle, FusedFMA2C.handle)."""
 
     def __init__(self, sims):
         self.sims = list(sims)
@@ -223,6 +243,8 @@ class SimGroup:
             for s in self.sims:
                 s.require_output('mplight' if agent == 'maxpressure' else 'wave')
                 s._ensure_maxwave_tables(1 if agent == 'maxpressure' else 0)
+        if agent == 'fma2c' and not hasattr(self._lib, 'rs_fma2c_create'):
+            raise RuntimeError('the loaded library has no rs_fma2c_*: rebuild it (there is no CPU fallback)')
         rc = self._lib.rs_group_step(self._hs, len(self.sims), C.byref(a), int(n_steps))
         if rc != 0:
             msgs = [m.decode() for m in (self._lib.rs_last_error(s._h) for s in self.sims) if m]

@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""FMA2C training loop on the GPU: HIP simulator -> fused FMA2C acting kernel on RS_BUF_LANE_AGG (rs_fma2c_act: input rows, both
+LSTM actor-critic nets of every manager and worker, the draw; state and fingerprints stay on the device) -> rs_step -> rewards.fma2c
+for all agents (VecMultiSignal.fma2c_rewards) -> the A2C learner in PyTorch (resco_amd/agents/fma2c.py: A2CLearner, an update every
+120 steps or at the episode's end) -> weights re-packed on the device.  The reference's FMA2C (agents/fma2c.py, agents/ma2c.py,
+config/agent_config.py:114-138) batched over N environments.
+
+    python tools/fma2c_train.py [--full] [--steps-per-episode n] [map] [n_envs] [episodes] [seed]
+
+Prints one JSON line per episode (mean episode return per agent, average trip delay as utils/readXML.py computes it, the last
+update's mean loss, env-steps/s including learning) and a final line with the best training episode and the on-device random policy
+on the same demand.  --full: FMA2CFULL (states.fma2c_full / rewards.fma2c_full).  --steps-per-episode cuts every episode short (smoke runs)."""
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from resco_amd.agents.fma2c import A2CLearner, BatchedFMA2C, FMA2CLayout, FusedFMA2C      # noqa: E402
+from resco_amd.config.agent_config import agent_configs                                 # noqa: E402
+from resco_amd.config.mdp_config import activate                                        # noqa: E402
+from resco_amd.multi_signal import VecMultiSignal                                       # noqa: E402
+
+
+def delay(env):
+    return float(env.sim.trip_delay().mean()), float(env.sim.stats()['arrived'].mean())
+
+
+def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_episode=0, quiet=False, keep=None):
+    """keep: a dict that receives net, policy, learner and env instead of having them closed (tests)"""
+    cfg = agent_configs['FMA2CFULL' if full else 'FMA2C']
+    activate('FMA2CFull' if full else 'FMA2C', map_name)
+    env = VecMultiSignal(map_name, n, states=(), rewards=(), seed=0, max_distance=cfg['max_distance'], outputs=('lane_agg', 'lane_arrivals'))
+    steps = min(env.horizon_steps, steps_per_episode) if steps_per_episode else env.horizon_steps
+    layout = FMA2CLayout(env.scenario, full)
+    net = BatchedFMA2C(layout).init_like_reference(seed).cuda()
+    policy = FusedFMA2C(net, n, seed=7 + seed)
+    learner = A2CLearner(net, n, batch_size=cfg['batch_size'], gamma=cfg['gamma'], lr=cfg['lr_init'], alpha=cfg['rmsp_alpha'],
+                         eps=cfg['rmsp_epsilon'], max_grad_norm=cfg['max_grad_norm'], value_coef=cfg['value_coef'],
+                         entropy_coef=cfg['entropy_coef_init'], reward_norm=cfg['reward_norm'], reward_clip=cfg['reward_clip'])
+    policy.refresh_on_device()
+    lane_agg, actions = env.tensor('lane_agg'), env.tensor('actions')
+    state, macts = policy.buffer('state'), policy.buffer('mgr_actions')
+
+    env.sim.set_seed(12345)
+    env.reset()
+    for k in range(steps):
+        env.act_random(k)
+        env.step(None)
+    rnd_delay, _ = delay(env)
+
+    rows, t = [], 0
+    for ep in range(episodes):
+        env.sim.set_seed(1000 + ep + 7919 * seed)
+        env.reset()
+        policy.reset()                      # model.reset() at the episode's end (ma2c.py:144-146); the fingerprints stay, as there
+        ret = torch.zeros(n, layout.K, device='cuda')
+        loss = None
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k in range(steps):
+            out = policy.act(lane_agg, step_key=t, actions=actions)
+            acts = torch.cat([macts, out['actions']], dim=1).long()
+            env.step(None)
+            done = k == steps - 1
+            r = env.fma2c_rewards(full)
+            rew = torch.stack([r[a] for a in layout.agents], dim=1)
+            ret += rew
+            res = learner.observe(out['rows'], acts, rew, out['value'], done, state, lambda: policy.value(lane_agg))
+            if res is not None:
+                loss = res
+                policy.refresh_on_device()
+            t += 1
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        d, arrived = delay(env)
+        rows.append(dict(episode=ep, mean_return=float(ret.mean()), avg_delay_s=round(d, 2), arrived_per_env=round(arrived, 1),
+                         updates=learner.updates, loss=float(loss.mean()) if loss is not None else None, env_steps_per_s=round(n * steps / dt)))
+        if not quiet:
+            print(json.dumps(rows[-1]), flush=True)
+    final = dict(map=map_name, agent='FMA2CFULL' if full else 'FMA2C', envs=n, episodes=episodes, steps_per_episode=steps, seed=seed,
+                 best_training_episode_delay_s=min(r['avg_delay_s'] for r in rows), random_avg_delay_s=round(rnd_delay, 2))
+    if not quiet:
+        print(json.dumps(final), flush=True)
+    if keep is not None:
+        keep.update(net=net, policy=policy, learner=learner, env=env, layout=layout, loss=loss)
+    else:
+        policy.close()
+        env.close()
+    return rows, final
+
+
+if __name__ == '__main__':
+    a = sys.argv[1:]
+    full = '--full' in a
+    a = [x for x in a if x != '--full']
+    spe = 0
+    if '--steps-per-episode' in a:
+        i = a.index('--steps-per-episode')
+        spe = int(a[i + 1])
+        del a[i:i + 2]
+    main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 30,
+         int(a[3]) if len(a) > 3 else 0, full=full, steps_per_episode=spe)
