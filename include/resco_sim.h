@@ -719,6 +719,46 @@ int rs_fma2c_set_device_weights(rs_policy_handle p, const float *weights);
 int rs_fma2c_buffer(rs_policy_handle p, int32_t which, void **dev_ptr);
 void rs_fma2c_destroy(rs_policy_handle p);
 
+/* ---- FMA2C: the A2C update on the device (resco_amd/csrc/resco_fma2c_train.h) -------------------------------------------------
+ * Replaces A2CLearner.update of resco_amd/agents/fma2c.py (the reference's ma2c.py:208-212, 286-306, 383-398, 566-612) for all K
+ * agents and n_envs lock-step environments: returns and advantages, the re-run of the segment from the learner's start state, the
+ * loss, BPTT through both LSTM nets, the per-agent global-norm clip and TF1's RMSProp (ms starts at ONE, eps inside the root), all in
+ * fp32 kernels; no floating-point atomics, so two runs give the same bits.
+ *
+ * rs_fma2c_learn_config: gamma, lr, alpha, eps, max_grad_norm (0: no clip), value_coef, entropy_coef, reward_norm (0: none),
+ * reward_clip (0: none); workspace_bytes caps the re-run's workspace (0: 4 GiB).  The update runs the agents in groups of as many as
+ * the workspace holds (one agent needs 2 * t_max * n_envs * 904 floats); the results do not depend on the grouping.
+ *
+ * rs_fma2c_learn_create: the learner owns the weights (a copy of the policy's CURRENT vector, in its packed layout), ms (ones), the
+ * gradients, states_bw float [n_envs][K][4][64] (zeros: the state the next segment is re-run from) and the workspace, and points
+ * the policy at its weights: the policy acts with what the learner has just written, no re-pack.  n_envs must be the policy's
+ * max_envs.  The policy must outlive the learner.
+ * Segment (device pointers): rows f32 [T][n_envs][K][W] (rs_fma2c_act's rows_out), acts i32 [T][n_envs][K] (managers first), rewards
+ * f32 [T][n_envs][K] RAW (normalised and clipped here), values f32 [T][n_envs][K] the acting values, dones i32 [T + 1] (entry t: the
+ * pre-step done of step t; entry T: the post-step done of the last step), R_boot f32 [n_envs][K] the bootstrap value.
+ * rs_fma2c_learn_grad: returns, advantages and the un-clipped gradients of the per-agent losses into the gradient buffer; loss_out:
+ * NULL or device f32 [K].  rs_fma2c_learn_step: norm, clip and RMSProp from the gradient buffer.  rs_fma2c_learn_update: grad, step,
+ * then states_bw <- states_fw (device f32 [n_envs][K][4][64], the acting state now) in stream order.  rs_fma2c_learn_reset: zeroes
+ * states_bw (model.reset() at done).  rs_fma2c_learn_buffer: which = 0 weights, 1 ms, 2 gradients (f32 [n], n = the packed vector's
+ * length), 3 states_bw, 4 returns, 5 advantages (f32 [t_max][n_envs][K], the first T entries), 6 the per-agent gradient norms,
+ * 7 the clip scales (f32 [K]).  rs_fma2c_learn_destroy copies the weights into the policy's own vector and points the policy back at it.
+ * Refusals (RS_EINVAL, text in rs_last_error(NULL), nothing launched): NULL handles or pointers; a policy that is not
+ * rs_fma2c_create's; T < 1 or T > t_max; n_envs != the policy's max_envs; a workspace cap below one agent's need. */
+typedef struct rs_fma2c_learn_config {
+    double gamma, lr, alpha, eps, max_grad_norm, value_coef, entropy_coef, reward_norm, reward_clip;
+    int64_t workspace_bytes;
+} rs_fma2c_learn_config;
+typedef struct rs_fma2c_learn *rs_fma2c_learn_handle;
+int rs_fma2c_learn_create(rs_policy_handle policy, const rs_fma2c_learn_config *config, int32_t n_envs, int32_t t_max, rs_fma2c_learn_handle *out);
+int rs_fma2c_learn_grad(rs_fma2c_learn_handle l, const float *rows, const int32_t *acts, const float *rewards, const float *values,
+                        const int32_t *dones, const float *R_boot, int32_t T, float *loss_out, void *stream);
+int rs_fma2c_learn_step(rs_fma2c_learn_handle l, void *stream);
+int rs_fma2c_learn_update(rs_fma2c_learn_handle l, const float *rows, const int32_t *acts, const float *rewards, const float *values,
+                          const int32_t *dones, const float *R_boot, int32_t T, float *loss_out, const float *states_fw, void *stream);
+int rs_fma2c_learn_reset(rs_fma2c_learn_handle l, void *stream);
+int rs_fma2c_learn_buffer(rs_fma2c_learn_handle l, int32_t which, void **dev_ptr);
+void rs_fma2c_learn_destroy(rs_fma2c_learn_handle l);
+
 /* static facts */
 int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal);
 

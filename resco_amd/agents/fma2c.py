@@ -393,6 +393,9 @@ class FusedFMA2C:
 
     def close(self):
         if getattr(self, '_h', None) is not None:
+            learner = getattr(self, '_learner', None)       # a FusedA2CLearner borrows this handle: it goes first
+            if learner is not None and learner() is not None:
+                learner().close()
             self._lib.rs_fma2c_destroy(self._h)
             self._h = None
 
@@ -431,18 +434,21 @@ class FusedFMA2C:
         assert lane_agg.is_cuda and lane_agg.dtype == torch.float32 and lane_agg.is_contiguous() and tuple(lane_agg.shape[1:]) == (self.L.O, 5)
         return lane_agg.shape[0], int(env_base), (torch_stream(self.device) if stream is None else stream)
 
-    def act(self, lane_agg, step_key=0, env_base=0, actions=None, want=('pi', 'value', 'rows'), dyn=None, stream=None):
+    def act(self, lane_agg, step_key=0, env_base=0, actions=None, want=('pi', 'value', 'rows'), dyn=None, stream=None, out=None):
         """one act of all agents on lane_agg [N, O, 5] (rows env_base .. of the library's state).  Returns dict(actions int32 [N, S]
-        = the workers' local actions, and pi [N, K, 8] / value [N, K] / rows [N, K, W] as asked in `want`)."""
+        = the workers' local actions, and pi [N, K, 8] / value [N, K] / rows [N, K, W] as asked in `want`).  out: optional dict of
+        caller-owned contiguous float32 tensors for 'pi' / 'value' / 'rows' (FusedA2CLearner.slot()), written instead of fresh ones."""
         N, eb, st = self._args(lane_agg, env_base, stream)
         dev, L = lane_agg.device, self.L
+        given, shapes = out or {}, {'pi': (N, L.K, A_MAX), 'value': (N, L.K), 'rows': (N, L.K, L.W)}
         out = {'actions': actions if actions is not None else torch.empty(N, L.S, dtype=torch.int32, device=dev)}
-        if 'pi' in want:
-            out['pi'] = torch.empty(N, L.K, A_MAX, device=dev)
-        if 'value' in want:
-            out['value'] = torch.empty(N, L.K, device=dev)
-        if 'rows' in want:
-            out['rows'] = torch.empty(N, L.K, L.W, device=dev)
+        for k in ('pi', 'value', 'rows'):
+            if k in given:
+                g = given[k]
+                assert g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == shapes[k], k
+                out[k] = g
+            elif k in want:
+                out[k] = torch.empty(*shapes[k], device=dev)
         ptr = lambda k: out[k].data_ptr() if k in out else None
         self._check(self._lib.rs_fma2c_act(self._h, lane_agg.data_ptr(), N, eb, self.seed, int(step_key) & 0xFFFFFFFF,
                                            dyn.data_ptr() if dyn is not None else None, ptr('actions'), ptr('pi'), ptr('value'), ptr('rows'), st),

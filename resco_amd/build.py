@@ -17,7 +17,7 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 #   v_cndmask pairs (and the s_nop the pair needs on gfx950): +0.6-0.9 % (profiles/r06_ab_linkrec_nnan.txt); results bit-identical
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fno-honor-nans', '-mllvm', '-disable-machine-licm', '-fPIC', '-shared',
          '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(HERE, 'csrc')]
-_DEPS = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('resco_host.h', 'resco_step.h', 'resco_tables.h', 'resco_policy.h', 'resco_frap.h', 'resco_fma2c.h', 'resco_ppo.h', 'resco_train.h', 'resco_ppo_train.h', 'resco_dqn_train.h', 'resco_frap_train.h', 'resco_group_train.h', 'resco_ppo_loop.h')] + \
+_DEPS = [SRC] + [os.path.join(HERE, 'csrc', f) for f in ('resco_host.h', 'resco_step.h', 'resco_tables.h', 'resco_policy.h', 'resco_frap.h', 'resco_fma2c.h', 'resco_fma2c_train.h', 'resco_ppo.h', 'resco_train.h', 'resco_ppo_train.h', 'resco_dqn_train.h', 'resco_frap_train.h', 'resco_group_train.h', 'resco_ppo_loop.h')] + \
         [os.path.join(ROOT, 'include', f) for f in ('resco_sim.h', 'resco_model.h')]
 
 

@@ -118,6 +118,7 @@ __device__ unsigned long long *g_sec_prof;
 #include "resco_frap_train.h"
 #include "resco_group_train.h"
 #include "resco_ppo_loop.h"
+#include "resco_fma2c_train.h"
 
 // ------------------------------------------------------------------------------------------------ kernels
 // The tables / state / output descriptors live in ONE constant block in device memory (StepArgs): passed by value they
@@ -709,6 +710,7 @@ struct rs_policy {
     FrapTab F{};                // MPLight
     Fma2cTab A{};               // FMA2C
     int fm_lds = 0;             // FMA2C: dynamic LDS of the kernel in bytes
+    const float *fm_own_w = nullptr;    // FMA2C: the create-time copy of the packed weights (A.w may point at a caller's or a learner's vector)
     std::vector<void *> allocs;
 };
 
@@ -1254,6 +1256,7 @@ extern "C" int rs_fma2c_create(int32_t device_id, const rs_fma2c_desc *d, const 
         rs_fma2c_destroy(p);
         return RS_EHIP;
     }
+    p->fm_own_w = A.w;
     *out = p;
     return RS_OK;
 }
@@ -1315,6 +1318,168 @@ extern "C" int rs_fma2c_buffer(rs_policy_handle p, int32_t which, void **dev_ptr
     if (p->kind != POLICY_FMA2C) return fma2c_refuse("rs_fma2c_buffer: the handle is not an rs_fma2c_create policy");
     if (which < 0 || which > 3) return fma2c_refuse("rs_fma2c_buffer: which = 0 state, 1 fingerprints, 2 manager actions, 3 parity");
     *dev_ptr = which == 0 ? (void *)p->A.state : (which == 1 ? (void *)p->A.fp : (which == 2 ? (void *)p->A.macts : (void *)p->A.parity));
+    return RS_OK;
+}
+
+// ---- FMA2C: the A2C update (resco_fma2c_train.h).  The learner owns weights, ms, gradients, states_bw and every workspace.
+struct rs_fma2c_learn : TrainHandle {
+    rs_policy *pol = nullptr;
+    rs_fma2c_learn_config cfg{};
+    int n_envs = 0, t_max = 0;
+    size_t n = 0, ws_floats = 0;
+    float *w = nullptr, *ms = nullptr, *grad = nullptr, *states_bw = nullptr, *ws = nullptr, *wT = nullptr, *part = nullptr,
+          *ret = nullptr, *adv = nullptr, *sqpart = nullptr, *norms = nullptr, *scales = nullptr, *loss = nullptr;
+    double *lossp = nullptr;
+};
+
+__global__ void ft_fill_kernel(float *p, size_t n, float v) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < n) p[idx] = v;
+}
+
+static int ft_segment_lds(int W) { return (int)(sizeof(float) * ((size_t)FM_TM * (W + 1) + FM_TM * FM_HS + FM_TM * FM_ZS + FM_TM * FM_AMAX + FM_TM * FT_DS)); }
+
+extern "C" void rs_fma2c_learn_destroy(rs_fma2c_learn_handle l) {
+    if (!l) return;
+    (void)hipSetDevice(l->device);
+    (void)hipDeviceSynchronize();
+    if (l->pol && l->w && l->pol->fm_own_w) {
+        (void)hipMemcpy((void *)l->pol->fm_own_w, l->w, l->n * sizeof(float), hipMemcpyDeviceToDevice);
+        l->pol->A.w = l->pol->fm_own_w;
+    }
+    train_destroy(l);
+}
+
+extern "C" int rs_fma2c_learn_create(rs_policy_handle p, const rs_fma2c_learn_config *cfg, int32_t n_envs, int32_t t_max, rs_fma2c_learn_handle *out) {
+    if (!out) return fma2c_refuse("rs_fma2c_learn_create: out is NULL");
+    *out = nullptr;
+    if (!p || !cfg) return fma2c_refuse("rs_fma2c_learn_create: NULL policy or config");
+    if (p->kind != POLICY_FMA2C) return fma2c_refuse("rs_fma2c_learn_create: the handle is not an rs_fma2c_create policy");
+    if (n_envs != p->A.max_envs) return fma2c_refuse("rs_fma2c_learn_create: n_envs must equal the policy's max_envs");
+    if (t_max < 1) return fma2c_refuse("rs_fma2c_learn_create: need t_max >= 1");
+    if (cfg->workspace_bytes < 0) return fma2c_refuse("rs_fma2c_learn_create: workspace_bytes < 0");
+    const Fma2cTab &A = p->A;
+    const size_t K = A.K, R = (size_t)t_max * n_envs, per_agent = 2 * R * FT_SLOT * sizeof(float);
+    const size_t cap = cfg->workspace_bytes ? (size_t)cfg->workspace_bytes : ((size_t)4 << 30);
+    if (cap < per_agent) return fma2c_refuse("rs_fma2c_learn_create: the workspace cap is below one agent's need (2 * t_max * n_envs * 904 floats)");
+    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
+    rs_fma2c_learn *l = new (std::nothrow) rs_fma2c_learn();
+    if (!l) return RS_ENOMEM;
+    l->device = p->device; l->pol = nullptr; l->cfg = *cfg; l->n_envs = n_envs; l->t_max = t_max;
+    l->n = Fma2cOff(A.K, A.NS, A.NW, A.NF).n;
+    const size_t kg = cap / per_agent < K ? cap / per_agent : K;       // the agents of a group at T = t_max
+    l->ws_floats = kg * 2 * R * FT_SLOT;
+    const size_t tiles = ((size_t)n_envs + FM_TM - 1) / FM_TM, nb = l->n * sizeof(float), E = (size_t)n_envs;
+    const size_t nT = K * 2 * (FM_HID + FM_L) * 4 * FM_L;
+    if (!l->alloc((void **)&l->w, nb) || !l->alloc((void **)&l->ms, nb) || !l->alloc((void **)&l->grad, nb) ||
+        !l->alloc((void **)&l->states_bw, E * K * 4 * FM_L * sizeof(float)) || !l->alloc((void **)&l->ws, l->ws_floats * sizeof(float)) ||
+        !l->alloc((void **)&l->wT, nT * sizeof(float)) || !l->alloc((void **)&l->part, (size_t)FT_PMAX * nb) ||
+        !l->alloc((void **)&l->lossp, tiles * K * 6 * sizeof(double)) || !l->alloc((void **)&l->ret, R * K * sizeof(float)) ||
+        !l->alloc((void **)&l->adv, R * K * sizeof(float)) || !l->alloc((void **)&l->sqpart, K * FT_NT * 2 * sizeof(float)) ||
+        !l->alloc((void **)&l->norms, K * sizeof(float)) || !l->alloc((void **)&l->scales, K * sizeof(float)) || !l->alloc((void **)&l->loss, K * sizeof(float))) {
+        g_create_err = "rs_fma2c_learn_create: device allocation failed";
+        train_destroy(l);
+        return RS_ENOMEM;
+    }
+    bool ok = hipMemcpy(l->w, A.w, nb, hipMemcpyDeviceToDevice) == hipSuccess && hipMemset(l->grad, 0, nb) == hipSuccess &&
+              hipMemset(l->states_bw, 0, E * K * 4 * FM_L * sizeof(float)) == hipSuccess && hipMemset(l->lossp, 0, tiles * K * 6 * sizeof(double)) == hipSuccess &&
+              hipMemset(l->ret, 0, R * K * sizeof(float)) == hipSuccess && hipMemset(l->adv, 0, R * K * sizeof(float)) == hipSuccess &&
+              hipMemset(l->norms, 0, K * sizeof(float)) == hipSuccess && hipMemset(l->scales, 0, K * sizeof(float)) == hipSuccess;
+    hipLaunchKernelGGL(ft_fill_kernel, dim3((unsigned)((l->n + 255) / 256)), dim3(256), 0, 0, l->ms, l->n, 1.0f);
+    ok = ok && hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+         hipFuncSetAttribute((const void *)ft_segment_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ft_segment_lds(FM_W_MAX)) == hipSuccess;
+    if (!ok) {
+        g_create_err = "rs_fma2c_learn_create: device initialisation failed";
+        train_destroy(l);
+        return RS_EHIP;
+    }
+    l->pol = p;
+    p->A.w = l->w;
+    *out = l;
+    return RS_OK;
+}
+
+static int ft_grad_launch(rs_fma2c_learn *l, const float *rows, const int32_t *acts, const float *rewards, const float *values, const int32_t *dones,
+                          const float *R_boot, int T, float *loss_out, hipStream_t st) {
+    const Fma2cTab &A = l->pol->A;
+    FtRun S{};
+    S.w = l->w; S.wT = l->wT; S.ws = l->ws; S.part = l->part; S.grad = l->grad; S.lossp = l->lossp;
+    S.rows = rows; S.acts = acts; S.rewards = rewards; S.values = values; S.R_boot = R_boot; S.dones = dones; S.state0 = l->states_bw;
+    S.ret = l->ret; S.adv = l->adv;
+    S.gamma = (float)l->cfg.gamma; S.reward_norm = (float)l->cfg.reward_norm; S.reward_clip = (float)l->cfg.reward_clip;
+    S.value_coef = (float)l->cfg.value_coef; S.entropy_coef = (float)l->cfg.entropy_coef;
+    S.T = T; S.N = l->n_envs; S.n = l->n;
+    const long long R = (long long)T * l->n_envs;
+    int per = 0;
+    S.P = ft_splits(R, &per); S.per = per;
+    const int K = A.K, tiles = (l->n_envs + FM_TM - 1) / FM_TM, jobs = ft_jobs(A.NS, A.NW, A.NF);
+    size_t kg = l->ws_floats / (2 * (size_t)R * FT_SLOT);
+    kg = kg > (size_t)K ? (size_t)K : kg;
+    hipLaunchKernelGGL(ft_returns_kernel, dim3((unsigned)((l->n_envs * K + 255) / 256)), dim3(256), 0, st, A, S);
+    const size_t nT = (size_t)K * 2 * (FM_HID + FM_L) * 4 * FM_L;
+    hipLaunchKernelGGL(ft_transpose_kernel, dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, st, A, S);
+    for (int k0 = 0; k0 < K; k0 += (int)kg) {
+        S.k0 = k0; S.Kg = K - k0 < (int)kg ? K - k0 : (int)kg;
+        hipLaunchKernelGGL(ft_segment_kernel, dim3(tiles, S.Kg, 2), dim3(256), ft_segment_lds(A.W), st, A, S);
+        hipLaunchKernelGGL(ft_wgrad_kernel, dim3((jobs + 3) / 4, S.Kg * 2, S.P), dim3(256), 0, st, A, S);
+    }
+    hipLaunchKernelGGL(ft_reduce_kernel, dim3((unsigned)((l->n + 255) / 256)), dim3(256), 0, st, S);
+    hipLaunchKernelGGL(ft_loss_kernel, dim3((K + 63) / 64), dim3(64), 0, st, A, S, loss_out ? loss_out : l->loss);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+static int ft_step_launch(rs_fma2c_learn *l, hipStream_t st) {
+    const Fma2cTab &A = l->pol->A;
+    FtStep Q{l->w, l->ms, l->sqpart, l->norms, l->scales, l->grad, l->cfg.lr, l->cfg.alpha, l->cfg.eps, l->cfg.max_grad_norm};
+    hipLaunchKernelGGL(ft_norm_kernel, dim3(A.K, FT_NT), dim3(256), 0, st, A, Q);
+    hipLaunchKernelGGL(ft_rmsprop_kernel, dim3(A.K, FT_NT, 16), dim3(256), 0, st, A, Q);
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+static int ft_check_segment(const char *name, rs_fma2c_learn_handle l, const void *rows, const void *acts, const void *rewards, const void *values,
+                            const void *dones, const void *R_boot, int T) {
+    static thread_local char msg[160];
+    if (!l || !rows || !acts || !rewards || !values || !dones || !R_boot) { snprintf(msg, sizeof msg, "%s: NULL handle or pointer", name); return fma2c_refuse(msg); }
+    if (T < 1 || T > l->t_max) { snprintf(msg, sizeof msg, "%s: need 1 <= T <= t_max", name); return fma2c_refuse(msg); }
+    return RS_OK;
+}
+
+extern "C" int rs_fma2c_learn_grad(rs_fma2c_learn_handle l, const float *rows, const int32_t *acts, const float *rewards, const float *values,
+                                   const int32_t *dones, const float *R_boot, int32_t T, float *loss_out, void *stream) {
+    if (int rc = ft_check_segment("rs_fma2c_learn_grad", l, rows, acts, rewards, values, dones, R_boot, T)) return rc;
+    if (hipSetDevice(l->device) != hipSuccess) return RS_EHIP;
+    return ft_grad_launch(l, rows, acts, rewards, values, dones, R_boot, T, loss_out, (hipStream_t)stream);
+}
+
+extern "C" int rs_fma2c_learn_step(rs_fma2c_learn_handle l, void *stream) {
+    if (!l) return fma2c_refuse("rs_fma2c_learn_step: NULL handle");
+    if (hipSetDevice(l->device) != hipSuccess) return RS_EHIP;
+    return ft_step_launch(l, (hipStream_t)stream);
+}
+
+extern "C" int rs_fma2c_learn_update(rs_fma2c_learn_handle l, const float *rows, const int32_t *acts, const float *rewards, const float *values,
+                                     const int32_t *dones, const float *R_boot, int32_t T, float *loss_out, const float *states_fw, void *stream) {
+    if (int rc = ft_check_segment("rs_fma2c_learn_update", l, rows, acts, rewards, values, dones, R_boot, T)) return rc;
+    if (!states_fw) return fma2c_refuse("rs_fma2c_learn_update: NULL handle or pointer");
+    if (hipSetDevice(l->device) != hipSuccess) return RS_EHIP;
+    if (int rc = ft_grad_launch(l, rows, acts, rewards, values, dones, R_boot, T, loss_out, (hipStream_t)stream)) return rc;
+    if (int rc = ft_step_launch(l, (hipStream_t)stream)) return rc;
+    const size_t bytes = (size_t)l->n_envs * l->pol->A.K * 4 * FM_L * sizeof(float);
+    return hipMemcpyAsync(l->states_bw, states_fw, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_fma2c_learn_reset(rs_fma2c_learn_handle l, void *stream) {
+    if (!l) return fma2c_refuse("rs_fma2c_learn_reset: NULL handle");
+    if (hipSetDevice(l->device) != hipSuccess) return RS_EHIP;
+    const size_t bytes = (size_t)l->n_envs * l->pol->A.K * 4 * FM_L * sizeof(float);
+    return hipMemsetAsync(l->states_bw, 0, bytes, (hipStream_t)stream) == hipSuccess ? RS_OK : RS_EHIP;
+}
+
+extern "C" int rs_fma2c_learn_buffer(rs_fma2c_learn_handle l, int32_t which, void **dev_ptr) {
+    if (!l || !dev_ptr) return fma2c_refuse("rs_fma2c_learn_buffer: NULL handle or pointer");
+    if (which < 0 || which > 7) return fma2c_refuse("rs_fma2c_learn_buffer: which = 0 weights, 1 ms, 2 gradients, 3 states_bw, 4 returns, 5 advantages, 6 norms, 7 scales");
+    float *const tab[8] = {l->w, l->ms, l->grad, l->states_bw, l->ret, l->adv, l->norms, l->scales};
+    *dev_ptr = tab[which];
     return RS_OK;
 }
 

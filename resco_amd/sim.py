@@ -43,7 +43,8 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
 
 # the FMA2C entry points (include/resco_sim.h: rs_fma2c_*)
 FMA2C_SYMBOLS = ['rs_fma2c_create', 'rs_fma2c_act', 'rs_fma2c_value', 'rs_fma2c_reset', 'rs_fma2c_set_device_weights', 'rs_fma2c_buffer',
-                 'rs_fma2c_destroy']
+                 'rs_fma2c_destroy', 'rs_fma2c_learn_create', 'rs_fma2c_learn_grad', 'rs_fma2c_learn_step', 'rs_fma2c_learn_update',
+                 'rs_fma2c_learn_reset', 'rs_fma2c_learn_buffer', 'rs_fma2c_learn_destroy']
 
 _lib = None
 
@@ -142,6 +143,15 @@ def bind(L):
         L.rs_fma2c_buffer.argtypes = [vp, i32, C.POINTER(vp)]
         L.rs_fma2c_destroy.argtypes = [vp]
         L.rs_fma2c_destroy.restype = None
+    if hasattr(L, 'rs_fma2c_learn_create'):
+        L.rs_fma2c_learn_create.argtypes = [vp, vp, i32, i32, C.POINTER(vp)]
+        L.rs_fma2c_learn_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+        L.rs_fma2c_learn_step.argtypes = [vp, vp]
+        L.rs_fma2c_learn_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+        L.rs_fma2c_learn_reset.argtypes = [vp, vp]
+        L.rs_fma2c_learn_buffer.argtypes = [vp, i32, C.POINTER(vp)]
+        L.rs_fma2c_learn_destroy.argtypes = [vp]
+        L.rs_fma2c_learn_destroy.restype = None
     if hasattr(L, 'rs_default_block'):      # (the host emulation of the CPU tests exports only what it implements)
         L.rs_default_block.argtypes = [i32, i32, i32]
         L.rs_default_block.restype = i32
@@ -169,6 +179,12 @@ def load_library():
 
 
 AGENT = {'none': 0, 'random': 1, 'maxwave': 2, 'maxpressure': 3, 'idqn': 4, 'mplight': 5, 'ippo': 6, 'fma2c': 7}      # enum rs_agent
+
+
+class Fma2cLearnConfig(C.Structure):
+    """ctypes mirror of rs_fma2c_learn_config (include/resco_sim.h)"""
+    _fields_ = [(k, C.c_double) for k in ('gamma', 'lr', 'alpha', 'eps', 'max_grad_norm', 'value_coef', 'entropy_coef', 'reward_norm',
+                                          'reward_clip')] + [('workspace_bytes', C.c_int64)]
 
 
 class GroupAgent(C.Structure):

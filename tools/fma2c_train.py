@@ -5,7 +5,10 @@ for all agents (VecMultiSignal.fma2c_rewards) -> the A2C learner in PyTorch (res
 120 steps or at the episode's end) -> weights re-packed on the device.  The reference's FMA2C (agents/fma2c.py, agents/ma2c.py,
 config/agent_config.py:114-138) batched over N environments.
 
-    python tools/fma2c_train.py [--full] [--steps-per-episode n] [map] [n_envs] [episodes] [seed]
+    python tools/fma2c_train.py [--full] [--device-update] [--steps-per-episode n] [map] [n_envs] [episodes] [seed]
+
+--device-update: the fused A2C update (rs_fma2c_learn_*; resco_amd/agents/fma2c_learn_fused.py: FusedA2CLearner) instead of the PyTorch
+learner: rows and values land in the learner's segment buffers, the policy acts with the learner's own weight vector (no re-pack).
 
 Prints one JSON line per episode (mean episode return per agent, average trip delay as utils/readXML.py computes it, the last
 update's mean loss, env-steps/s including learning) and a final line with the best training episode and the on-device random policy
@@ -29,7 +32,7 @@ def delay(env):
     return float(env.sim.trip_delay().mean()), float(env.sim.stats()['arrived'].mean())
 
 
-def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_episode=0, quiet=False, keep=None):
+def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_episode=0, quiet=False, keep=None, device_update=False):
     """keep: a dict that receives net, policy, learner and env instead of having them closed (tests)"""
     cfg = agent_configs['FMA2CFULL' if full else 'FMA2C']
     activate('FMA2CFull' if full else 'FMA2C', map_name)
@@ -38,10 +41,15 @@ def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_
     layout = FMA2CLayout(env.scenario, full)
     net = BatchedFMA2C(layout).init_like_reference(seed).cuda()
     policy = FusedFMA2C(net, n, seed=7 + seed)
-    learner = A2CLearner(net, n, batch_size=cfg['batch_size'], gamma=cfg['gamma'], lr=cfg['lr_init'], alpha=cfg['rmsp_alpha'],
-                         eps=cfg['rmsp_epsilon'], max_grad_norm=cfg['max_grad_norm'], value_coef=cfg['value_coef'],
-                         entropy_coef=cfg['entropy_coef_init'], reward_norm=cfg['reward_norm'], reward_clip=cfg['reward_clip'])
-    policy.refresh_on_device()
+    hyper = dict(batch_size=cfg['batch_size'], gamma=cfg['gamma'], lr=cfg['lr_init'], alpha=cfg['rmsp_alpha'],
+                 eps=cfg['rmsp_epsilon'], max_grad_norm=cfg['max_grad_norm'], value_coef=cfg['value_coef'],
+                 entropy_coef=cfg['entropy_coef_init'], reward_norm=cfg['reward_norm'], reward_clip=cfg['reward_clip'])
+    if device_update:
+        from resco_amd.agents.fma2c_learn_fused import FusedA2CLearner
+        learner = FusedA2CLearner(net, policy, n, **hyper)
+    else:
+        learner = A2CLearner(net, n, **hyper)
+        policy.refresh_on_device()
     lane_agg, actions = env.tensor('lane_agg'), env.tensor('actions')
     state, macts = policy.buffer('state'), policy.buffer('mgr_actions')
 
@@ -62,7 +70,8 @@ def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for k in range(steps):
-            out = policy.act(lane_agg, step_key=t, actions=actions)
+            out = policy.act(lane_agg, step_key=t, actions=actions, want=('value', 'rows'), out=learner.slot()) if device_update else \
+                policy.act(lane_agg, step_key=t, actions=actions)
             acts = torch.cat([macts, out['actions']], dim=1).long()
             env.step(None)
             done = k == steps - 1
@@ -72,7 +81,8 @@ def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_
             res = learner.observe(out['rows'], acts, rew, out['value'], done, state, lambda: policy.value(lane_agg))
             if res is not None:
                 loss = res
-                policy.refresh_on_device()
+                if not device_update:
+                    policy.refresh_on_device()
             t += 1
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -85,6 +95,8 @@ def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_
                  best_training_episode_delay_s=min(r['avg_delay_s'] for r in rows), random_avg_delay_s=round(rnd_delay, 2))
     if not quiet:
         print(json.dumps(final), flush=True)
+    if device_update:
+        learner.pull()
     if keep is not None:
         keep.update(net=net, policy=policy, learner=learner, env=env, layout=layout, loss=loss)
     else:
@@ -95,12 +107,12 @@ def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_
 
 if __name__ == '__main__':
     a = sys.argv[1:]
-    full = '--full' in a
-    a = [x for x in a if x != '--full']
+    full, dev_up = '--full' in a, '--device-update' in a
+    a = [x for x in a if x not in ('--full', '--device-update')]
     spe = 0
     if '--steps-per-episode' in a:
         i = a.index('--steps-per-episode')
         spe = int(a[i + 1])
         del a[i:i + 2]
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 30,
-         int(a[3]) if len(a) > 3 else 0, full=full, steps_per_episode=spe)
+         int(a[3]) if len(a) > 3 else 0, full=full, steps_per_episode=spe, device_update=dev_up)
