@@ -761,6 +761,12 @@ void rs_fma2c_learn_destroy(rs_fma2c_learn_handle l);
 
 /* static facts */
 int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal);
+/* the step kernel the handle launches: "rs_step_kernel_fix_v64<ingolstadt21>" -- the kernel of a shipped map, whose table scalars and
+   working-memory offsets are literals; chosen when every constant of the handle equals them -- or "rs_step_kernel_v64<896>", the generic
+   kernel of the capacity (any other scenario or parameters, or RESCO_STEP_GENERIC=1 in the environment when the handle was created).
+   Both compute the same bits.  While the in-kernel timers are on (rs_phase_profile) the launches go to the profiling kernel
+   instead, whatever this names.  The string lives as long as the handle. */
+const char *rs_info_kernel(rs_handle h);
 
 #ifdef __cplusplus
 }

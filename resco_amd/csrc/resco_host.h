@@ -192,6 +192,33 @@ static inline void rs_ktab_scalars(KTab &K, const PackedTables &PT, const rs_sce
     K.horizon = sc->horizon; K.capacity = sc->capacity; K.step_length = sc->step_length; K.yellow_length = sc->yellow_length * ratio; K.lmax = PT.lmax;
     K.n_arr = PT.n_arr; K.n_dep = PT.n_dep;
 }
+// ---- scenario -> the constants of a handle (resco_step.h: ScnConsts).  No device is touched: rs_create computes them this way, and so
+// does the build, ahead of the HIP compile, for the literals of the per-map step kernels (resco_scn_consts.cpp).
+// From the packed tables of the scenario; `L` (optional) receives the layout of the working memory they describe.  The budget is the
+// one of the default workgroup shape: rs_create puts in what its block_threads argument selects.
+static inline void rs_scn_consts_from(const PackedTables &PT, const rs_scenario *sc, int ratio, ScnConsts *c, Lds *L = nullptr) {
+    KTab K{};
+    rs_ktab_scalars(K, PT, sc, ratio);
+    Lds l{};
+    const size_t bytes = lds_carve(&l, sc->capacity, K.n_cells, K.n_arr, K.n_dep, sc->n_obs, sc->n_signals, sc->n_vtypes, K.tls_maxl);
+    l.cell_inv = PT.cell_inv;
+#define X(n) c->n = K.n;
+    RS_SCN_KTAB(X)
+#undef X
+#define X(n) memcpy(&c->n##_bits, &K.n, 4);
+    RS_SCN_KTAB_F(X)
+#undef X
+    scn_consts_layout(c, l, bytes);
+    c->budget = rs_default_budget(sc->capacity, bytes);
+    if (L) *L = l;
+}
+// from the scenario itself (packs the tables first); false: the scenario exceeds a limit of the tables
+static inline bool rs_scn_consts_of(const rs_scenario *sc, int ratio, ScnConsts *c) {
+    PackedTables PT;
+    if (rs_pack_tables(PT, sc)) return false;
+    rs_scn_consts_from(PT, sc, ratio, c);
+    return true;
+}
 // the parameters of a handle that every launch starts from (launch_step / run_step fill in the per-launch members)
 static inline KParams rs_kparams(const rs_params *p, int32_t env_base, int32_t n_envs) {
     KParams P{};

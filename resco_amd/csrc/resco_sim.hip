@@ -123,8 +123,7 @@ __device__ unsigned long long *g_sec_prof;
 // ------------------------------------------------------------------------------------------------ kernels
 // The tables / state / output descriptors live in ONE constant block in device memory (StepArgs): passed by value they
 // would pin ~70 SGPRs for the whole kernel (beyond ~100 the compiler spills SGPRs into VGPR lanes around every use);
-// behind a const __restrict__ pointer every field is a re-loadable scalar load.
-struct StepArgs { KTab T; State G; Out O; Lds L; };
+// behind a const __restrict__ pointer every field is a re-loadable scalar load.  (struct StepArgs: resco_step.h)
 // the block is read through the CONSTANT address space: scalar loads, and the compiler takes pointers loaded from it for
 // global ones (global_load instead of flat_load, which would also tie up the LDS wait counter)
 typedef const __attribute__((address_space(4))) StepArgs *StepArgsPtr;
@@ -182,7 +181,7 @@ template <int CAP, bool PROF> __device__ __forceinline__ void rs_step_kernel_bod
     if (threadIdx.x == 0) g_sec_prof = P.prof;
 #endif
     DevExec<PROF> ex{(int)blockDim.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), PROF ? P.prof : nullptr, (PROF && P.prof) ? wall_clock64() : 0ull};
-    rs_step_body<CAP>(ex, A->L, A->T, A->G, A->O, P, actions, (int)blockIdx.x);
+    rs_step_body<CAP>(ex, A->L, A->T, A->GP, A->O, P, actions, (int)blockIdx.x);
 }
 template <int CAP>
 __global__ void __launch_bounds__(1024, 8)
@@ -196,6 +195,32 @@ rs_step_kernel_v128(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actio
 // the profiling build (rs_phase_profile / RS_STUDY_SECTIONS): any capacity, 80 VGPRs
 __global__ void __launch_bounds__(768, 6)
 rs_step_kernel_prof(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<0, true>(Ac, P, actions); }
+
+// ONE step kernel per shipped map, at the register budget rs_create chooses for it: F = ScnFix_<map> of the generated header
+// (resco_amd/build.py), every scalar of the tables and every offset of the working memory a literal (resco_step.h: KTabFix / LdsScn).
+// The same body as the kernels above; a handle launches one only if all its constants equal F (rs_create), otherwise -- any other
+// scenario, other parameters, another register budget, RESCO_STEP_GENERIC=1 -- the generic kernel of its capacity.
+#ifndef RS_ONE_CAP
+#include "resco_scn_fix.h"
+#elif defined(RS_ONE_MAP)       // (study builds: the generic kernels of one capacity, and the kernel of ONE map -- tools/isa_map.sh)
+#include "resco_scn_fix.h"
+#undef RS_SCN_MAPS
+#define RS_SCN_MAPS(X) X(RS_ONE_MAP)
+#else
+#define RS_SCN_MAPS(X)
+#endif
+template <class F> __device__ __forceinline__ void rs_step_kernel_fix_body(StepArgsPtr Ac, const KParams &P, const int32_t *__restrict__ actions) {
+    if ((int)blockIdx.x >= P.n_envs) return;
+    const StepArgs *A = (const StepArgs *)Ac;
+    DevExec<false> ex{(int)blockDim.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), nullptr, 0ull};
+    rs_step_body_fix<F>(ex, A->T, A->GP, A->O, P, actions, (int)blockIdx.x);
+}
+template <class F>
+__global__ void __launch_bounds__(1024, 8)
+rs_step_kernel_fix_v64(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_fix_body<F>(Ac, P, actions); }
+template <class F>
+__global__ void __launch_bounds__(768, 6)
+rs_step_kernel_fix_v80(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_fix_body<F>(Ac, P, actions); }
 
 // reset / fresh Signal objects / the static agents: the bodies are in resco_host.h (shared with the host emulation)
 __global__ void rs_reset_kernel(KTab T, State G, KParams P) { rs_reset_env(T, G, P, (int)blockIdx.x, (int)threadIdx.x, blockDim.x); }
@@ -211,7 +236,7 @@ __global__ void rs_act_maxwave_kernel(KTab T, KParams P, const int32_t *pairs, i
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-enum RegBudget { V64 = 0, V128 = 1, V80 = 2 };      // VGPRs of the step kernel a handle launches (the index step_kernel_for takes)
+struct FixKernel;       // a per-map step kernel (below)
 struct rs_sim {
     int device = 0;
     int n_envs = 0, env_base = 0, block = 256;
@@ -219,7 +244,10 @@ struct rs_sim {
     size_t lds = 0;
     KTab K{};
     StepArgs *args = nullptr;      // device copy of {K, G, O}
-    RegBudget budget = V64;
+    RegBudget budget = V64;         // (resco_step.h) the index step_kernel_for takes
+    ScnConsts consts{};             // every constant of this handle (resco_step.h): what decides whether a per-map kernel fits
+    const FixKernel *fix = nullptr; // the per-map step kernel this handle launches (NULL: the generic kernel of its capacity)
+    std::string kernel;             // the name of the step kernel launch_step launches (rs_info_kernel)
     State G{};
     Out O{};
     KParams P{};
@@ -294,6 +322,26 @@ static step_kernel_fn step_kernel_for(int regs, int capacity) {
 #endif
 }
 
+// the per-map kernels: the one of a map's register budget is the only one instantiated
+typedef bool (*scn_match_fn)(const ScnConsts &);
+struct FixKernel { const char *name; step_kernel_fn fn; scn_match_fn matches; };
+template <class F> static step_kernel_fn fix_kernel_fn() {
+    if constexpr (F::budget == V64) return rs_step_kernel_fix_v64<F>;
+    else return rs_step_kernel_fix_v80<F>;
+}
+static const FixKernel kFixKernels[] = {
+#define RS_FIX_ENTRY(m) RS_FIX_ENTRY_(m)
+#define RS_FIX_ENTRY_(m) {ScnFix_##m::budget == V64 ? "rs_step_kernel_fix_v64<" #m ">" : "rs_step_kernel_fix_v80<" #m ">", fix_kernel_fn<ScnFix_##m>(), scn_fix_matches<ScnFix_##m>},
+    RS_SCN_MAPS(RS_FIX_ENTRY)
+#undef RS_FIX_ENTRY
+#undef RS_FIX_ENTRY_
+    {nullptr, nullptr, nullptr}};
+static const FixKernel *fix_kernel_for(const ScnConsts &c) {
+    for (const FixKernel *k = kFixKernels; k->fn; ++k)
+        if (k->matches(c)) return k;
+    return nullptr;
+}
+
 // every synchronous entry point waits for the handle's own stream AND the caller stream of the last launch
 static hipError_t wait_idle(rs_sim *h) {
     hipError_t e = hipStreamSynchronize(h->stream);
@@ -361,6 +409,7 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
     }
     const int C = sc->capacity;
     if (C < 64 || (C % 64) || C > 1984) { h->err = "capacity must be a multiple of 64 in [64, 1984]"; return fail(RS_ELIMIT); }
+    if ((size_t)n_envs * (size_t)C >= RS_STATE_MAX_SLOTS) { h->err = "n_envs * capacity must stay below 2^30 slots (the step kernels address a field of the state with 32-bit byte offsets)"; return fail(RS_ELIMIT); }
     if (sc->kmax < 1 || sc->kmax > 16) { h->err = "kmax (lanes per edge) must be in [1, 16]"; return fail(RS_ELIMIT); }
     PackedTables PT;
     if (const char *msg = rs_pack_tables(PT, sc)) { h->err = msg; return fail(RS_ELIMIT); }
@@ -390,7 +439,9 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
     if (p->trip_log && (rc = dev_alloc(h, &G.trip_log, N * (size_t)sc->n_trips * 4))) return fail(rc);
     rs_fill_bufs(h->bufs, G, O, h->actions, BufDims{n_envs, C, sc->n_signals, sc->n_obs, lmax, h->K.n_dep, p->trip_log ? sc->n_trips : 0});
 
-    h->lds = lds_carve(nullptr, C, h->K.n_cells, h->K.n_arr, h->K.n_dep, sc->n_obs, sc->n_signals, sc->n_vtypes, h->K.tls_maxl);
+    Lds layout{};
+    rs_scn_consts_from(PT, sc, h->ratio, &h->consts, &layout);
+    h->lds = h->consts.lds_bytes;
     if (const char *pad = getenv("RESCO_STUDY_LDS_PAD")) h->lds += (size_t)atoi(pad);      // study knob: unused bytes, to hold the residency fixed in an A/B
     if (h->lds > 160 * 1024) { h->err = "scenario needs more than 160 KiB of LDS per environment"; return fail(RS_ELIMIT); }
     if (block_threads == 0) block_threads = rs_default_block(C, n_envs, device_id);
@@ -399,6 +450,26 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
         return fail(RS_EINVAL);
     }
     h->block = block_threads;
+    // which step kernel: the one of a shipped map if EVERY constant of this handle is that kernel's literal (the register budget the
+    // block selects and the LDS bytes, a study pad included), else the generic one.  RESCO_STEP_GENERIC=1: always the generic one
+    // (the other side of an A/B and of tests/test_gpu_scn_fix.py)
+    h->consts.budget = h->budget; h->consts.lds_bytes = (uint32_t)h->lds;
+    {
+        const char *g = getenv("RESCO_STEP_GENERIC");
+        h->fix = (g && atoi(g) != 0) ? nullptr : fix_kernel_for(h->consts);
+        if (h->fix) h->kernel = h->fix->name;
+        else {
+            char nm[64];
+#ifdef RS_ONE_CAP
+            const int kcap = RS_ONE_CAP;
+#else
+            int kcap = 0;
+            for (int cp : kStepCaps) if (cp == C) kcap = cp;
+#endif
+            snprintf(nm, sizeof(nm), "rs_step_kernel_v%d<%d>", h->budget == V64 ? 64 : (h->budget == V80 ? 80 : 128), kcap);
+            h->kernel = nm;
+        }
+    }
     {
         // the dynamic-LDS ceiling is an attribute of the kernel (per device), not of a launch: only ever raise it,
         // or a handle created earlier for a larger scenario could no longer launch
@@ -412,6 +483,10 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
                     if (hipFuncSetAttribute((const void *)step_kernel_for(v, cp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess) {
                         h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return fail(RS_EHIP);
                     }
+            for (const FixKernel *k = kFixKernels; k->fn; ++k)
+                if (hipFuncSetAttribute((const void *)k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess) {
+                    h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return fail(RS_EHIP);
+                }
             if (hipFuncSetAttribute((const void *)rs_step_kernel_prof, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess) {
                 h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return fail(RS_EHIP);
             }
@@ -419,10 +494,8 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
         }
     }
     {
-        StepArgs sa{h->K, h->G, h->O, Lds{}};
-        lds_carve(&sa.L, C, h->K.n_cells, h->K.n_arr, h->K.n_dep, sc->n_obs, sc->n_signals, sc->n_vtypes, h->K.tls_maxl);
+        StepArgs sa{h->K, h->G, h->O, layout, StateP(h->G)};
         if (!lds_fix_matches(sa.L, C)) { h->err = "the layout of the working memory does not match the kernel's literals (lds_carve / LdsFix)"; return fail(RS_EINVAL); }
-        sa.L.cell_inv = PT.cell_inv;
         if ((rc = dev_alloc(h, &h->args, 1, false))) return fail(rc);
         if (hipMemcpy(h->args, &sa, sizeof(sa), hipMemcpyHostToDevice) != hipSuccess) { h->err = "hipMemcpy(StepArgs) failed"; return fail(RS_EHIP); }
     }
@@ -472,7 +545,7 @@ static int launch_step(rs_sim *h, hipStream_t st, int n_ticks, int do_fsm, int d
         HIPCHK(h, hipEventRecord(e0, st));
     }
     // (the in-kernel timers live in a kernel of their own: any capacity, 80 VGPRs, at most 768 threads)
-    const step_kernel_fn fn = (h->prof && h->block <= 768) ? (step_kernel_fn)rs_step_kernel_prof : step_kernel_for(h->budget, h->K.capacity);
+    const step_kernel_fn fn = (h->prof && h->block <= 768) ? (step_kernel_fn)rs_step_kernel_prof : (h->fix ? h->fix->fn : step_kernel_for(h->budget, h->K.capacity));
     hipLaunchKernelGGL(fn, dim3(h->n_envs), dim3(h->block), h->lds, st, (StepArgsPtr)h->args, P, (const int32_t *)h->actions);
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(e1, st));
@@ -692,6 +765,8 @@ extern "C" int rs_set_seed(rs_handle h, uint32_t seed) {
     return RS_OK;
 }
 
+// (with the in-kernel timers switched on -- rs_phase_profile, blocks up to 768 threads -- launch_step launches rs_step_kernel_prof instead)
+extern "C" const char *rs_info_kernel(rs_handle h) { return h ? h->kernel.c_str() : ""; }
 extern "C" int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal) {
     if (!h) return RS_EINVAL;
     rs_info_describe(h->n_envs, h->block, h->lds, h->K.lmax, n_envs, block_threads, lds_bytes, max_lanes_per_signal);

@@ -53,6 +53,50 @@ struct State {      // env-major SoA in HBM: field[env][slot]
     RS_HD uint8_t *owner() const { return RS_G((uint8_t *)(base + 42 * nc)); }
     static size_t bytes(size_t nc_) { return 51 * nc_; }
 };
+// The same state with every field ADDRESS computed once by the host: what the step kernels read from the constant argument block
+// (StepArgs, next to the State the other kernels take by value).  A field pointer is one 8-byte scalar load there; rebuilding
+// `base + k * nc` costs a 16-byte load of (base, nc) and six scalar instructions per field and site.  The phases take either (GT).
+// An element of an array in global memory at an UNSIGNED 32-bit byte offset from its (wave-uniform) base, the offset computed in 32 bits:
+// the compiler then addresses it as SGPR base + VGPR offset (the `saddr` form) instead of building a 64-bit address per lane
+// (resco_tables.h: rec_load16).  Needs the array below 4 GiB: the tables are (16-bit ids), a field of the state is as long as
+// N * C < 2^30 slots, which rs_create enforces.
+template <class Tp, class I> RS_MEM const Tp &rs_at(const Tp *p, I i) { return *(const Tp *)((const char *)p + (uint32_t)i * (uint32_t)sizeof(Tp)); }
+template <class Tp> struct GOff {       // a field of StateP: field()[i] is rs_at, writable
+    Tp *p;
+    RS_HD Tp &operator[](size_t i) const { return *(Tp *)((char *)p + (uint32_t)i * (uint32_t)sizeof(Tp)); }
+};
+#define RS_STATE_MAX_SLOTS ((size_t)1 << 30)      // N * C of a handle: the 4-byte fields stay below 4 GiB
+struct StateP {
+    float *pos_, *speed_, *accel_, *tloss_, *sf_;
+    uint32_t *coop_[2], *cooplead_[2];
+    uint16_t *lane_, *trip_, *cursor_, *swait_, *rwait_, *depart_, *wtot_;
+    uint8_t *owner_;
+    int32_t *trip_log, *env, *tls;
+    long long *stats;
+    uint16_t *dep_next;
+    uint32_t *mail;
+    StateP() = default;
+    explicit StateP(const State &G)
+        : pos_(G.pos()), speed_(G.speed()), accel_(G.accel()), tloss_(G.tloss()), sf_(G.sf()), coop_{G.coop(0), G.coop(1)},
+          cooplead_{G.cooplead(0), G.cooplead(1)}, lane_(G.lane()), trip_(G.trip()), cursor_(G.cursor()), swait_(G.swait()), rwait_(G.rwait()),
+          depart_(G.depart()), wtot_(G.wtot()), owner_(G.owner()), trip_log(G.trip_log), env(G.env), tls(G.tls), stats(G.stats),
+          dep_next(G.dep_next), mail(G.mail) {}
+    RS_HD GOff<float> pos() const { return GOff<float>{RS_G(pos_)}; }
+    RS_HD GOff<float> speed() const { return GOff<float>{RS_G(speed_)}; }
+    RS_HD GOff<float> accel() const { return GOff<float>{RS_G(accel_)}; }
+    RS_HD GOff<float> tloss() const { return GOff<float>{RS_G(tloss_)}; }
+    RS_HD GOff<float> sf() const { return GOff<float>{RS_G(sf_)}; }
+    RS_HD GOff<uint32_t> coop(int par) const { return GOff<uint32_t>{RS_G(coop_[par])}; }
+    RS_HD GOff<uint32_t> cooplead(int par) const { return GOff<uint32_t>{RS_G(cooplead_[par])}; }
+    RS_HD GOff<uint16_t> lane() const { return GOff<uint16_t>{RS_G(lane_)}; }
+    RS_HD GOff<uint16_t> trip() const { return GOff<uint16_t>{RS_G(trip_)}; }
+    RS_HD GOff<uint16_t> cursor() const { return GOff<uint16_t>{RS_G(cursor_)}; }
+    RS_HD GOff<uint16_t> swait() const { return GOff<uint16_t>{RS_G(swait_)}; }
+    RS_HD GOff<uint16_t> rwait() const { return GOff<uint16_t>{RS_G(rwait_)}; }
+    RS_HD GOff<uint16_t> depart() const { return GOff<uint16_t>{RS_G(depart_)}; }
+    RS_HD GOff<uint16_t> wtot() const { return GOff<uint16_t>{RS_G(wtot_)}; }
+    RS_HD GOff<uint8_t> owner() const { return GOff<uint8_t>{RS_G(owner_)}; }
+};
 
 struct Out {        // one allocation; n = N, o = n_obs, s = n_signals, lm = lanes of the largest signal
     char *base;
@@ -374,6 +418,112 @@ RS_CARVE float pick_cell_len(const rs_scenario *sc, int n_arr, int n_dep, int tl
     return choices[0];          // (PackedTables::build reports the vehicle type that is too short)
 }
 
+// ------------------------------------------------------------------------------------------------ the constants of a handle
+// Everything a step kernel reads that is fixed once rs_create returns -- the scalars of KTab, the whole layout of the working memory,
+// what rs_create chooses from them -- as ONE plain struct of 32-bit members (floats as their bit patterns): rs_scn_consts_of
+// (resco_host.h) computes it from a scenario without a device.  The build writes the structs of the shipped maps out as literals
+// (ScnFix_<map> in the generated resco_scn_fix.h, resco_amd/build.py) and a step kernel is instantiated per map from them: to such a
+// kernel T.kmax, L.vtp, L.cell_inv ... are literals instead of scalar loads from the constant argument block, and what depends on them
+// folds (KTabFix / LdsScn below).  A handle launches the kernel of a map only if EVERY member equals that kernel's literals
+// (scn_fix_matches); otherwise the generic kernel of its capacity, which computes the same from the loaded values.
+// X(member) lists: the scalars of KTab; the floats; X(member, element type) the arrays of the working memory
+#define RS_SCN_KTAB(X)                                                                                                                \
+    X(kmax) X(tls_maxl) X(n_signals) X(n_obs) X(n_vtypes) X(n_dep) X(n_arr) X(n_trips) X(n_lanes) X(n_cells) X(capacity) X(lmax)     \
+    X(step_length) X(yellow_length) X(horizon)
+#define RS_SCN_KTAB_F(X) X(maxlen) X(occ_unit)
+#define RS_SCN_LDS(X)                                                                                                                 \
+    X(node, Node) X(aux, Aux) X(vnx, float) X(vtp, float) X(grid, uint16_t) X(arr, int32_t) X(dep, uint16_t) X(dep_t, uint16_t)       \
+    X(alive, uint32_t) X(alive0, uint32_t) X(insm, uint32_t) X(mailw, uint32_t) X(agg_q, int32_t) X(agg_a, int32_t) X(agg_w, int32_t) \
+    X(agg_m, int32_t) X(agg_n, int32_t) X(agg_s, uint32_t) X(sig_arr, int32_t) X(sig_dep, int32_t) X(phase, int32_t) X(left, int32_t) \
+    X(nextp, int32_t) X(tstate, uint8_t) X(sc, int32_t) X(ls_h, uint16_t) X(ls_lc, uint16_t) X(ls_mh, uint16_t)
+enum RegBudget { V64 = 0, V128 = 1, V80 = 2 };      // VGPRs of the step kernel a handle launches
+struct ScnConsts {
+#define X(n) int32_t n;
+    RS_SCN_KTAB(X)
+#undef X
+#define X(n) uint32_t n##_bits;
+    RS_SCN_KTAB_F(X)
+#undef X
+    uint32_t cell_inv_bits;     // Lds::cell_inv
+#define X(n, tp) uint32_t o_##n;
+    RS_SCN_LDS(X)
+#undef X
+    uint32_t gstride, lcap;
+    uint32_t lds_bytes;         // what lds_carve returns
+    int32_t budget;             // the RegBudget of the handle (rs_scn_consts_of: the one the default workgroup shape gets)
+};
+#define RS_SCN_STR_(n) #n ","
+#define RS_SCN_STR_F_(n) #n "_bits,"
+#define RS_SCN_STR_O_(n, tp) "o_" #n ","
+#define RS_SCN_NAMES RS_SCN_KTAB(RS_SCN_STR_) RS_SCN_KTAB_F(RS_SCN_STR_F_) "cell_inv_bits," RS_SCN_LDS(RS_SCN_STR_O_) "gstride,lcap,lds_bytes,budget"
+// the register budget of the workgroup shape rs_create picks by default for a large batch (one thread per two slots, at most 512 threads):
+// 64 VGPRs where four 512-thread workgroups share a CU, else 80 (resco_sim.hip: rs_default_block / decode_block)
+RS_CARVE int rs_default_budget(int C, size_t lds) {
+    const int waves = C >= 768 ? 8 : ((C / 2) + 63) / 64;
+    return (waves * 64 == 512 && lds <= RS_LDS_4WG_LIMIT) ? V64 : V80;
+}
+// the layout half of ScnConsts from the table lds_carve fills
+RS_CARVE void scn_consts_layout(ScnConsts *c, const Lds &L, size_t lds_bytes) {
+#define X(n, tp) c->o_##n = L.n.off;
+    RS_SCN_LDS(X)
+#undef X
+    c->gstride = L.gstride; c->lcap = L.lcap; c->lds_bytes = (uint32_t)lds_bytes;
+    __builtin_memcpy(&c->cell_inv_bits, &L.cell_inv, 4);
+}
+// does a handle with the constants c compute what the kernel instantiated from the literals F computes?  Every member, no exception
+template <class F> RS_CARVE bool scn_fix_matches(const ScnConsts &c) {
+    bool ok = c.cell_inv_bits == F::cell_inv_bits && c.gstride == F::gstride && c.lcap == F::lcap && c.lds_bytes == F::lds_bytes && c.budget == F::budget;
+#define X(n) ok = ok && c.n == F::n;
+    RS_SCN_KTAB(X)
+#undef X
+#define X(n) ok = ok && c.n##_bits == F::n##_bits;
+    RS_SCN_KTAB_F(X)
+#undef X
+#define X(n, tp) ok = ok && c.o_##n == F::o_##n;
+    RS_SCN_LDS(X)
+#undef X
+    return ok;
+}
+
+// THE constant argument block of the step kernels, one per handle in device memory (resco_sim.hip: StepArgsPtr): the tables, the state
+// as the other kernels take it, the outputs, the layout of the working memory and the field addresses of the state
+struct StepArgs { KTab T; State G; Out O; Lds L; StateP GP; };
+
+#ifndef RS_LAYOUT_ONLY      // (a host-only includer that wants the layout and the constants alone -- resco_scn_consts.cpp -- stops here: what
+                            //  follows needs the includer's atomics and working memory)
+// The tables and the working memory as a kernel of ONE MAP sees them: the phases are written against `T.<scalar>`, `T.<table>()`,
+// `T.cold.<table>` and `L.<array>[i]`, and take KTab / Lds (every value loaded), LdsFix<C> (the offsets that follow from the capacity
+// are literals) or these views, in which every scalar and every offset is a literal of F = ScnFix_<map> and only the table pointers
+// are still read from the constant argument block.  No model logic differs between the views.
+template <class F> struct KTabFix {
+    const KTab &K;
+    const KCold &cold;
+    RS_MEM explicit KTabFix(const KTab &K_) : K(K_), cold(K_.cold) {}
+#define X(n) static constexpr int32_t n = F::n;
+    RS_SCN_KTAB(X)
+#undef X
+#define X(n) static constexpr float n = __builtin_bit_cast(float, (uint32_t)F::n##_bits);
+    RS_SCN_KTAB_F(X)
+#undef X
+    RS_MEM const LaneRec *lanes() const { return K.lanes(); }
+    RS_MEM const LinkRec *links() const { return K.links(); }
+    RS_MEM const FoeRec *foes() const { return K.foes(); }
+    RS_MEM const RStep *rsteps() const { return K.rsteps(); }
+    RS_MEM const float *route_cont() const { return K.route_cont(); }
+    RS_MEM const uint16_t *next_link() const { return K.next_link(); }
+    RS_MEM const uint16_t *notbest() const { return K.notbest(); }
+    RS_MEM const RouteRec *routes() const { return K.routes(); }
+    RS_MEM const uint16_t *trip_route() const { return K.trip_route(); }
+    RS_MEM const uint8_t *trip_vtype() const { return K.trip_vtype(); }
+};
+template <class F> struct LdsScn {
+#define X(n, tp) CPtr<tp, F::o_##n> n;
+    RS_SCN_LDS(X)
+#undef X
+    static constexpr uint32_t gstride = F::gstride, lcap = F::lcap;
+    static constexpr float cell_inv = __builtin_bit_cast(float, (uint32_t)F::cell_inv_bits);
+};
+
 // ------------------------------------------------------------------------------------------------ grid primitives
 #ifdef RS_EMU_DEBUG         // host emulation, debug build: a chain that does not end means a vehicle entered a grid twice
 #define RS_CHAIN_GUARD if (++rs_dbg_chain > 50000000L) { printf("endless chain walk\n"); fflush(stdout); abort(); }
@@ -604,18 +754,18 @@ template <class LT> RS_DEV int at_or_behind_within(const LT &L, const Grid &grid
 }
 
 // ------------------------------------------------------------------------------------------------ model helpers
-template <class LT> RS_DEV int tls_state(const KTab &T, const LT &L, int tls, int pos) {
+template <class TT, class LT> RS_DEV int tls_state(const TT &T, const LT &L, int tls, int pos) {
     if (tls == 0xFF) return TLS_G;
     return L.tstate[tls * T.tls_maxl + pos];
 }
 // the link a vehicle on lane `lane` (record LR) takes at route step rq: link index | NLINK_ARR, NLINK_NONE when there is
 // none (last edge / a dead end for this route).  For a normal lane it is a table of (route step, lane index, trip parity)
-RS_DEV uint16_t cache_link(const KTab &T, const LaneRec &LR, int lane, int rq, int trip) {
+template <class TT> RS_DEV uint16_t cache_link(const TT &T, const LaneRec &LR, int lane, int rq, int trip) {
     if (LR.link_cnt == 0) return NLINK_NONE;
-    if (LR.flags & LF_INTERNAL) { const int l = LR.link_start; return (uint16_t)(l | (T.links()[l].arr_idx >= 0 ? NLINK_ARR : 0)); }
-    return T.next_link()[((size_t)rq * T.kmax + (lane - (int)LR.edge_lane0)) * 2 + (trip & 1)];
+    if (LR.flags & LF_INTERNAL) { const int l = LR.link_start; return (uint16_t)(l | (rs_at(T.links(), l).arr_idx >= 0 ? NLINK_ARR : 0)); }
+    return rs_at(T.next_link(), ((uint32_t)rq * (uint32_t)T.kmax + (uint32_t)(lane - (int)LR.edge_lane0)) * 2u + (uint32_t)(trip & 1));
 }
-template <class LT> RS_DEV bool foe_blocked(const KTab &T, const LT &L, const Grid &grid, const LinkRec &K) {
+template <class TT, class LT> RS_DEV bool foe_blocked(const TT &T, const LT &L, const Grid &grid, const LinkRec &K) {
     for (int i = K.foe_start; i < K.foe_start + K.foe_cnt; ++i) {
         const FoeRec F = rec_load16(T.foes(), i);
         if (F.tls != 0xFF && tls_state(T, L, F.tls, F.tls_pos) == TLS_R) continue;
@@ -626,7 +776,7 @@ template <class LT> RS_DEV bool foe_blocked(const KTab &T, const LT &L, const Gr
     return false;
 }
 // copy the link states of signal s in phase ph into the working memory (called by the thread that owns the signal)
-template <class LT> RS_DEV void tls_refresh(const KTab &T, const LT &L, const KParams &P, int s, int ph) {
+template <class TT, class LT> RS_DEV void tls_refresh(const TT &T, const LT &L, const KParams &P, int s, int ph) {
     // rows of the state tables are tls_maxl bytes (a multiple of 4, zero padded) and 4-byte aligned: the row is copied with
     // independent 32-bit loads (up to 8 of them in flight) -- all signals change phase in the same ticks, and this copy is on the
     // critical path of those ticks' C phase
@@ -641,7 +791,7 @@ template <class LT> RS_DEV void tls_refresh(const KTab &T, const LT &L, const KP
 #pragma unroll 1
     for (int i = 8; i < w; ++i) dst[i] = src[i];
 }
-template <class LT> RS_DEV void set_phase(const KTab &T, const LT &L, const KParams &P, int s, int ph) {
+template <class TT, class LT> RS_DEV void set_phase(const TT &T, const LT &L, const KParams &P, int s, int ph) {
     if (ph < 0 || ph >= T.cold.tls_nphase[s]) return;
     L.phase[s] = ph;
     L.left[s] = P.tls_expiry ? T.cold.tls_dur[T.cold.tls_dur_off[s] + ph] : RM_TLS_HOLD_TICKS;      // rs_params.tls_expiry
@@ -649,7 +799,7 @@ template <class LT> RS_DEV void set_phase(const KTab &T, const LT &L, const KPar
 }
 // TLS switch events at the beginning of tick `tick` of this launch, preceded by Signal.set_phase when the yellow
 // ticks are over
-template <class LT> RS_DEV void tls_begin_of_tick(const KTab &T, const LT &L, const KParams &P, int s, int tick) {
+template <class TT, class LT> RS_DEV void tls_begin_of_tick(const TT &T, const LT &L, const KParams &P, int s, int tick) {
     if (P.do_fsm && !P.fixed_program && tick == T.yellow_length) set_phase(T, L, P, s, L.nextp[s]);
     int left = L.left[s];
     if (left == 0) {
@@ -664,9 +814,9 @@ template <class LT> RS_DEV void tls_begin_of_tick(const KTab &T, const LT &L, co
 }
 // the continuation lengths of the lanes of route step rq (route_cont row), loaded once: the first four in registers
 struct ContRow { float c[4]; const float *cn; };
-RS_DEV ContRow cont_row(const KTab &T, int rq) {
+template <class TT> RS_DEV ContRow cont_row(const TT &T, int rq) {
     ContRow R;
-    R.cn = T.route_cont() + (size_t)rq * T.kmax;
+    R.cn = (const float *)((const char *)T.route_cont() + (uint32_t)rq * (uint32_t)T.kmax * 4u);
     for (int j = 0; j < 4; ++j) R.c[j] = j < T.kmax ? R.cn[j] : 0.0f;
     return R;
 }
@@ -710,8 +860,8 @@ RS_DEV int strategic_dir(const ContRow &R, int kk, int n, float x, float v, int 
 // approach registration for the coming tick: a moving vehicle whose next link somebody may have to yield to registers
 // its arrival time there (v, pos, vType, lane length and next link of the vehicle AFTER this tick's move)
 // (the three fields of the link the registration needs are one dword of its record: arr_idx | tls << 16 | tls_pos << 24)
-RS_DEV uint32_t link_reg_word(const KTab &T, int nlk) { return ((const uint32_t *)&T.links()[nlk & 0x7FFF])[2]; }
-template <class LT> RS_DEV void register_approach_w(const KTab &T, const LT &L, uint32_t kw, float v, float pos, float lane_len, int vt) {
+template <class TT> RS_DEV uint32_t link_reg_word(const TT &T, int nlk) { return rs_at((const uint32_t *)T.links(), (uint32_t)(nlk & 0x7FFF) * 8u + 2u); }
+template <class TT, class LT> RS_DEV void register_approach_w(const TT &T, const LT &L, uint32_t kw, float v, float pos, float lane_len, int vt) {
     const int st = tls_state(T, L, (int)((kw >> 16) & 0xFFu), (int)(kw >> 24));
     if (st == TLS_R) return;
     const float dist = lane_len - pos;
@@ -720,14 +870,14 @@ template <class LT> RS_DEV void register_approach_w(const KTab &T, const LT &L, 
     const int q = ta * 10.0f >= 65000.0f ? 65000 : (int)(ta * 10.0f);
     rs_atomic_min(&L.arr[(int16_t)(kw & 0xFFFFu)], q);
 }
-template <class LT> RS_DEV void register_approach(const KTab &T, const LT &L, int nlk, float v, float pos, float lane_len, int vt) {
+template <class TT, class LT> RS_DEV void register_approach(const TT &T, const LT &L, int nlk, float v, float pos, float lane_len, int vt) {
     if (!(nlk & NLINK_ARR)) return;         // nobody yields to my next link (or I have none)
     if (v <= RM_HALT_SPEED) return;
     register_approach_w(T, L, link_reg_word(T, nlk), v, pos, lane_len, vt);
 }
 // follow `X` (a vehicle on a neighbouring lane of my edge) as if it were my leader, braking no harder than comfortably:
 // the cooperative part of the lane changing (oracle: plan(), coop / coop_lead).  key = trip << 16 | slot.
-template <class LT> RS_DEV void follow_neighbour(const KTab &T, const LT &L, uint32_t key, bool clamp_gap, const LaneRec &LR, int lane, float x, float v,
+template <class TT, class LT> RS_DEV void follow_neighbour(const TT &T, const LT &L, uint32_t key, bool clamp_gap, const LaneRec &LR, int lane, float x, float v,
                              float b, float tau, float mingap, float &vsafe) {
     const int X = (int)(key & 0xFFFFu), kx = (int)(key >> 16);
     if ((int)L.node[X].trip != kx) return;
@@ -797,7 +947,7 @@ RS_DEV bool may_change_lanes_row(const ContRow &R, const LaneRec &LR, int lane, 
 // the same from the not-best MASK of the route step (KTab::notbest: bit k = lane k is not one of the step's best lanes -- the signs of the
 // continuation row as one 16-bit word): the move classifies every vehicle every tick, and all it needs of the row is two of these bits.
 // The lengths themselves are fetched only when the neighbour lane of a speed-gain candidate is not a best lane either (rare).
-RS_DEV bool may_change_lanes(const KTab &T, int rq, uint32_t nb, const LaneRec &LR, int lane, int k, float x, float v, int t) {
+template <class TT> RS_DEV bool may_change_lanes(const TT &T, int rq, uint32_t nb, const LaneRec &LR, int lane, int k, float x, float v, int t) {
     const int n = LR.flags >> 2;
     if ((LR.flags & LF_INTERNAL) || n < 2) return false;
     const int kk = lane - (int)LR.edge_lane0;
@@ -816,7 +966,7 @@ RS_DEV bool may_change_lanes(const KTab &T, int rq, uint32_t nb, const LaneRec &
     return r;
 }
 // The work of tick t for the vehicle in slot s (state as of the beginning of that tick): its flags, and it is queued
-template <class LT> RS_DEV int classify(const KTab &T, const LT &L, int s, const float *vt, float v, float x, const LaneRec &LR, int lane, int rq, uint32_t nb, int k, float sf, int t) {
+template <class TT, class LT> RS_DEV int classify(const TT &T, const LT &L, int s, const float *vt, float v, float x, const LaneRec &LR, int lane, int rq, uint32_t nb, int k, float sf, int t) {
     int fl = 0;
     if (looks_beyond(vt, v, x, LR.len, LR.vmax, sf)) { fl |= FL_H; list_push(L, L.ls_h, SC_NH, s); }
     if (may_change_lanes(T, rq, nb, LR, lane, k, x, v, t)) { fl |= FL_LC; list_push(L, L.ls_lc, SC_NLC, s); }
@@ -827,7 +977,7 @@ template <class LT> RS_DEV int classify(const KTab &T, const LT &L, int s, const
 // P: plan (Krauss car-following + links) for slot s.  LONG = false: the short path, for a vehicle WITHOUT FL_H -- nothing beyond
 // the end of its lane is inside its look-ahead (classify() decided that on the very state this plan sees; the host emulation
 // checks it) --, so the walk over the links is not compiled into what the waves on the short path run.
-template <bool LONG, class LT> RS_DEV void phase_plan(const KTab &T, const LT &L, const Grid &grid, const State &G, size_t eo, const KParams &P, int genv, int t, int s) {
+template <bool LONG, class TT, class LT, class GT> RS_DEV void phase_plan(const TT &T, const LT &L, const Grid &grid, const GT &G, size_t eo, const KParams &P, int genv, int t, int s) {
     RS_SEC_BEGIN
     const Aux ax = L.aux[s];
     const int lane = ax.lane;
@@ -883,7 +1033,7 @@ template <bool LONG, class LT> RS_DEV void phase_plan(const KTab &T, const LT &L
             LinkRec K;
             if (link == NLINK_NONE) {
                 // last edge of the route: free run to its end; otherwise a dead end: wait for a lane change
-                if (!cur_int && T.rsteps()[rq].next_edge == 0xFFFF) break;
+                if (!cur_int && rs_at(T.rsteps(), rq).next_edge == 0xFFFF) break;
                 stop_here = true;
             } else {
                 K = link_load(T.links(), link);
@@ -956,7 +1106,7 @@ template <bool LONG, class LT> RS_DEV void phase_plan(const KTab &T, const LT &L
 
 // M: move slot s -- sideways first (the lane change decided in the plan phase), then forward, over to the next lanes, or
 // out of the network; leave the old grid, enter the new one; register the approach of the coming tick
-template <bool LONG, class LT> RS_DEV void phase_move(const KTab &T, const LT &L, const Grid &gnew, const State &G, const KParams &P, int env, size_t eo,
+template <bool LONG, class TT, class LT, class GT> RS_DEV void phase_move(const TT &T, const LT &L, const Grid &gnew, const GT &G, const KParams &P, int env, size_t eo,
                        int t, bool last_tick, bool more, int s, int &active, int &halted, int &top) {
     const Aux ax = L.aux[s];
     const Node me = L.node[s];
@@ -973,7 +1123,7 @@ template <bool LONG, class LT> RS_DEV void phase_move(const KTab &T, const LT &L
     LaneRec LR = rec_load16(T.lanes(), lane);
 #endif
     // what the end of the move needs from the tables is requested now (the common case: the vehicle stays on its lane)
-    uint32_t nb = T.notbest()[ax.rq];       // (which lanes of my route step are not its best ones: what classify() needs of the continuation row)
+    uint32_t nb = rs_at(T.notbest(), ax.rq);       // (which lanes of my route step are not its best ones: what classify() needs of the continuation row)
     uint32_t kw = 0;
     if (more && (ax.nlink & NLINK_ARR)) kw = link_reg_word(T, ax.nlink);
     const float sfv = sf_of(me.sfq);
@@ -1019,7 +1169,7 @@ template <bool LONG, class LT> RS_DEV void phase_move(const KTab &T, const LT &L
         if (!(x > LR.len)) break;
         const bool li = (LR.flags & LF_INTERNAL) != 0;
         if (link == NLINK_NONE) {
-            if (!li && T.rsteps()[rq].next_edge == 0xFFFF) arrived = true; else x = LR.len;
+            if (!li && rs_at(T.rsteps(), rq).next_edge == 0xFFFF) arrived = true; else x = LR.len;
             break;
         }
         x -= LR.len;
@@ -1065,7 +1215,7 @@ template <bool LONG, class LT> RS_DEV void phase_move(const KTab &T, const LT &L
     nn.pos = x; nn.speed = vn; nn.fl = (uint8_t)(me.fl & fl_mh(t));
     nn.nxt = grid_push(gnew, LR.cell0 + cell_of(L, x, lane_cells(L, LR)), s, vn > RM_HALT_SPEED);
     if (more) {
-        if (LONG && relink) { nb = T.notbest()[rq]; if (na.nlink & NLINK_ARR) kw = link_reg_word(T, na.nlink); }
+        if (LONG && relink) { nb = rs_at(T.notbest(), rq); if (na.nlink & NLINK_ARR) kw = link_reg_word(T, na.nlink); }
         nn.fl |= classify(T, L, s, L.vtp + me.vt * VT_COLS, vn, x, LR, lane, rq, nb, k, sfv, t + 1);
         L.node[s] = nn;
         if ((na.nlink & NLINK_ARR) && vn > RM_HALT_SPEED) register_approach_w(T, L, kw, vn, x, LR.len, me.vt);
@@ -1085,7 +1235,7 @@ template <class LT> RS_DEV int overlapping(const LT &L, const Grid &grid, int ce
 
 // The lane-change decision of slot s on the state at the beginning of the tick: returns LCT_* (0: stay).  A blocked strategic
 // changer asks for cooperation; a mutual block is swapped out (oracle: lane_change())
-template <class LT> RS_DEV int phase_lc_decide(const KTab &T, const LT &L, const Grid &grid, const State &G, size_t eo, int t, int s, const Aux &ax, const Node &me) {
+template <class TT, class LT, class GT> RS_DEV int phase_lc_decide(const TT &T, const LT &L, const Grid &grid, const GT &G, size_t eo, int t, int s, const Aux &ax, const Node &me) {
     const int lane = ax.lane;
     // (everything the decision may need from global memory is requested at once)
 #ifdef RS_FIELD_LOADS
@@ -1186,12 +1336,12 @@ template <class LT> RS_DEV int phase_lc_decide(const KTab &T, const LT &L, const
 
 // C: does the oldest waiting trip of departure lane d get onto the network in tick t?  The space on its lane is judged
 // AFTER this tick's move of the vehicles that are on it now -- their next speeds are known (oracle: insertion_check)
-template <class LT> RS_DEV bool phase_insert_decide(const KTab &T, const LT &L, const Grid &grid, int t, int d) {
+template <class TT, class LT> RS_DEV bool phase_insert_decide(const TT &T, const LT &L, const Grid &grid, int t, int d) {
     if ((int)L.dep_t[d] > t) return false;           // nothing due on this lane (the common case: no global access)
     const int k = L.dep[d];
     // (one 8-byte record per departure lane instead of lane id -> lane record: the two loads of this check are independent)
     const DepInfo LR = rec_load8(T.cold.dep_info, d);
-    const float *vt = L.vtp + T.trip_vtype()[k] * VT_COLS;
+    const float *vt = L.vtp + rs_at(T.trip_vtype(), k) * VT_COLS;
     const float mypos = vt[VT_LENGTH] < LR.len ? vt[VT_LENGTH] : LR.len;
     // only vehicles with pos - length < mypos + minGap can be in the way
     const int nc = (int)(LR.len * L.cell_inv) + 1;      // lane_cells(L, )
@@ -1222,7 +1372,7 @@ template <class LT> RS_DEV int nth_free_slot(const LT &L, int C, int r) {      /
 }
 
 // the lane-change decision of the vehicle in slot s, queued for the move when it changes lanes (what a lane-change chunk does per entry)
-template <class LT> RS_DEV void lc_decide_and_flag(const KTab &T, const LT &L, const Grid &grid, const State &G, size_t eo, int t, int s) {
+template <class TT, class LT, class GT> RS_DEV void lc_decide_and_flag(const TT &T, const LT &L, const Grid &grid, const GT &G, size_t eo, int t, int s) {
     const Aux ax = L.aux[s];
     if (ax.lane == LANE_NONE) return;
     const int code = phase_lc_decide(T, L, grid, G, eo, t, s, ax, L.node[s]);
@@ -1234,8 +1384,8 @@ struct ExecInline {};
 
 // ------------------------------------------------------------------------------------------------ the step
 // CAP: the slot capacity as a compile-time constant (0: read it from the tables at run time)
-template <int CAP, class Exec, class LT>
-RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G, const Out &O, const KParams &P,
+template <int CAP, class Exec, class LT, class TT, class GT>
+RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const TT &T, const GT &G, const Out &O, const KParams &P,
                             const int32_t *actions, int env) {
     const int B = ex.B;
     const int C = CAP ? CAP : T.capacity, S = T.n_signals, NO = T.n_obs;
@@ -1290,7 +1440,7 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
             // a request of the last tick before this launch waits in the mailboxes: the first plan reads those of parity (t + 1) & 1
             if ((G.mail[(size_t)env * ((C + 31) / 32) + (s >> 5)] >> (s & 31)) & 1u) nn.sfq |= (uint16_t)SFQ_MAIL((L.sc[SC_T] + 1) & 1);
             nn.nxt = grid_push(Grid{grid0, 0u}, LR0.cell0 + cell_of(L, x, lane_cells(L, LR0)), s, sp > RM_HALT_SPEED);
-            if (n_ticks > 0) nn.fl = (uint8_t)classify(T, L, s, L.vtp + nn.vt * VT_COLS, sp, x, LR0, ln, rq, T.notbest()[rq], tr, sf_of(nn.sfq), L.sc[SC_T]);
+            if (n_ticks > 0) nn.fl = (uint8_t)classify(T, L, s, L.vtp + nn.vt * VT_COLS, sp, x, LR0, ln, rq, rs_at(T.notbest(), rq), tr, sf_of(nn.sfq), L.sc[SC_T]);
             L.node[s] = nn;
             rs_atomic_or(&L.alive[s >> 5], 1u << (s & 31));
         }
@@ -1436,7 +1586,7 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
                         const int s = nth_free_slot(L, C, rank);
                         if (s < 0) continue;
                         const int k = L.dep[d];
-                        const int v = T.trip_vtype()[k];
+                        const int v = rs_at(T.trip_vtype(), k);
                         const float *vt = L.vtp + v * VT_COLS;
                         const RouteRec RR = rec_load16(T.routes(), T.trip_route()[k]);
                         const LaneRec LRd = rec_load16(T.lanes(), RR.depart_lane);
@@ -1510,7 +1660,7 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
             const int oi = T.cold.lane_obs[lane];
             bool detect = false;
             if (oi >= 0) {
-                const float d = (LR.len - L.node[s].pos) + T.rsteps()[rq].tlsdist;
+                const float d = (LR.len - L.node[s].pos) + rs_at(T.rsteps(), rq).tlsdist;
                 detect = d <= P.max_distance;
             }
             if (!detect) {
@@ -1634,11 +1784,19 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const KTab &T, const State &G
 }
 
 // the step for a capacity known at compile time (CAP: the offsets that follow from it are literals) or at run time (CAP = 0)
-template <int CAP, class Exec>
-RS_DEV void rs_step_body(Exec &ex, const Lds &L, const KTab &T, const State &G, const Out &O, const KParams &P,
+template <int CAP, class Exec, class GT>
+RS_DEV void rs_step_body(Exec &ex, const Lds &L, const KTab &T, const GT &G, const Out &O, const KParams &P,
                          const int32_t *actions, int env) {
     if constexpr (CAP != 0) {
         const LdsFix<CAP> Lf(L);
         rs_step_body_on<CAP>(ex, Lf, T, G, O, P, actions, env);
     } else rs_step_body_on<CAP>(ex, L, T, G, O, P, actions, env);
 }
+// the step of one map: F = ScnFix_<map>, every scalar and every offset a literal (the host's Lds table is not read at all)
+template <class F, class Exec, class GT>
+RS_DEV void rs_step_body_fix(Exec &ex, const KTab &T, const GT &G, const Out &O, const KParams &P, const int32_t *actions, int env) {
+    const KTabFix<F> Tf(T);
+    const LdsScn<F> Lf{};
+    rs_step_body_on<F::capacity>(ex, Lf, Tf, G, O, P, actions, env);
+}
+#endif      // RS_LAYOUT_ONLY

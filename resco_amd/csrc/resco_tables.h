@@ -144,11 +144,14 @@ static_assert(sizeof(DepInfo) == 8 && alignof(DepInfo) == 8, "DepInfo: one 8-byt
 #define rec_load8(tab, i) ((tab)[i])
 #define link_load(tab, i) ((tab)[i])
 #else
+// The record's address is the (wave-uniform) table pointer plus an UNSIGNED 32-bit byte offset computed in 32 bits: that is the form for
+// which a gather takes the table's SGPR pair as its base and one VGPR as its offset (the `saddr` form of global_load) instead of a 64-bit
+// VGPR address built per lane (sign extension + v_lshl_add_u64, a VGPR pair).  Every table is far below 4 GiB (16-bit ids x 32 bytes).
 struct alignas(16) RecRaw16 { uint32_t a, b, c, d; };
 template <class R, class I> RS_MEM R rec_load16(const R *tab, I i) {
     static_assert(sizeof(R) == 16 && alignof(R) == 16, "rec_load16: a 16-byte record");
     RecRaw16 r;
-    __builtin_memcpy(&r, &tab[i], 16);
+    __builtin_memcpy(&r, (const char *)tab + (uint32_t)i * 16u, 16);
     RS_KEEP4(r.a, r.b, r.c, r.d)
     R out;
     __builtin_memcpy(&out, &r, 16);
@@ -157,7 +160,7 @@ template <class R, class I> RS_MEM R rec_load16(const R *tab, I i) {
 template <class R, class I> RS_MEM R rec_load8(const R *tab, I i) {
     static_assert(sizeof(R) == 8 && alignof(R) == 8, "rec_load8: an 8-byte record");
     struct alignas(8) Raw { uint32_t a, b; } r;
-    __builtin_memcpy(&r, &tab[i], 8);
+    __builtin_memcpy(&r, (const char *)tab + (uint32_t)i * 8u, 8);
     RS_KEEP2(r.a, r.b)
     R out;
     __builtin_memcpy(&out, &r, 8);
@@ -166,7 +169,7 @@ template <class R, class I> RS_MEM R rec_load8(const R *tab, I i) {
 // both halves of a link record are requested before either is used
 template <class I> RS_MEM LinkRec link_load(const LinkRec *tab, I i) {
     RecRaw16 r[2];
-    __builtin_memcpy(r, &tab[i], 32);
+    __builtin_memcpy(r, (const char *)tab + (uint32_t)i * 32u, 32);
     RS_KEEP4(r[0].a, r[0].b, r[0].c, r[0].d)
     RS_KEEP4(r[1].a, r[1].b, r[1].c, r[1].d)
     LinkRec out;

@@ -39,7 +39,7 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_mplight_dqn_create', 'rs_mplight_dqn_sample', 'rs_mplight_dqn_grad', 'rs_mplight_dqn_step', 'rs_mplight_dqn_update',
                'rs_mplight_dqn_steps', 'rs_mplight_dqn_destroy',
                'rs_idqn_pack_weights', 'rs_dqn_sync_target', 'rs_mplight_dqn_sync_target', 'rs_group_train',
-               'rs_ppo_perm', 'rs_ippo_pack_weights', 'rs_group_ppo_train']
+               'rs_ppo_perm', 'rs_ippo_pack_weights', 'rs_group_ppo_train', 'rs_info_kernel']
 
 # the FMA2C entry points (include/resco_sim.h: rs_fma2c_*)
 FMA2C_SYMBOLS = ['rs_fma2c_create', 'rs_fma2c_act', 'rs_fma2c_value', 'rs_fma2c_reset', 'rs_fma2c_set_device_weights', 'rs_fma2c_buffer',
@@ -79,6 +79,9 @@ def bind(L):
     L.rs_phase_profile.argtypes = [vp, i32, vp]
     L.rs_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.rs_group_step.argtypes = [vp, i32, vp, i32]
+    if hasattr(L, 'rs_info_kernel'):
+        L.rs_info_kernel.argtypes = [vp]
+        L.rs_info_kernel.restype = C.c_char_p
     if hasattr(L, 'rs_idqn_create'):
         L.rs_idqn_create.argtypes = [i32, i32, i32] + [vp] * 9 + [C.POINTER(vp)]
         L.rs_idqn_act.argtypes = [vp, vp, i32, i32, i32, f32, u32, u32, vp, vp, vp, vp]
@@ -434,7 +437,10 @@ class BatchedSim:
     def info(self):
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._lib.rs_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-        return dict(n_envs=a.value, block_threads=b.value, lds_bytes=c.value, max_lanes_per_signal=d.value)
+        out = dict(n_envs=a.value, block_threads=b.value, lds_bytes=c.value, max_lanes_per_signal=d.value)
+        if hasattr(self._lib, 'rs_info_kernel'):      # (a library built before the per-map step kernels has no such entry)
+            out['step_kernel'] = self._lib.rs_info_kernel(self._h).decode()
+        return out
 
     # ------------------------------------------------------------------ stepping
     def reset(self, stream=None):
