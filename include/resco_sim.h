@@ -759,6 +759,70 @@ int rs_fma2c_learn_reset(rs_fma2c_learn_handle l, void *stream);
 int rs_fma2c_learn_buffer(rs_fma2c_learn_handle l, int32_t which, void **dev_ptr);
 void rs_fma2c_learn_destroy(rs_fma2c_learn_handle l);
 
+/* ---- FMA2C: the reward on the device and the training loop in one call (resco_amd/csrc/resco_fma2c_loop.h) ----------------------
+ * rs_fma2c_reward_table (caller-owned DEVICE memory, as rs_rollout is): rewards.fma2c / fma2c_full (rewards.py:72-136) of all K agents
+ * are the linear form G W of VecMultiSignal.fma2c_rewards, G = [queue (n_obs) | max_wait (n_obs) | lane arrivals (n_obs) | signal
+ * arrivals (S) | signal departures (S)] per environment.  The table holds the non-zeros of W column by column, rows ascending (CSR
+ * over the agents, managers first as everywhere in rs_fma2c_*): off i32 [K + 1] from 0, idx i32 [off[K]] in 0 .. n_rows - 1, w f32
+ * [off[K]]; n_rows = 3 n_obs + 2 S.  The contents are NOT checked (the kernel cannot afford to, and they live on the device): an idx
+ * outside 0 .. n_rows - 1 reads out of bounds.  resco_amd/sim.py: Fma2cRewardTable asserts them before the upload.
+ *
+ * rs_fma2c_record: ONE launch on `stream` (NULL: the handle's), one thread per (environment, agent), after the step kernel.  G is
+ * never materialised: row r reads RS_BUF_LANE_AGG [e][r][0] (r < n_obs), RS_BUF_LANE_AGG [e][r - n_obs][3], RS_BUF_LANE_ARRIVALS,
+ * RS_BUF_ARRIVALS or RS_BUF_DEPARTURES, the counts cast to float.  rew_out[e][k] = the RAW reward (the learner normalises and clips):
+ * acc = 0.0f, then acc = acc + G[idx] * w over the column's entries in stored order, product and sum each rounded (the build's
+ * contraction is off), so a host restatement gives the same bits.  acts_out[e][k] (or NULL) = the policy's manager action of
+ * environment env_base + e for k < M, else RS_BUF_ACTIONS[e][k - M] -- the step kernel only reads RS_BUF_ACTIONS, so the actions of
+ * the step are still there after it and one launch records actions and rewards together.  ret_acc[e][k] (or NULL) += the reward.
+ * Refusals (RS_EINVAL, text in rs_last_error of the handle and of NULL, nothing launched): a NULL handle, policy, table, table
+ * pointer or rew_out; a policy that is not rs_fma2c_create's, lives on another device or does not fit the scenario (n_signals, n_obs,
+ * env_base + n_envs <= max_envs); table->K != the policy's K; n_rows != 3 n_obs + 2 S; RS_BUF_LANE_AGG or RS_BUF_LANE_ARRIVALS
+ * switched off with rs_set_outputs.
+ *
+ * rs_group_fma2c_train: FusedA2CLearner.observe's loop (tools/fma2c_train.py --device-update) for k < n_steps, with slot i = (slot0 +
+ * k) mod T, everything on the LEGACY default stream (hipStreamLegacy: PyTorch's default stream):
+ *   1. rs_fma2c_act with key t0 + k on the handle's RS_BUF_LANE_AGG: rows_out and value_out straight into slot i of rows and vals,
+ *      the workers' actions into RS_BUF_ACTIONS;
+ *   2. the step kernel;
+ *   3. rs_fma2c_record into slot i of rews and acts (and ret_acc);
+ *   4. dones[i + 1] = (k == done_step), written by a kernel (one launch for the slots a call fills up to the next update);
+ *   5. when i == T - 1 or k == done_step, the update: R_boot = zeros at done, rs_fma2c_value otherwise; the launches of
+ *      rs_fma2c_learn_update on the first i + 1 slots with states_fw = the policy's state buffer (the hand-over of the state is a
+ *      kernel here, no memcpy); dones[0] = dones[i + 1] by a kernel; at done what rs_fma2c_learn_reset does (states_bw zeroed).
+ * A segment is cut at the episode's end: after a done the caller goes on with slot0 = 0 (unlike rs_group_ppo_train), otherwise with
+ * (slot0 + n_steps) mod T, and with t0 + n_steps either way.  A call does not run past a done: done_step is -1 or n_steps - 1.  The
+ * reset of simulator and policy between episodes stays with the caller.  ONE handle, for the reasons of rs_group_ppo_train.  The call
+ * creates no stream, no event and no wait and uses no asynchronous memcpy; the library keeps no loop state.  Asynchronous.  NOT
+ * checked: the sizes of the buffers, the table's contents.
+ * Refusals (RS_EINVAL, text in rs_last_error of the handle and of NULL, nothing launched): n_handles != 1; n_steps < 1; T outside 1
+ * .. t_max of the learner; slot0 outside 0 .. T - 1; done_step outside -1 .. n_steps - 1, or inside it but not n_steps - 1; a negative
+ * t0; a NULL buffer (ret_acc and loss_out may be NULL); a policy that is not rs_fma2c_create's, does not fit the scenario or whose
+ * max_envs is not the handle's n_envs (with env_base 0); a learner created for another policy; what rs_fma2c_record refuses of the
+ * table and the switched-off outputs; a non-blocking handle stream; rs_timing enabled. */
+typedef struct rs_fma2c_reward_table {
+    int32_t K, n_rows;
+    const int32_t *off /* [K + 1] */, *idx;
+    const float *w;
+} rs_fma2c_reward_table;
+typedef struct rs_fma2c_train {
+    rs_policy_handle policy;
+    rs_fma2c_learn_handle learner;
+    rs_fma2c_reward_table table;
+    float *rows;                 /* device [T][n_envs][K][W]: the learner's segment */
+    int32_t *acts;               /* device [T][n_envs][K] */
+    float *rews, *vals;          /* device [T][n_envs][K] */
+    int32_t *dones;              /* device [T + 1] */
+    float *R_boot;               /* device [n_envs][K] */
+    float *ret_acc;              /* device [n_envs][K] or NULL */
+    float *loss_out;             /* device [K] or NULL */
+    int64_t t0;                  /* env-steps before this call: key of the first step */
+    int32_t T, slot0, done_step; /* slots of a segment; filled slots at entry (0 .. T-1); -1 or n_steps - 1: the horizon is reached there */
+    uint32_t policy_seed;
+} rs_fma2c_train;
+int rs_fma2c_record(rs_handle h, rs_policy_handle p, const rs_fma2c_reward_table *tab, float *rew_out /* [n_envs][K] */,
+                    int32_t *acts_out /* [n_envs][K] or NULL */, float *ret_acc /* [n_envs][K] or NULL */, void *stream);
+int rs_group_fma2c_train(const rs_handle *handles, int32_t n_handles, const rs_fma2c_train *tr, int32_t n_steps);
+
 /* static facts */
 int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal);
 /* the step kernel the handle launches: "rs_step_kernel_fix_v64<ingolstadt21>" -- the kernel of a shipped map, whose table scalars and

@@ -1,4 +1,4 @@
-"""ctypes mirror of the C-ABI structs in include/resco_sim.h (rs_scenario / rs_params / rs_train / rs_rollout / rs_ppo_train)."""
+"""ctypes mirror of the C-ABI structs in include/resco_sim.h (rs_scenario / rs_params / rs_train / rs_rollout / rs_ppo_train / rs_fma2c_reward_table / rs_fma2c_train)."""
 import ctypes as C
 
 import numpy as np
@@ -70,6 +70,20 @@ class PPOTrainStruct(C.Structure):
                 ('adv', C.c_void_p), ('ret', C.c_void_p), ('gae_scratch', C.c_void_p), ('perm', C.c_void_p), ('loss_out', C.c_void_p),
                 ('t0', C.c_int64), ('update0', C.c_int64), ('slot0', C.c_int32), ('done_step', C.c_int32), ('epochs', C.c_int32),
                 ('minibatch', C.c_int32), ('gamma', C.c_float), ('lambda', C.c_float), ('policy_seed', C.c_uint32), ('learner_seed', C.c_uint32)]
+
+
+class Fma2cRewardTableStruct(C.Structure):
+    """rs_fma2c_reward_table: the non-zeros of the FMA2C reward matrix, CSR over the agents, in caller-owned device memory"""
+    _fields_ = [('K', C.c_int32), ('n_rows', C.c_int32), ('off', C.c_void_p), ('idx', C.c_void_p), ('w', C.c_void_p)]
+
+
+class Fma2cTrainStruct(C.Structure):
+    """rs_fma2c_train: what rs_group_fma2c_train is told about the policy, the learner, the reward table, the learner's segment and
+    the position (field order of the header)"""
+    _fields_ = [('policy', C.c_void_p), ('learner', C.c_void_p), ('table', Fma2cRewardTableStruct), ('rows', C.c_void_p), ('acts', C.c_void_p),
+                ('rews', C.c_void_p), ('vals', C.c_void_p), ('dones', C.c_void_p), ('R_boot', C.c_void_p), ('ret_acc', C.c_void_p),
+                ('loss_out', C.c_void_p), ('t0', C.c_int64), ('T', C.c_int32), ('slot0', C.c_int32), ('done_step', C.c_int32),
+                ('policy_seed', C.c_uint32)]
 
 
 def pack_scenario(sc, step_length=10, yellow_length=None):

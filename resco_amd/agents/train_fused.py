@@ -13,10 +13,17 @@ can be mixed step by step and give the same bits.  The reset between episodes st
 policy.value, learner.update_from_rollout with the learner's device_perm shuffles, policy.refresh_on_device.  One environment (one
 handle), a FusedPPOLearner, a FusedIPPO and a DeviceRollout over that handle; the trainer owns the update's buffers (done bytes,
 bootstrap value, advantages, returns, shuffles).
+
+`DeviceA2CTrainer(env, learner, policy, full=False)` does the same for the loop of tools/fma2c_train.py --device-update
+(rs_group_fma2c_train; resco_amd/csrc/resco_fma2c_loop.h): policy.act into the learner's slot, env.step, the rewards (by the reward
+kernel of rs_fma2c_record, not the dense product), ret += rew and FusedA2CLearner.observe.  One environment, a FusedA2CLearner and a
+FusedFMA2C; the trainer owns the uploaded reward table, the bootstrap value and the return accumulator.
 """
 import torch
 
-from ..sim import DQNRing, MPLightRing, SimGroup
+from ..sim import DQNRing, Fma2cRewardTable, MPLightRing, SimGroup
+from .fma2c import FusedFMA2C
+from .fma2c_learn_fused import FusedA2CLearner
 from .idqn_learn import linear_epsilon
 from .idqn_learn_fused import FusedDQNLearner
 from .ippo_fused import FusedIPPO
@@ -119,5 +126,57 @@ class DevicePPOTrainer:
                              learner_seed=L.seed, loss_out=ptr(L.loss_out))
         self.updates += (self.slot + n) // T
         self.slot = (self.slot + n) % T
+        self.t += n
+        return env.advance(n)
+
+
+class DeviceA2CTrainer:
+    def __init__(self, env, learner, policy, full=False):
+        if not isinstance(learner, FusedA2CLearner) or not isinstance(policy, FusedFMA2C):
+            raise TypeError('DeviceA2CTrainer needs a FusedA2CLearner and a FusedFMA2C: the loop runs in the library (there is no CPU fallback)')
+        if learner.policy is not policy:
+            raise ValueError('the learner was created for another policy')
+        if learner.N != env.sim.n_envs or policy.max_envs != env.sim.n_envs:
+            raise ValueError('learner (%d) and policy (%d) must be built for the environment\'s %d environments' % (learner.N, policy.max_envs, env.sim.n_envs))
+        self.env, self.learner, self.policy, self.full = env, learner, policy, bool(full)
+        self.group = SimGroup([env.sim])
+        L = policy.L
+        self.table = Fma2cRewardTable(env.scenario, L.cfg, full, env.sim.device)
+        dev = 'cuda:%d' % env.sim.device
+        self.R_boot = torch.zeros(env.sim.n_envs, L.K, dtype=torch.float32, device=dev)
+        self.ret = torch.zeros(env.sim.n_envs, L.K, dtype=torch.float32, device=dev)    # the episode's return: zero it at a reset
+        self.t = 0                              # env-steps so far: the key of the next act
+
+    def run(self, n_steps):
+        """n_steps env-steps of training, enqueued by one call; asynchronous.  Advances the step counter, the environment's step
+        counter and the learner's host counters (n, steps_done, updates, dones, last_loss) as FusedA2CLearner.observe would have, so
+        calls and Python observe steps can alternate, and returns done (the episode's horizon is reached)."""
+        n, env, L = int(n_steps), self.env, self.learner
+        if n < 1:
+            raise ValueError('need n_steps >= 1')
+        if env.steps + n > env.horizon_steps:
+            raise ValueError('%d steps from step %d would cross the horizon (%d): the reset between episodes is the caller\'s' %
+                             (n, env.steps, env.horizon_steps))
+        if torch.cuda.current_stream().cuda_stream != 0:
+            raise ValueError('DeviceA2CTrainer needs PyTorch\'s default stream current: the loop is launched on the legacy stream')
+        done_step = n - 1 if env.steps + n == env.horizon_steps else -1
+        ptr = lambda t: t.data_ptr()
+        self.group.fma2c_train(n, self.policy.handle, L.handle, self.table, ptr(L.rows), ptr(L.acts), ptr(L.rews), ptr(L.vals), ptr(L.dones_dev),
+                               ptr(self.R_boot), L.T, self.t, L.n, done_step=done_step, policy_seed=self.policy.seed, ret=ptr(self.ret),
+                               loss_out=ptr(L._loss))
+        updated = False
+        for k in range(n):                      # FusedA2CLearner.observe's bookkeeping, step by step
+            done = k == done_step
+            L.dones.append(done)
+            L.n += 1
+            L.steps_done += 1
+            if L.steps_done % L.T == 0 or done:
+                L.dones, L.n = [L.dones[-1]], 0
+                L.updates += 1
+                updated = True
+            if done:
+                L.steps_done = 0
+        if updated:
+            L.last_loss = L._loss.clone()
         self.t += n
         return env.advance(n)

@@ -119,6 +119,7 @@ __device__ unsigned long long *g_sec_prof;
 #include "resco_group_train.h"
 #include "resco_ppo_loop.h"
 #include "resco_fma2c_train.h"
+#include "resco_fma2c_loop.h"
 
 // ------------------------------------------------------------------------------------------------ kernels
 // The tables / state / output descriptors live in ONE constant block in device memory (StepArgs): passed by value they
@@ -1345,6 +1346,12 @@ static void fma2c_act_launch(const rs_policy *p, const float *lane_agg, int n_en
     hipLaunchKernelGGL(rs_fma2c_kernel<true>, dim3(tiles, A.S), dim3(256), p->fm_lds, st, A, lane_agg, n_envs, env_base, A.M, seed, step_key, (const uint32_t *)dyn, out);
 }
 
+// the bootstrap value: the value net of all agents in one launch
+static void fma2c_value_launch(const rs_policy *p, const float *lane_agg, int n_envs, int env_base, float *value_out, hipStream_t st) {
+    hipLaunchKernelGGL(rs_fma2c_kernel<false>, dim3((n_envs + FM_TM - 1) / FM_TM, p->A.K), dim3(256), p->fm_lds, st, p->A, lane_agg, n_envs,
+                       env_base, 0, 0u, 0u, (const uint32_t *)nullptr, Fma2cOut{nullptr, nullptr, value_out, nullptr});
+}
+
 static int fma2c_check(rs_policy_handle p, int32_t n_envs, int32_t env_base, const char *kind_msg, const char *range_msg) {
     if (!p) return fma2c_refuse("rs_fma2c: NULL policy handle");
     if (p->kind != POLICY_FMA2C) return fma2c_refuse(kind_msg);
@@ -1367,8 +1374,7 @@ extern "C" int rs_fma2c_value(rs_policy_handle p, const float *lane_agg, int32_t
                              "rs_fma2c_value: need 1 <= n_envs, 0 <= env_base, env_base + n_envs <= max_envs")) return rc;
     if (!lane_agg || !value_out) return fma2c_refuse("rs_fma2c_value: lane_agg or value_out is NULL");
     if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    hipLaunchKernelGGL(rs_fma2c_kernel<false>, dim3((n_envs + FM_TM - 1) / FM_TM, p->A.K), dim3(256), p->fm_lds, (hipStream_t)stream, p->A, lane_agg, n_envs,
-                       env_base, 0, 0u, 0u, (const uint32_t *)nullptr, Fma2cOut{nullptr, nullptr, value_out, nullptr});
+    fma2c_value_launch(p, lane_agg, n_envs, env_base, value_out, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
 }
 
@@ -2069,6 +2075,101 @@ extern "C" int rs_group_ppo_train(const rs_handle *hs, int32_t n_handles, const 
         ppo_perm_launch(n, tr->epochs, tr->learner_seed, P.update_key, tr->perm, st);
         ppo_fit_launch(pp, R.obs, R.act, R.logp, tr->adv, tr->ret, n, tr->perm, tr->epochs, tr->minibatch, tr->loss_out, st);
         ippo_pack_launch(pol, pp->T.par, st);
+        HIPCHK(h, hipGetLastError());
+    }
+    return RS_OK;
+}
+
+// ---- rs_fma2c_record: the reward of all agents and the recorder of a step (resco_fma2c_loop.h), one launch
+// why a call with this handle, policy and table is refused, or NULL
+static const char *fma2c_record_refusal(const rs_sim *h, const rs_policy *p, const rs_fma2c_reward_table *tab) {
+    if (!p) return "the policy handle is NULL";
+    if (!tab || !tab->off || !tab->idx || !tab->w) return "the reward table or one of its pointers is NULL";
+    if (p->kind != POLICY_FMA2C) return "the policy is not an rs_fma2c_create policy";
+    if (p->A.S != h->K.n_signals || p->A.O != h->K.n_obs) return "needs a policy built for this scenario (n_signals, n_obs)";
+    if (p->device != h->device) return "the policy lives on another device than the handle";
+    if (h->P.env_base < 0 || (int64_t)h->P.env_base + h->n_envs > p->A.max_envs) return "env_base + n_envs of the handle exceeds the policy's max_envs";
+    if (tab->K != p->A.K) return "the reward table's K is not the policy's K";
+    if (tab->n_rows != 3 * h->K.n_obs + 2 * h->K.n_signals) return "the reward table's n_rows is not 3 n_obs + 2 S of this scenario";
+    if (!(h->out_mask & OUT_LANE_AGG)) return "the reward reads RS_BUF_LANE_AGG, which rs_set_outputs has switched off";
+    if (!(h->out_mask & OUT_LANE_ARR)) return "the reward reads RS_BUF_LANE_ARRIVALS, which rs_set_outputs has switched off";
+    return nullptr;
+}
+static void fma2c_record_launch(const rs_sim *h, const rs_policy *p, const rs_fma2c_reward_table &tab, float *rew, int32_t *acts, float *ret, hipStream_t st) {
+    const Fma2cTab &A = p->A;
+    const FlRec R{A.K, A.M, h->K.n_obs, h->K.n_signals, h->n_envs, tab.off, tab.idx, tab.w, h->O.lane_agg(), h->O.lane_arr(), h->O.arrivals(),
+                  h->O.departures(), A.macts + (size_t)h->P.env_base * A.M, h->actions, rew, acts, ret};
+    const size_t n = (size_t)h->n_envs * A.K;
+    hipLaunchKernelGGL(rs_fma2c_record_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, R);
+}
+extern "C" int rs_fma2c_record(rs_handle h, rs_policy_handle p, const rs_fma2c_reward_table *tab, float *rew_out, int32_t *acts_out, float *ret_acc,
+                               void *stream) {
+    if (!h) { g_create_err = "rs_fma2c_record: NULL handle"; return RS_EINVAL; }
+    const char *why = fma2c_record_refusal(h, p, tab);
+    if (!why && !rew_out) why = "rew_out is NULL";
+    if (why) { h->err = std::string("rs_fma2c_record: ") + why; g_create_err = h->err; return RS_EINVAL; }
+    hipStream_t st;
+    if (int rc = enter(h, stream, &st)) return rc;
+    fma2c_record_launch(h, p, *tab, rew_out, acts_out, ret_acc, st);
+    HIPCHK(h, hipGetLastError());
+    return RS_OK;
+}
+
+// ---- rs_group_fma2c_train: the --device-update loop of tools/fma2c_train.py (FusedA2CLearner.observe), n_steps iterations enqueued by
+// one call (include/resco_sim.h).  Everything goes to the legacy stream, in the tool's order: per step the act into the segment's slot,
+// the step kernel and the recorder (with the done words of the slots ahead written once per run of slots); after the step that fills
+// the last slot or ends the episode the bootstrap value (zeros at done), the update's launches, the hand-over of the state and the
+// carried done word.  No stream, event, wait or asynchronous memcpy is made here.
+extern "C" int rs_group_fma2c_train(const rs_handle *hs, int32_t n_handles, const rs_fma2c_train *tr, int32_t n_steps) {
+    if (!hs || n_handles < 1 || !hs[0]) { g_create_err = "rs_group_fma2c_train: NULL handles"; return RS_EINVAL; }
+    rs_sim *h = hs[0];
+    auto refuse = [&](const std::string &why) { h->err = "rs_group_fma2c_train: " + why; g_create_err = h->err; return RS_EINVAL; };
+    if (n_handles != 1) return refuse("one handle only: a segment has no row stride, and pipes in training were measured below one handle");
+    if (!tr) return refuse("NULL arguments");
+    if (n_steps < 1) return refuse("need n_steps >= 1");
+    if (!tr->policy || !tr->learner) return refuse("the policy or the learner handle is NULL");
+    rs_policy *pol = tr->policy;
+    rs_fma2c_learn *l = tr->learner;
+    const int T = tr->T;
+    if (T < 1 || T > l->t_max) return refuse("need 1 <= T <= t_max of the learner");
+    if (tr->slot0 < 0 || tr->slot0 > T - 1) return refuse("slot0 must be one of the segment's slots, 0 .. T - 1");
+    if (tr->done_step < -1 || tr->done_step > n_steps - 1) return refuse("done_step must be -1 (no episode ends in this call) or a step of this call, 0 .. n_steps - 1");
+    if (tr->done_step != -1 && tr->done_step != n_steps - 1) return refuse("done_step must be the call's last step, n_steps - 1: a call does not run past a done");
+    if (tr->t0 < 0) return refuse("need t0 >= 0");
+    if (!tr->rows || !tr->acts || !tr->rews || !tr->vals || !tr->dones || !tr->R_boot)
+        return refuse("a buffer pointer is NULL (rows, acts, rews, vals, dones, R_boot)");
+    if (const char *why = fma2c_record_refusal(h, pol, &tr->table)) return refuse(why);
+    if (pol->A.max_envs != h->n_envs || h->P.env_base != 0) return refuse("the policy's max_envs must be the handle's n_envs (and its env_base 0): the learner's segment is the policy's batch");
+    if (l->pol != pol) return refuse("the learner was created for another policy");
+    if (!h->blocking) return refuse("this handle's stream is a non-blocking stream (RESCO_PLAIN_STREAMS, or hipExtStreamCreateWithCUMask failed at rs_create): "
+                                    "nothing would order its other launches with this loop's on the legacy stream");
+    if (h->timing) return refuse("rs_timing is enabled on this handle: its events are not part of this loop");
+
+    const Fma2cTab &A = pol->A;
+    const int N = h->n_envs;
+    const size_t nk = (size_t)N * A.K, n_state = nk * 4 * FM_L;
+    for (int k = 0; k < n_steps; ++k) {
+        const FlStep P = fl_plan(T, tr->slot0, tr->t0, tr->done_step, k);
+        hipStream_t st;
+        if (int rc = enter(h, (void *)hipStreamLegacy, &st)) return rc;
+        if (k == 0 || P.slot == 0) {        // the post-step dones of the slots this call fills from here to the next update
+            const int m = T - P.slot < n_steps - k ? T - P.slot : n_steps - k;
+            hipLaunchKernelGGL(rs_fma2c_done_kernel, dim3((m + 255) / 256), dim3(256), 0, st, tr->dones + P.slot + 1, m, tr->done_step - k);
+        }
+        const size_t at = (size_t)P.slot * nk;
+        fma2c_act_launch(pol, h->O.lane_agg(), N, 0, tr->policy_seed, P.key, nullptr, Fma2cOut{h->actions, nullptr, tr->vals + at, tr->rows + at * A.W}, st);
+        HIPCHK(h, hipGetLastError());
+        if (int rc = launch_step(h, st, h->K.step_length * h->ratio, 1)) return rc;
+        fma2c_record_launch(h, pol, tr->table, tr->rews + at, tr->acts + at, tr->ret_acc, st);
+        HIPCHK(h, hipGetLastError());
+        if (!P.update) continue;
+        if (P.done) hipLaunchKernelGGL(ft_fill_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, tr->R_boot, nk, 0.0f);
+        else fma2c_value_launch(pol, h->O.lane_agg(), N, 0, tr->R_boot, st);
+        HIPCHK(h, hipGetLastError());
+        if (ft_grad_launch(l, tr->rows, tr->acts, tr->rews, tr->vals, tr->dones, tr->R_boot, P.n_slots, tr->loss_out, st) != RS_OK ||
+            ft_step_launch(l, st) != RS_OK) { h->err = "rs_group_fma2c_train: a launch of the update failed"; return RS_EHIP; }
+        hipLaunchKernelGGL(rs_fma2c_state_kernel, dim3((unsigned)((n_state + 255) / 256)), dim3(256), 0, st, l->states_bw, (const float *)A.state, n_state, P.done);
+        hipLaunchKernelGGL(rs_fma2c_done_carry_kernel, dim3(1), dim3(64), 0, st, tr->dones, P.n_slots);
         HIPCHK(h, hipGetLastError());
     }
     return RS_OK;

@@ -433,6 +433,63 @@ def fma2c_state_tables(sc, cfg, full=False):
     return keys, s_idx, s_scale, lanes, lane_pos, fringes, same_region
 
 
+def fma2c_reward_matrix(sc, cfg, full=False):
+    """The matrix W float32 [3 O + 2 S, S + M] of rewards.fma2c / fma2c_full (reference rewards.py:72-136): every reward is the linear
+    form G @ W of G = [queue (O), max_wait (O), lane arrivals (O), signal arrivals (S), signal departures (S)] per environment.
+    Columns in the key order of fma2c_state_tables: signals in all_ts_ids order, then managers.  cfg: the ACTIVE mdp_configs['FMA2C' |
+    'FMA2CFull'] of the map.  No GPU is needed."""
+    sup, alpha = cfg['supervisors'], float(cfg['alpha'])
+    ids = list(sc.signal_ids)
+    O, S = sc.n_obs, len(ids)
+    keys, _, _, lanes, lane_pos, fringes, same_region = fma2c_state_tables(sc, cfg, full)
+    W = np.zeros((3 * O + 2 * S, len(keys)), np.float32)
+    own = np.zeros((3 * O + 2 * S, S), np.float32)
+    for i, sid in enumerate(ids):
+        for l in lanes[sid]:
+            own[lane_pos[l], i] -= 1.0
+            own[O + lane_pos[l], i] -= float(cfg['coef'])
+    pos = {sid: i for i, sid in enumerate(ids)}
+    for i, sid in enumerate(ids):
+        W[:, i] = own[:, i]
+        for nb in same_region[sid]:
+            W[:, i] += alpha * own[:, pos[nb]]
+    mg = {mgr: np.zeros(3 * O + 2 * S, np.float32) for mgr in cfg['management']}
+    for i, sid in enumerate(ids):
+        m = mg[sup[sid]]
+        m[3 * O + S + i] += 1.0         # departures
+        m[3 * O + i] -= 1.0             # arrivals
+        for l in lanes[sid]:
+            if l in fringes[sup[sid]]:
+                m[2 * O + lane_pos[l]] += 1.0
+    for j, mgr in enumerate(cfg['management']):
+        W[:, S + j] = mg[mgr]
+        for n in cfg['management_neighbors'][mgr]:
+            W[:, S + j] += alpha * mg[n]
+    return W
+
+
+def fma2c_reward_csr(W, columns=None):
+    """The non-zeros of W [R, K] column by column, rows ascending, as the three arrays of rs_fma2c_reward_table (include/resco_sim.h):
+    off int32 [K + 1], idx int32 [nnz], w float32 [nnz].  columns: the order the columns are stored in (default: W's own)."""
+    W = np.asarray(W, np.float32)
+    cols = range(W.shape[1]) if columns is None else columns
+    off, idx, w = [0], [], []
+    for j in cols:
+        nz = np.flatnonzero(W[:, j])
+        idx.append(nz.astype(np.int32))
+        w.append(W[nz, j])
+        off.append(off[-1] + len(nz))
+    return np.asarray(off, np.int32), np.concatenate(idx).astype(np.int32), np.concatenate(w).astype(np.float32)
+
+
+def fma2c_reward_table(sc, cfg, full=False):
+    """(off, idx, w, n_rows) of the reward matrix with its columns in the order of the learner's agents -- FMA2CLayout.agents:
+    managers in `management` order, then the signals -- which is what rs_fma2c_record and rs_group_fma2c_train read"""
+    W = fma2c_reward_matrix(sc, cfg, full)
+    S, M = len(sc.signal_ids), len(cfg['management'])
+    return fma2c_reward_csr(W, list(range(S, S + M)) + list(range(S))) + (W.shape[0],)
+
+
 class VecMultiSignal:
     """N lock-step environments on one GPU; observations / rewards are zero-copy torch tensors over the
     library-owned device buffers (the agent boundary), actions are an int32 [N, S] tensor or None (actions
@@ -502,37 +559,12 @@ class VecMultiSignal:
             return cache[full]
         from .config.mdp_config import mdp_configs
         cfg, sc = mdp_configs['FMA2CFull' if full else 'FMA2C'], self.scenario
-        sup, alpha = cfg['supervisors'], float(cfg['alpha'])
-        ids = self.all_ts_ids
-        O, S = sc.n_obs, self.n_signals
-        keys, s_idx, s_scale, lanes, lane_pos, fringes, same_region = fma2c_state_tables(sc, cfg, full)
+        keys, s_idx, s_scale = fma2c_state_tables(sc, cfg, full)[:3]
         dev = self.tensor('lane_agg').device
         st = {k: (torch.as_tensor(s_idx[k], dtype=torch.long, device=dev), torch.as_tensor(s_scale[k], dtype=torch.float32, device=dev))
               for k in keys}
         # rewards: G = [queue (O), max_wait (O), lane arrivals (O), signal arrivals (S), signal departures (S)] @ W
-        W = np.zeros((3 * O + 2 * S, len(keys)), np.float32)
-        own = np.zeros((3 * O + 2 * S, S), np.float32)
-        for i, sid in enumerate(ids):
-            for l in lanes[sid]:
-                own[lane_pos[l], i] -= 1.0
-                own[O + lane_pos[l], i] -= float(cfg['coef'])
-        pos = {sid: i for i, sid in enumerate(ids)}
-        for i, sid in enumerate(ids):
-            W[:, i] = own[:, i]
-            for nb in same_region[sid]:
-                W[:, i] += alpha * own[:, pos[nb]]
-        mg = {mgr: np.zeros(3 * O + 2 * S, np.float32) for mgr in cfg['management']}
-        for i, sid in enumerate(ids):
-            m = mg[sup[sid]]
-            m[3 * O + S + i] += 1.0         # departures
-            m[3 * O + i] -= 1.0             # arrivals
-            for l in lanes[sid]:
-                if l in fringes[sup[sid]]:
-                    m[2 * O + lane_pos[l]] += 1.0
-        for j, mgr in enumerate(cfg['management']):
-            W[:, S + j] = mg[mgr]
-            for n in cfg['management_neighbors'][mgr]:
-                W[:, S + j] += alpha * mg[n]
+        W = fma2c_reward_matrix(sc, cfg, full)
         cache[full] = dict(cfg=cfg, keys=keys, states=st, W=torch.as_tensor(W, device=dev), full=full)
         return cache[full]
 
@@ -559,6 +591,29 @@ class VecMultiSignal:
                        self.tensor('departures').float()), dim=1)
         R = G @ t['W']
         return {k: R[:, j] for j, k in enumerate(t['keys'])}
+
+    def fma2c_rewards_device(self, full=False, out=None, policy=None):
+        """The rewards of fma2c_rewards for all K agents as ONE f32 tensor [N, K] in the order of the learner's agents (managers
+        first), by one HIP kernel on the library's buffers (rs_fma2c_record: neither actions nor a return are recorded) instead of
+        the casts, the cat and the dense product.  The summation order is the kernel's (a column's non-zeros, rows ascending), so the
+        values differ from fma2c_rewards' in the last bits.  policy: the FusedFMA2C of these environments -- the entry point takes
+        its agent counts from it; needed on the first call, remembered afterwards.  out: an f32 [N, K] device tensor to write."""
+        import torch
+        from .sim import Fma2cRewardTable, torch_stream
+        if policy is not None:
+            self._fma2c_policy = policy
+        policy = getattr(self, '_fma2c_policy', None)
+        if policy is None:
+            raise ValueError('fma2c_rewards_device needs the FusedFMA2C policy of these environments on its first call (policy=...)')
+        t = self._fma2c_tables(full)
+        if 'table' not in t:
+            t['table'] = Fma2cRewardTable(self.scenario, t['cfg'], full, self.sim.device)
+        K = t['table'].K
+        if out is None:
+            out = torch.empty(self.n_envs, K, dtype=torch.float32, device=self.tensor('lane_agg').device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (self.n_envs, K)
+        self.sim.fma2c_record(policy.handle, t['table'], out, stream=torch_stream(self.sim.device))
+        return out
 
     def _pack(self):
         obs = {}

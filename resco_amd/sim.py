@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from ._abi import ParamsStruct, PPOTrainStruct, RolloutStruct, TrainStruct, pack_scenario
+from ._abi import Fma2cRewardTableStruct, Fma2cTrainStruct, ParamsStruct, PPOTrainStruct, RolloutStruct, TrainStruct, pack_scenario
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RESCO_SIM_LIB: another build of the same HIP library (A/B variants compiled with different -D switches, tools/ab.py)
@@ -44,7 +44,9 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
 # the FMA2C entry points (include/resco_sim.h: rs_fma2c_*)
 FMA2C_SYMBOLS = ['rs_fma2c_create', 'rs_fma2c_act', 'rs_fma2c_value', 'rs_fma2c_reset', 'rs_fma2c_set_device_weights', 'rs_fma2c_buffer',
                  'rs_fma2c_destroy', 'rs_fma2c_learn_create', 'rs_fma2c_learn_grad', 'rs_fma2c_learn_step', 'rs_fma2c_learn_update',
-                 'rs_fma2c_learn_reset', 'rs_fma2c_learn_buffer', 'rs_fma2c_learn_destroy']
+                 'rs_fma2c_learn_reset', 'rs_fma2c_learn_buffer', 'rs_fma2c_learn_destroy', 'rs_fma2c_record']
+# the FMA2C training loop (include/resco_sim.h: rs_group_fma2c_train)
+FMA2C_LOOP_SYMBOLS = ['rs_group_fma2c_train']
 
 _lib = None
 
@@ -155,6 +157,9 @@ def bind(L):
         L.rs_fma2c_learn_buffer.argtypes = [vp, i32, C.POINTER(vp)]
         L.rs_fma2c_learn_destroy.argtypes = [vp]
         L.rs_fma2c_learn_destroy.restype = None
+    if hasattr(L, 'rs_group_fma2c_train'):
+        L.rs_fma2c_record.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.rs_group_fma2c_train.argtypes = [vp, i32, vp, i32]
     if hasattr(L, 'rs_default_block'):      # (the host emulation of the CPU tests exports only what it implements)
         L.rs_default_block.argtypes = [i32, i32, i32]
         L.rs_default_block.restype = i32
@@ -201,6 +206,29 @@ class Fma2cDesc(C.Structure):
     ARRAYS = ('n_a', 'n_s', 'n_w', 'n_f', 'gather_off', 'gather_idx', 'gather_scale', 'fp_off', 'fp_src', 'mgr_off', 'mgr_src')
     _fields_ = [(k, C.c_int32) for k in ('K', 'M', 'S', 'n_obs', 'full')] + \
                [(k, C.c_float) for k in ('norm_wave', 'clip_wave', 'norm_wait', 'clip_wait')] + [(k, C.c_void_p) for k in ARRAYS]
+
+
+class Fma2cRewardTable:
+    """The reward matrix of rewards.fma2c / fma2c_full as rs_fma2c_reward_table (include/resco_sim.h): the CSR arrays of
+    multi_signal.fma2c_reward_table uploaded to the device, agents in the learner's order (managers first).  The library does NOT
+    check the contents, so they are asserted here before the upload.  `struct` is what the entry points take; the tensors live as
+    long as this object."""
+
+    def __init__(self, scenario, cfg, full=False, device=0):
+        import torch
+        from .multi_signal import fma2c_reward_table
+        off, idx, w, n_rows = fma2c_reward_table(scenario, cfg, full)
+        K = len(off) - 1
+        assert n_rows == 3 * scenario.n_obs + 2 * scenario.n_signals
+        assert off.dtype == np.int32 and idx.dtype == np.int32 and w.dtype == np.float32 and len(idx) == len(w) == int(off[-1])
+        assert off[0] == 0 and bool((np.diff(off) >= 0).all()), 'off must be non-decreasing from 0'
+        assert len(idx) == 0 or (0 <= int(idx.min()) and int(idx.max()) < n_rows), 'idx outside 0 .. n_rows - 1'
+        dev = 'cuda:%d' % int(device)
+        self.K, self.n_rows, self.nnz = K, int(n_rows), len(idx)
+        self.off = torch.as_tensor(off, device=dev)
+        self.idx = torch.as_tensor(idx if len(idx) else np.zeros(1, np.int32), device=dev)
+        self.w = torch.as_tensor(w if len(w) else np.zeros(1, np.float32), device=dev)
+        self.struct = Fma2cRewardTableStruct(K, self.n_rows, self.off.data_ptr(), self.idx.data_ptr(), self.w.data_ptr())
 
 
 Rollout = RolloutStruct     # ctypes mirror of rs_rollout (include/resco_sim.h): the device buffers of one handle's trajectory segment
@@ -315,6 +343,22 @@ class SimGroup:
         if rc != 0:
             msgs = [m.decode() for m in [self._lib.rs_last_error(s._h) for s in self.sims] + [self._lib.rs_last_error(None)] if m]
             raise RuntimeError('rs_group_ppo_train failed (%d): %s' % (rc, '; '.join(dict.fromkeys(msgs))))
+
+    def fma2c_train(self, n_steps, policy, learner, table, rows, acts, rews, vals, dones, R_boot, T, t0, slot0, done_step=-1, policy_seed=0,
+                    ret=None, loss_out=None):
+        """rs_group_fma2c_train: n_steps iterations of the --device-update loop of tools/fma2c_train.py (act into the segment's slot,
+        step, reward and recorder; at a full segment or the episode's end the bootstrap value and the A2C update), all on the legacy
+        default stream, enqueued by one call.  A group of ONE handle.  policy / learner: the library handles (FusedFMA2C.handle, the
+        FusedA2CLearner's); table: an Fma2cRewardTable; the others: device pointers of the learner's segment; the position (t0,
+        slot0) BEFORE the call.  Nothing is advanced on the Python side: agents/train_fused.py: DeviceA2CTrainer does that."""
+        if not hasattr(self._lib, 'rs_group_fma2c_train'):
+            raise RuntimeError('the loaded library has no rs_group_fma2c_train: rebuild it (there is no CPU fallback)')
+        t = Fma2cTrainStruct(policy, learner, table.struct if hasattr(table, 'struct') else table, rows, acts, rews, vals, dones, R_boot, ret,
+                             loss_out, int(t0), int(T), int(slot0), int(done_step), int(policy_seed) & 0xFFFFFFFF)
+        rc = self._lib.rs_group_fma2c_train(self._hs, len(self.sims), C.byref(t), int(n_steps))
+        if rc != 0:
+            msgs = [m.decode() for m in [self._lib.rs_last_error(s._h) for s in self.sims] + [self._lib.rs_last_error(None)] if m]
+            raise RuntimeError('rs_group_fma2c_train failed (%d): %s' % (rc, '; '.join(dict.fromkeys(msgs))))
 
     def sync(self):
         for s in self.sims:
@@ -497,6 +541,18 @@ class BatchedSim:
 
     def sync(self):
         self._check(self._lib.rs_sync(self._h))
+
+    def fma2c_record(self, policy, table, rew_out, acts_out=None, ret_acc=None, stream=None):
+        """rs_fma2c_record: the FMA2C rewards of all agents (RAW) into rew_out f32 [N, K]; acts_out int32 [N, K] = the managers' and
+        the workers' actions of the step; ret_acc f32 [N, K] += the reward.  policy: an rs_policy_handle (FusedFMA2C.handle); table:
+        an Fma2cRewardTable (or None, which the library refuses); the others: device tensors or None."""
+        if not hasattr(self._lib, 'rs_fma2c_record'):
+            raise RuntimeError('the loaded library has no rs_fma2c_record: rebuild it (there is no CPU fallback)')
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        tab = C.byref(table.struct) if hasattr(table, 'struct') else (C.byref(table) if table is not None else None)
+        rc = self._lib.rs_fma2c_record(self._h, policy, tab, ptr(rew_out), ptr(acts_out), ptr(ret_acc), stream)
+        if rc != 0:
+            raise RuntimeError('rs_fma2c_record failed (%d): %s' % (rc, (self._lib.rs_last_error(self._h) or b'?').decode()))
 
     def act_random(self, step_key, stream=None):
         self._check(self._lib.rs_act_random(self._h, int(step_key) & 0xFFFFFFFF, stream))

@@ -5,10 +5,14 @@ for all agents (VecMultiSignal.fma2c_rewards) -> the A2C learner in PyTorch (res
 120 steps or at the episode's end) -> weights re-packed on the device.  The reference's FMA2C (agents/fma2c.py, agents/ma2c.py,
 config/agent_config.py:114-138) batched over N environments.
 
-    python tools/fma2c_train.py [--full] [--device-update] [--steps-per-episode n] [map] [n_envs] [episodes] [seed]
+    python tools/fma2c_train.py [--full] [--device-update [--device-rewards] | --device-loop] [--steps-per-episode n] [map] [n_envs] [episodes] [seed]
 
 --device-update: the fused A2C update (rs_fma2c_learn_*; resco_amd/agents/fma2c_learn_fused.py: FusedA2CLearner) instead of the PyTorch
 learner: rows and values land in the learner's segment buffers, the policy acts with the learner's own weight vector (no re-pack).
+--device-rewards (with --device-update): the rewards come from the reward kernel (rs_fma2c_record; VecMultiSignal.fma2c_rewards_device)
+instead of the dense product of fma2c_rewards; the summation order differs, so the figures differ in the last bits.
+--device-loop: the whole loop in the library, one call per episode (rs_group_fma2c_train; resco_amd/agents/train_fused.py:
+DeviceA2CTrainer): the same bits as --device-update --device-rewards, and the same JSON lines.
 
 Prints one JSON line per episode (mean episode return per agent, average trip delay as utils/readXML.py computes it, the last
 update's mean loss, env-steps/s including learning) and a final line with the best training episode and the on-device random policy
@@ -32,8 +36,13 @@ def delay(env):
     return float(env.sim.trip_delay().mean()), float(env.sim.stats()['arrived'].mean())
 
 
-def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_episode=0, quiet=False, keep=None, device_update=False):
+def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_episode=0, quiet=False, keep=None, device_update=False,
+         device_rewards=False, device_loop=False):
     """keep: a dict that receives net, policy, learner and env instead of having them closed (tests)"""
+    if device_loop:
+        device_update = True
+    elif device_rewards and not device_update:
+        raise ValueError('--device-rewards goes with --device-update')
     cfg = agent_configs['FMA2CFULL' if full else 'FMA2C']
     activate('FMA2CFull' if full else 'FMA2C', map_name)
     env = VecMultiSignal(map_name, n, states=(), rewards=(), seed=0, max_distance=cfg['max_distance'], outputs=('lane_agg', 'lane_arrivals'))
@@ -60,6 +69,12 @@ def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_
         env.step(None)
     rnd_delay, _ = delay(env)
 
+    trainer = None
+    if device_loop:
+        from resco_amd.agents.train_fused import DeviceA2CTrainer
+        trainer = DeviceA2CTrainer(env, learner, policy, full)
+        if steps != env.horizon_steps:
+            env.horizon_steps = steps       # (--steps-per-episode: the trainer reads the episode's end off the environment)
     rows, t = [], 0
     for ep in range(episodes):
         env.sim.set_seed(1000 + ep + 7919 * seed)
@@ -69,14 +84,24 @@ def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_
         loss = None
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for k in range(steps):
+        if trainer is not None:
+            trainer.ret.zero_()
+            updates = learner.updates
+            trainer.run(steps)              # (returns done: `steps` steps from a reset reach the horizon)
+            ret = trainer.ret
+            if learner.updates > updates:
+                loss = learner.last_loss
+        for k in range(steps if trainer is None else 0):
             out = policy.act(lane_agg, step_key=t, actions=actions, want=('value', 'rows'), out=learner.slot()) if device_update else \
                 policy.act(lane_agg, step_key=t, actions=actions)
             acts = torch.cat([macts, out['actions']], dim=1).long()
             env.step(None)
             done = k == steps - 1
-            r = env.fma2c_rewards(full)
-            rew = torch.stack([r[a] for a in layout.agents], dim=1)
+            if device_rewards:
+                rew = env.fma2c_rewards_device(full, policy=policy)
+            else:
+                r = env.fma2c_rewards(full)
+                rew = torch.stack([r[a] for a in layout.agents], dim=1)
             ret += rew
             res = learner.observe(out['rows'], acts, rew, out['value'], done, state, lambda: policy.value(lane_agg))
             if res is not None:
@@ -107,12 +132,12 @@ def main(map_name='cologne1', n=256, episodes=30, seed=0, full=False, steps_per_
 
 if __name__ == '__main__':
     a = sys.argv[1:]
-    full, dev_up = '--full' in a, '--device-update' in a
-    a = [x for x in a if x not in ('--full', '--device-update')]
+    full, dev_up, dev_rew, dev_loop = '--full' in a, '--device-update' in a, '--device-rewards' in a, '--device-loop' in a
+    a = [x for x in a if x not in ('--full', '--device-update', '--device-rewards', '--device-loop')]
     spe = 0
     if '--steps-per-episode' in a:
         i = a.index('--steps-per-episode')
         spe = int(a[i + 1])
         del a[i:i + 2]
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 30,
-         int(a[3]) if len(a) > 3 else 0, full=full, steps_per_episode=spe, device_update=dev_up)
+         int(a[3]) if len(a) > 3 else 0, full=full, steps_per_episode=spe, device_update=dev_up, device_rewards=dev_rew, device_loop=dev_loop)
