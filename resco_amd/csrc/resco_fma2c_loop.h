@@ -74,11 +74,9 @@ GT_HD void fl_record(const FlRec &R, int64_t i0, int64_t stride) {
 }
 
 // ------------------------------------------------------------------------------------------------ the done words
-// done[j] = (j == hit) for j < m: the post-step dones of the slots a call fills from one slot on to the next update, in one launch
-// (the learner's dones are int32 [T + 1]: resco_fma2c_train.h); hit outside 0 .. m - 1: none of them
-GT_HD void fl_done(int32_t *done, int32_t m, int32_t hit, int i0, int stride) {
-    for (int j = i0; j < m; j += stride) done[j] = (int32_t)(j == hit);
-}
+// gt_done of resco_group_train.h over the learner's int32 dones [T + 1] (resco_fma2c_train.h): the post-step dones of the slots a call
+// fills from one slot on to the next update, under the name the host build of the tests calls (tests/fma2c_loop_host)
+GT_HD void fl_done(int32_t *done, int32_t m, int32_t hit, int i0, int stride) { gt_done(done, m, hit, i0, stride); }
 
 // ------------------------------------------------------------------------------------------------ the state hand-over
 // After an update the acting state becomes the next segment's start state (states_bw <- states_fw); at an episode's end the start
@@ -113,9 +111,6 @@ GT_HD FlStep fl_plan(int32_t T, int32_t slot0, int64_t t0, int32_t done_step, in
 // one thread per (environment, agent): a few hundred loads out of cache-resident buffers, no LDS, no atomics, no workspace
 __global__ void __launch_bounds__(256) rs_fma2c_record_kernel(FlRec R) {
     fl_record(R, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256);
-}
-__global__ void __launch_bounds__(256) rs_fma2c_done_kernel(int32_t *done, int32_t m, int32_t hit) {
-    fl_done(done, m, hit, (int)(blockIdx.x * 256 + threadIdx.x), (int)(gridDim.x * 256));
 }
 // dones[0] = dones[n]: the post-step done of an update's last slot is the pre-step done of the next segment's first
 __global__ void rs_fma2c_done_carry_kernel(int32_t *dones, int32_t n) {

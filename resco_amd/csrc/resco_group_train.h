@@ -191,6 +191,14 @@ GT_HD void gt_sync_tensor(const GtSync &Y, int t, int i0, int stride) {
     for (int64_t i = nv * 4 + i0; i < n; i += stride) dst[i] = src[i];
 }
 
+// ------------------------------------------------------------------------------------------------ the done flags of a segment
+// done[j] = (j == hit) for j < m: the slots a segment loop (resco_ppo_loop.h: bytes; resco_fma2c_loop.h: the learner's int32 words)
+// fills from one slot on to the segment's or the call's end, in one launch; hit = the step at which the horizon is reached, counted
+// from the first of them (anything outside 0 .. m - 1: none of them).
+template <class E> GT_HD void gt_done(E *done, int32_t m, int32_t hit, int i0, int stride) {
+    for (int j = i0; j < m; j += stride) done[j] = (E)(j == hit);
+}
+
 // ------------------------------------------------------------------------------------------------ the bookkeeping of a step
 // Step k of a call that starts at agent step t0 with the ring at (head, count): what one iteration of the tools' --device-update
 // loops decides on the host.  The observation and the transition go into `slot`; afterwards the ring stands at (head, count), which
@@ -244,4 +252,8 @@ __global__ void __launch_bounds__(256) rs_ippo_pack_kernel(GtPackValue P) {
 }
 // grid (x, tensors)
 __global__ void __launch_bounds__(256) rs_sync_target_kernel(GtSync Y) { gt_sync_tensor(Y, (int)blockIdx.y, (int)(blockIdx.x * 256 + threadIdx.x), (int)(gridDim.x * 256)); }
+// E = uint8_t (rs_group_ppo_train) or int32_t (rs_group_fma2c_train)
+template <class E> __global__ void __launch_bounds__(256) rs_done_kernel(E *done, int32_t m, int32_t hit) {
+    gt_done(done, m, hit, (int)(blockIdx.x * 256 + threadIdx.x), (int)(gridDim.x * 256));
+}
 #endif

@@ -55,11 +55,8 @@ GP_DEV void gp_perm_row(uint32_t seed, uint32_t key, int32_t e, int32_t n, int32
 }
 
 // ------------------------------------------------------------------------------------------------ the done bytes
-// done[j] = (j == hit) for j < m: the slots a call fills from one slot on to the segment's or the call's end, in one launch; hit = the
-// step at which the horizon is reached, counted from the first of them (anything outside 0 .. m - 1: none of them).
-GT_HD void gp_done(uint8_t *done, int32_t m, int32_t hit, int i0, int stride) {
-    for (int j = i0; j < m; j += stride) done[j] = (uint8_t)(j == hit);
-}
+// gt_done of resco_group_train.h over bytes, under the name the host build of the tests calls (tests/ppo_loop_host)
+GT_HD void gp_done(uint8_t *done, int32_t m, int32_t hit, int i0, int stride) { gt_done(done, m, hit, i0, stride); }
 
 // ------------------------------------------------------------------------------------------------ the bookkeeping of a step
 // Step k of a call that starts at env-step t0 with slot0 slots of the segment filled and update0 updates finished: what one iteration
@@ -92,8 +89,5 @@ GT_HD GpStep gp_plan(const GpLoop &L, int32_t k) {
 // grid (x, epochs)
 __global__ void __launch_bounds__(256) rs_ppo_perm_kernel(uint32_t seed, uint32_t key, int32_t n, int32_t *perm) {
     gp_perm_row(seed, key, (int32_t)blockIdx.y, n, perm, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256);
-}
-__global__ void __launch_bounds__(256) rs_ppo_done_kernel(uint8_t *done, int32_t m, int32_t hit) {
-    gp_done(done, m, hit, (int)(blockIdx.x * 256 + threadIdx.x), (int)(gridDim.x * 256));
 }
 #endif

@@ -28,6 +28,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "resco_sim.h"
@@ -280,6 +281,14 @@ static thread_local std::string g_create_err;
             return RS_EHIP;                                                                        \
         }                                                                                          \
     } while (0)
+
+// what an entry point without a simulator handle ends with, once its arguments are checked: the device made current, the launches,
+// one read of the runtime's error
+template <class F> static int on_device(int device, F &&launch) {
+    if (hipSetDevice(device) != hipSuccess) return RS_EHIP;
+    launch();
+    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+}
 
 template <typename Tp>
 static int dev_alloc(rs_sim *h, Tp **p, size_t count, bool zero = true) {
@@ -864,9 +873,7 @@ extern "C" int rs_idqn_act(rs_policy_handle p, const void *obs, int32_t n_envs, 
                            const void *dyn, int32_t *actions, float *q, void *stream) {
     if (p && p->kind != POLICY_IDQN) g_create_err = "rs_idqn_act: the handle is not an rs_idqn_create policy";
     if (!p || p->kind != POLICY_IDQN || !obs || !actions || n_envs <= 0 || mode < 0 || mode > 1) return RS_EINVAL;
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    idqn_launch(p->W, obs, n_envs, env_base, mode, epsilon, seed, step_key, dyn, actions, q, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] { idqn_launch(p->W, obs, n_envs, env_base, mode, epsilon, seed, step_key, dyn, actions, q, (hipStream_t)stream); });
 }
 
 // ---- IPPO: the actor-critic launch of the same trunk (resco_policy.h: rs_ippo_forward_kernel)
@@ -880,9 +887,7 @@ extern "C" int rs_ippo_act(rs_policy_handle p, const void *obs, int32_t n_envs, 
                            const void *dyn, int32_t *actions, float *logp, float *value, float *logits, void *stream) {
     // actions and logp come together, or not at all (value-only: the bootstrap value of the state after a segment)
     if (!p || p->kind != POLICY_IDQN || !obs || !value || n_envs <= 0 || (actions == nullptr) != (logp == nullptr)) return RS_EINVAL;
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    ippo_launch(p->W, obs, n_envs, env_base, seed, step_key, dyn, actions, nullptr, logp, value, logits, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] { ippo_launch(p->W, obs, n_envs, env_base, seed, step_key, dyn, actions, nullptr, logp, value, logits, (hipStream_t)stream); });
 }
 
 // ---- PPO: GAE + per-signal standardisation (resco_ppo.h)
@@ -1025,16 +1030,12 @@ extern "C" int rs_ppo_grad(rs_ppo_handle p, const void *obs, const int32_t *act,
     if (!p) { g_create_err = "rs_ppo_grad: NULL handle"; return RS_EINVAL; }
     if (!obs || !act || !logp || !adv || !ret || !idx) { g_create_err = "rs_ppo_grad: a data pointer is NULL"; return RS_EINVAL; }
     if (B < 1 || B > p->max_batch) { g_create_err = "rs_ppo_grad: need 1 <= B <= max_minibatch of rs_ppo_create"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    ppo_grad_launch(p, PpoBatch{(const __half *)obs, act, logp, adv, ret, idx, B}, loss_out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] { ppo_grad_launch(p, PpoBatch{(const __half *)obs, act, logp, adv, ret, idx, B}, loss_out, (hipStream_t)stream); });
 }
 
 extern "C" int rs_ppo_step(rs_ppo_handle p, void *stream) {
     if (!p) { g_create_err = "rs_ppo_step: NULL handle"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    ppo_step_launch(p, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] { ppo_step_launch(p, (hipStream_t)stream); });
 }
 
 // the launches of a whole update: every epoch's minibatches of perm[e], the last of them short when minibatch does not divide n
@@ -1055,9 +1056,7 @@ extern "C" int rs_ppo_fit(rs_ppo_handle p, const void *obs, const int32_t *act, 
     if (n < 1 || epochs < 1 || minibatch < 1 || minibatch > p->max_batch) {
         g_create_err = "rs_ppo_fit: need 1 <= n, 1 <= epochs, 1 <= minibatch <= max_minibatch of rs_ppo_create"; return RS_EINVAL;
     }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    ppo_fit_launch(p, obs, act, logp, adv, ret, n, perm, epochs, minibatch, loss_out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] { ppo_fit_launch(p, obs, act, logp, adv, ret, n, perm, epochs, minibatch, loss_out, (hipStream_t)stream); });
 }
 
 // ---- the shuffle of an update (resco_ppo_loop.h): one launch, every element by its own thread
@@ -1074,13 +1073,21 @@ extern "C" int rs_ppo_perm(int32_t n, int32_t epochs, uint32_t seed, uint32_t up
 
 extern "C" int64_t rs_ppo_steps(rs_ppo_handle p) { return p ? (int64_t)p->t : -1; }
 
+// ---- The two DQN learners: what rs_dqn (IDQN) and rs_mplight_dqn (MPLight) share beside TrainHandle.  Each adds its table T and, as
+// overloads on its handle and ring type, what really differs: dqn_ring_refusal, dqn_batch, dqn_sample_launch / dqn_grad_launch /
+// dqn_step_launch and dqn_sync_launch.  The entry points of both are ONE implementation over those ("the DQN learners' entry points",
+// below the MPLight learner).
+struct DqnHandle : TrainHandle {
+    rs_dqn_config cfg{};
+    int32_t *idx = nullptr;     // the minibatch *_update draws: [max_batch][S][2] (IDQN), [max_batch][3] (MPLight)
+    const void *ring_ok[4] = {nullptr, nullptr, nullptr, nullptr};     // the ring arrays last found on this handle's device (dqn_check)
+};
+
 // ---- IDQN: the DQN update (resco_dqn_train.h), five tensor sets and the caller's ring; the library also owns the index array of
 // rs_dqn_update
-struct rs_dqn : TrainHandle {
+struct rs_dqn : DqnHandle {
+    static constexpr const char *kCreate = "rs_dqn_create";
     DqnTrainTab T{};
-    rs_dqn_config cfg{};
-    int32_t *idx = nullptr;     // [max_batch][S][2]: the minibatch rs_dqn_update draws
-    const void *ring_ok[4] = {nullptr, nullptr, nullptr, nullptr};     // the ring arrays last found on this handle's device (dqn_check)
 };
 
 extern "C" void rs_dqn_destroy(rs_dqn_handle p) { train_destroy(p); }
@@ -1103,29 +1110,13 @@ extern "C" int rs_dqn_create(int32_t device_id, int32_t n_signals, int32_t lmax,
     return RS_OK;
 }
 
-// what every call that reads the ring checks before it launches anything; `name` goes into the message
+// is ptr memory of `device`, as far as the runtime knows?
 static bool dqn_on_device(const void *ptr, int device) {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }     // (not memory the runtime knows)
     return at.device == device;
 }
-static int dqn_check(rs_dqn *p, const rs_dqn_ring *r, int32_t batch, const char *name) {
-    auto refuse = [&](const char *why) { g_create_err = std::string(name) + ": " + why; return RS_EINVAL; };
-    if (!p) return refuse("NULL handle");
-    if (!r || !r->obs || !r->act || !r->rew || !r->done) return refuse("a ring pointer is NULL");
-    if (batch < 1 || batch > p->max_batch) return refuse("need 1 <= batch <= max_batch of rs_dqn_create");
-    if (r->capacity < 2 || r->n_envs < 1) return refuse("the ring needs capacity >= 2 and n_envs >= 1");
-    if (r->count < 2) return refuse("the ring needs count >= 2: a transition is a slot and its written successor");
-    if (r->count > r->capacity || r->head < 0 || r->head >= r->capacity) return refuse("head or count outside the ring");
-    // where the four arrays live is asked of the runtime once per ring, not once per step: a ring keeps its storages
-    const void *ring[4] = {r->obs, r->act, r->rew, r->done};
-    if (memcmp(ring, p->ring_ok, sizeof(ring)) != 0) {
-        for (const void *a : ring)
-            if (!dqn_on_device(a, p->device)) return refuse("a ring array is not device memory of this handle's device (another device, or host memory)");
-        memcpy(p->ring_ok, ring, sizeof(ring));
-    }
-    return RS_OK;
-}
+static const char *dqn_ring_refusal(const rs_dqn *, const rs_dqn_ring *) { return nullptr; }      // (a ring of rs_dqn_ring has no sizes of its own to check)
 static DqnBatch dqn_batch(const rs_dqn_ring *r, const int32_t *idx, int32_t B) {
     return DqnBatch{(const __half *)r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, idx, B};
 }
@@ -1148,51 +1139,6 @@ static void dqn_step_launch(rs_dqn *p, hipStream_t st) {
     hipLaunchKernelGGL(dqn_adam_kernel, dim3(p->T.S, p->T.H + 1), dim3(PPT_T), 0, st, p->T, K);
     if (hipPeekAtLastError() == hipSuccess) p->t += 1;      // a step that could not be launched is not counted
 }
-
-extern "C" int rs_dqn_sample(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key, int32_t *idx_out, void *stream) {
-    if (int rc = dqn_check(p, ring, batch, "rs_dqn_sample")) return rc;
-    if (!idx_out) { g_create_err = "rs_dqn_sample: idx_out is NULL"; return RS_EINVAL; }
-    if (!dqn_on_device(idx_out, p->device)) { g_create_err = "rs_dqn_sample: idx_out is not device memory of this handle's device"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    dqn_sample_launch(p, ring, batch, seed, update_key, idx_out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
-}
-
-extern "C" int rs_dqn_grad(rs_dqn_handle p, const rs_dqn_ring *ring, const int32_t *idx, int32_t batch, float *loss_out, void *stream) {
-    if (int rc = dqn_check(p, ring, batch, "rs_dqn_grad")) return rc;
-    if (!idx) { g_create_err = "rs_dqn_grad: idx is NULL"; return RS_EINVAL; }
-    if (!dqn_on_device(idx, p->device)) { g_create_err = "rs_dqn_grad: idx is not device memory of this handle's device"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    dqn_grad_launch(p, dqn_batch(ring, idx, batch), loss_out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
-}
-
-extern "C" int rs_dqn_step(rs_dqn_handle p, void *stream) {
-    if (!p) { g_create_err = "rs_dqn_step: NULL handle"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    dqn_step_launch(p, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
-}
-
-// n_updates x [sample -> gradient -> Adam step] (rs_dqn_update, rs_group_train); the caller reads hipGetLastError
-static void dqn_update_launch(rs_dqn *p, const rs_dqn_ring *ring, int batch, uint32_t seed, int n_updates, float *loss_out, hipStream_t st) {
-    for (int j = 0; j < n_updates; ++j) {       // the launches of a stream run in order: update j + 1 may overwrite idx and the workspace
-        dqn_sample_launch(p, ring, batch, seed, (uint32_t)p->t, p->idx, st);
-        dqn_grad_launch(p, dqn_batch(ring, p->idx, batch), loss_out, st);
-        dqn_step_launch(p, st);
-        if (hipPeekAtLastError() != hipSuccess) break;      // nothing more is enqueued behind a launch that failed
-    }
-}
-
-extern "C" int rs_dqn_update(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out, void *stream) {
-    if (int rc = dqn_check(p, ring, batch, "rs_dqn_update")) return rc;
-    if (n_updates < 1) { g_create_err = "rs_dqn_update: need 1 <= n_updates"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    dqn_update_launch(p, ring, batch, seed, n_updates, loss_out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
-}
-
-extern "C" int64_t rs_dqn_steps(rs_dqn_handle p) { return p ? (int64_t)p->t : -1; }
 
 // ------------------------------------------------------------------------------------------------ fused MPLight (FRAP) policy
 static void mplight_launch(const FrapTab &F, const void *obs, int n_envs, int env_base, float eps, uint32_t seed, uint32_t step_key,
@@ -1250,9 +1196,7 @@ extern "C" int rs_mplight_act(rs_policy_handle p, const void *obs, int32_t n_env
                               const void *dyn, int32_t *actions, int32_t *pair_index, float *q, void *stream) {
     if (p && p->kind != POLICY_MPLIGHT) g_create_err = "rs_mplight_act: the handle is not an rs_mplight_create policy";
     if (!p || p->kind != POLICY_MPLIGHT || !obs || !actions || n_envs <= 0) return RS_EINVAL;
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    mplight_launch(p->F, obs, n_envs, env_base, epsilon, seed, step_key, dyn, actions, pair_index, q, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] { mplight_launch(p->F, obs, n_envs, env_base, epsilon, seed, step_key, dyn, actions, pair_index, q, (hipStream_t)stream); });
 }
 
 extern "C" int rs_mplight_set_device_weights(rs_policy_handle p, const float *weights) {
@@ -1364,27 +1308,25 @@ extern "C" int rs_fma2c_act(rs_policy_handle p, const float *lane_agg, int32_t n
     if (int rc = fma2c_check(p, n_envs, env_base, "rs_fma2c_act: the handle is not an rs_fma2c_create policy",
                              "rs_fma2c_act: need 1 <= n_envs, 0 <= env_base, env_base + n_envs <= max_envs")) return rc;
     if (!lane_agg) return fma2c_refuse("rs_fma2c_act: lane_agg is NULL");
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    fma2c_act_launch(p, lane_agg, n_envs, env_base, seed, step_key, dyn, Fma2cOut{actions, pi_out, value_out, rows_out}, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] {
+        fma2c_act_launch(p, lane_agg, n_envs, env_base, seed, step_key, dyn, Fma2cOut{actions, pi_out, value_out, rows_out}, (hipStream_t)stream);
+    });
 }
 
 extern "C" int rs_fma2c_value(rs_policy_handle p, const float *lane_agg, int32_t n_envs, int32_t env_base, float *value_out, void *stream) {
     if (int rc = fma2c_check(p, n_envs, env_base, "rs_fma2c_value: the handle is not an rs_fma2c_create policy",
                              "rs_fma2c_value: need 1 <= n_envs, 0 <= env_base, env_base + n_envs <= max_envs")) return rc;
     if (!lane_agg || !value_out) return fma2c_refuse("rs_fma2c_value: lane_agg or value_out is NULL");
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    fma2c_value_launch(p, lane_agg, n_envs, env_base, value_out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] { fma2c_value_launch(p, lane_agg, n_envs, env_base, value_out, (hipStream_t)stream); });
 }
 
 extern "C" int rs_fma2c_reset(rs_policy_handle p, int32_t env_base, int32_t n_envs, int32_t clear_fingerprints, void *stream) {
     if (int rc = fma2c_check(p, n_envs, env_base, "rs_fma2c_reset: the handle is not an rs_fma2c_create policy",
                              "rs_fma2c_reset: need 1 <= n_envs, 0 <= env_base, env_base + n_envs <= max_envs")) return rc;
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
     const size_t n = (size_t)n_envs * p->A.K * 4 * FM_L;
-    hipLaunchKernelGGL(rs_fma2c_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->A, env_base, n_envs, clear_fingerprints ? 1 : 0);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] {
+        hipLaunchKernelGGL(rs_fma2c_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->A, env_base, n_envs, clear_fingerprints ? 1 : 0);
+    });
 }
 
 extern "C" int rs_fma2c_set_device_weights(rs_policy_handle p, const float *weights) {
@@ -1566,11 +1508,9 @@ extern "C" int rs_fma2c_learn_buffer(rs_fma2c_learn_handle l, int32_t which, voi
 
 // ---- MPLight: the shared-DQN update (resco_frap_train.h), five flat vectors and the caller's ring; the library owns the per-tile
 // partials, the pair table and the index array of rs_mplight_dqn_update
-struct rs_mplight_dqn : TrainHandle {
+struct rs_mplight_dqn : DqnHandle {
+    static constexpr const char *kCreate = "rs_mplight_dqn_create";
     FrapTrainTab T{};
-    rs_dqn_config cfg{};
-    int32_t *idx = nullptr;     // [max_batch][3]: the minibatch rs_mplight_dqn_update draws
-    const void *ring_ok[4] = {nullptr, nullptr, nullptr, nullptr};     // the ring arrays last found on this handle's device
 };
 
 extern "C" void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p) { train_destroy(p); }
@@ -1613,18 +1553,68 @@ extern "C" int rs_mplight_dqn_create(int32_t device_id, int32_t demand_shape, in
     return RS_OK;
 }
 
-// what every call that reads the ring checks before it launches anything; `name` goes into the message
-static int mplight_dqn_check(rs_mplight_dqn *p, const rs_mplight_ring *r, int32_t batch, const char *name) {
-    auto refuse = [&](const char *why) { g_create_err = std::string(name) + ": " + why; return RS_EINVAL; };
+// the sizes an rs_mplight_ring carries beside the common ones (dqn_check)
+static const char *dqn_ring_refusal(const rs_mplight_dqn *p, const rs_mplight_ring *r) {
+    if (r->n_signals != p->T.S) return "the ring's n_signals is not the handle's";
+    if (r->width != 1 + FRAP_MV * p->T.D) return "the ring's width is not the handle's 1 + 12 demand_shape";
+    return nullptr;
+}
+static FrapBatch dqn_batch(const rs_mplight_ring *r, const int32_t *idx, int32_t B) {
+    return FrapBatch{r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, r->n_signals, r->width, idx, B};
+}
+
+// the launches; the arguments have been checked
+static void dqn_sample_launch(const rs_mplight_dqn *, const rs_mplight_ring *r, int B, uint32_t seed, uint32_t key, int32_t *idx, hipStream_t st) {
+    hipLaunchKernelGGL(frap_dqn_sample_kernel, dim3((B + 255) / 256), dim3(256), 0, st, seed, key, r->capacity, r->n_envs, r->n_signals, r->head, r->count, B,
+                       idx);
+}
+static void dqn_grad_launch(const rs_mplight_dqn *p, const FrapBatch &D, float *loss_out, hipStream_t st) {
+    const FrapTrainTab &T = p->T;
+    hipLaunchKernelGGL(frap_dqn_tile_kernel, dim3((D.B + FPT_TM - 1) / FPT_TM), dim3(FPT_T), 0, st, T, D);
+    hipLaunchKernelGGL(frap_dqn_reduce_kernel, dim3((T.n + 255) / 256), dim3(256), 0, st, T, D.B, loss_out);
+}
+static void dqn_step_launch(rs_mplight_dqn *p, hipStream_t st) {
+    const PpoStepConsts K = ppo_step_consts(p->cfg.lr, p->cfg.adam_eps, p->cfg.beta1, p->cfg.beta2, 0.0, p->t + 1);
+    hipLaunchKernelGGL(frap_dqn_adam_kernel, dim3((p->T.n + 255) / 256), dim3(256), 0, st, p->T, K);
+    if (hipPeekAtLastError() == hipSuccess) p->t += 1;      // a step that could not be launched is not counted
+}
+
+// target <- params (resco_group_train.h): one launch, the sources, destinations and element counts listed per learner
+static void sync_launch(const GtSync &Y, hipStream_t st) {
+    int64_t most = 1;
+    for (int i = 0; i < Y.count; ++i) most = Y.n[i] > most ? Y.n[i] : most;
+    const int64_t blocks = (most / 4 + 255) / 256 + 1;
+    hipLaunchKernelGGL(rs_sync_target_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024), Y.count), dim3(256), 0, st, Y);
+}
+// the element counts of a BatchedIDQN's eight tensors, in rs_dqn_tensors order
+static void dqn_sync_launch(const rs_dqn *p, hipStream_t st) {
+    const DqnTrainTab &T = p->T;
+    const int64_t S = T.S, n[8] = {S * 256, S * 64, S * 64 * T.H * 4 * 64, S * 64, S * 4096, S * 64, S * 64 * T.amax, S * T.amax};
+    GtSync Y{};
+    Y.count = 8;
+    for (int i = 0; i < 8; ++i) { Y.src[i] = T.par.p[i]; Y.dst[i] = T.tgt.p[i]; Y.n[i] = n[i]; }
+    sync_launch(Y, st);
+}
+static void dqn_sync_launch(const rs_mplight_dqn *p, hipStream_t st) {
+    GtSync Y{};
+    Y.count = 1; Y.src[0] = p->T.par; Y.dst[0] = (float *)p->T.tgt; Y.n[0] = p->T.n;      // (the writable alias of the vector the create call took as const)
+    sync_launch(Y, st);
+}
+
+// ---- the DQN learners' entry points: one implementation for H = rs_dqn with Ring = rs_dqn_ring and H = rs_mplight_dqn with
+// Ring = rs_mplight_ring; `name`: the entry point, for the message
+// what every call that reads the ring checks before it launches anything
+template <class H, class Ring> static int dqn_check(H *p, const Ring *r, int32_t batch, const char *name) {
+    auto refuse = [&](const std::string &why) { g_create_err = std::string(name) + ": " + why; return RS_EINVAL; };
     if (!p) return refuse("NULL handle");
     if (!r || !r->obs || !r->act || !r->rew || !r->done) return refuse("a ring pointer is NULL");
-    if (batch < 1 || batch > p->max_batch) return refuse("need 1 <= batch <= max_batch of rs_mplight_dqn_create");
+    if (batch < 1 || batch > p->max_batch) return refuse(std::string("need 1 <= batch <= max_batch of ") + H::kCreate);
     if (r->capacity < 2 || r->n_envs < 1) return refuse("the ring needs capacity >= 2 and n_envs >= 1");
-    if (r->n_signals != p->T.S) return refuse("the ring's n_signals is not the handle's");
-    if (r->width != 1 + FRAP_MV * p->T.D) return refuse("the ring's width is not the handle's 1 + 12 demand_shape");
+    if (const char *why = dqn_ring_refusal(p, r)) return refuse(why);
     if (r->count < 2) return refuse("the ring needs count >= 2: a transition is a slot and its written successor");
     if (r->count > r->capacity || r->head < 0 || r->head >= r->capacity) return refuse("head or count outside the ring");
-    const void *ring[4] = {r->obs, r->act, r->rew, r->done};      // asked of the runtime once per ring: a ring keeps its storages
+    // where the four arrays live is asked of the runtime once per ring, not once per step: a ring keeps its storages
+    const void *ring[4] = {r->obs, r->act, r->rew, r->done};
     if (memcmp(ring, p->ring_ok, sizeof(ring)) != 0) {
         for (const void *a : ring)
             if (!dqn_on_device(a, p->device)) return refuse("a ring array is not device memory of this handle's device (another device, or host memory)");
@@ -1632,72 +1622,108 @@ static int mplight_dqn_check(rs_mplight_dqn *p, const rs_mplight_ring *r, int32_
     }
     return RS_OK;
 }
-static FrapBatch mplight_dqn_batch(const rs_mplight_ring *r, const int32_t *idx, int32_t B) {
-    return FrapBatch{r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, r->n_signals, r->width, idx, B};
+// ... and every call that takes an index array of the caller's
+template <class H> static int dqn_check_idx(const H *p, const void *idx, const char *what, const char *name) {
+    if (idx && dqn_on_device(idx, p->device)) return RS_OK;
+    g_create_err = std::string(name) + ": " + what + (idx ? " is not device memory of this handle's device" : " is NULL");
+    return RS_EINVAL;
 }
-
-// the launches; the arguments have been checked
-static void mplight_dqn_sample_launch(const rs_mplight_ring *r, int B, uint32_t seed, uint32_t key, int32_t *idx, hipStream_t st) {
-    hipLaunchKernelGGL(frap_dqn_sample_kernel, dim3((B + 255) / 256), dim3(256), 0, st, seed, key, r->capacity, r->n_envs, r->n_signals, r->head, r->count, B,
-                       idx);
-}
-static void mplight_dqn_grad_launch(const rs_mplight_dqn *p, const FrapBatch &D, float *loss_out, hipStream_t st) {
-    const FrapTrainTab &T = p->T;
-    hipLaunchKernelGGL(frap_dqn_tile_kernel, dim3((D.B + FPT_TM - 1) / FPT_TM), dim3(FPT_T), 0, st, T, D);
-    hipLaunchKernelGGL(frap_dqn_reduce_kernel, dim3((T.n + 255) / 256), dim3(256), 0, st, T, D.B, loss_out);
-}
-static void mplight_dqn_step_launch(rs_mplight_dqn *p, hipStream_t st) {
-    const PpoStepConsts K = ppo_step_consts(p->cfg.lr, p->cfg.adam_eps, p->cfg.beta1, p->cfg.beta2, 0.0, p->t + 1);
-    hipLaunchKernelGGL(frap_dqn_adam_kernel, dim3((p->T.n + 255) / 256), dim3(256), 0, st, p->T, K);
-    if (hipPeekAtLastError() == hipSuccess) p->t += 1;      // a step that could not be launched is not counted
-}
-
-extern "C" int rs_mplight_dqn_sample(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key,
-                                     int32_t *idx_out, void *stream) {
-    if (int rc = mplight_dqn_check(p, ring, batch, "rs_mplight_dqn_sample")) return rc;
-    if (!idx_out) { g_create_err = "rs_mplight_dqn_sample: idx_out is NULL"; return RS_EINVAL; }
-    if (!dqn_on_device(idx_out, p->device)) { g_create_err = "rs_mplight_dqn_sample: idx_out is not device memory of this handle's device"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    mplight_dqn_sample_launch(ring, batch, seed, update_key, idx_out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
-}
-
-extern "C" int rs_mplight_dqn_grad(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, const int32_t *idx, int32_t batch, float *loss_out, void *stream) {
-    if (int rc = mplight_dqn_check(p, ring, batch, "rs_mplight_dqn_grad")) return rc;
-    if (!idx) { g_create_err = "rs_mplight_dqn_grad: idx is NULL"; return RS_EINVAL; }
-    if (!dqn_on_device(idx, p->device)) { g_create_err = "rs_mplight_dqn_grad: idx is not device memory of this handle's device"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    mplight_dqn_grad_launch(p, mplight_dqn_batch(ring, idx, batch), loss_out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
-}
-
-extern "C" int rs_mplight_dqn_step(rs_mplight_dqn_handle p, void *stream) {
-    if (!p) { g_create_err = "rs_mplight_dqn_step: NULL handle"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    mplight_dqn_step_launch(p, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
-}
-
-// n_updates x [sample -> gradient -> Adam step] (rs_mplight_dqn_update, rs_group_train); the caller reads hipGetLastError
-static void mplight_dqn_update_launch(rs_mplight_dqn *p, const rs_mplight_ring *ring, int batch, uint32_t seed, int n_updates, float *loss_out, hipStream_t st) {
+// n_updates x [sample -> gradient -> Adam step] (*_update, rs_group_train); the caller reads hipGetLastError
+template <class H, class Ring> static void dqn_update_launch(H *p, const Ring *ring, int batch, uint32_t seed, int n_updates, float *loss_out, hipStream_t st) {
     for (int j = 0; j < n_updates; ++j) {       // the launches of a stream run in order: update j + 1 may overwrite idx and the workspace
-        mplight_dqn_sample_launch(ring, batch, seed, (uint32_t)p->t, p->idx, st);
-        mplight_dqn_grad_launch(p, mplight_dqn_batch(ring, p->idx, batch), loss_out, st);
-        mplight_dqn_step_launch(p, st);
+        dqn_sample_launch(p, ring, batch, seed, (uint32_t)p->t, p->idx, st);
+        dqn_grad_launch(p, dqn_batch(ring, p->idx, batch), loss_out, st);
+        dqn_step_launch(p, st);
         if (hipPeekAtLastError() != hipSuccess) break;      // nothing more is enqueued behind a launch that failed
     }
 }
-
-extern "C" int rs_mplight_dqn_update(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out,
-                                     void *stream) {
-    if (int rc = mplight_dqn_check(p, ring, batch, "rs_mplight_dqn_update")) return rc;
-    if (n_updates < 1) { g_create_err = "rs_mplight_dqn_update: need 1 <= n_updates"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    mplight_dqn_update_launch(p, ring, batch, seed, n_updates, loss_out, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+template <class H, class Ring>
+static int dqn_sample(const char *name, H *p, const Ring *ring, int32_t batch, uint32_t seed, uint32_t update_key, int32_t *idx_out, void *stream) {
+    if (int rc = dqn_check(p, ring, batch, name)) return rc;
+    if (int rc = dqn_check_idx(p, idx_out, "idx_out", name)) return rc;
+    return on_device(p->device, [&] { dqn_sample_launch(p, ring, batch, seed, update_key, idx_out, (hipStream_t)stream); });
+}
+template <class H, class Ring> static int dqn_grad(const char *name, H *p, const Ring *ring, const int32_t *idx, int32_t batch, float *loss_out, void *stream) {
+    if (int rc = dqn_check(p, ring, batch, name)) return rc;
+    if (int rc = dqn_check_idx(p, idx, "idx", name)) return rc;
+    return on_device(p->device, [&] { dqn_grad_launch(p, dqn_batch(ring, idx, batch), loss_out, (hipStream_t)stream); });
+}
+template <class H, class Ring>
+static int dqn_update(const char *name, H *p, const Ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out, void *stream) {
+    if (int rc = dqn_check(p, ring, batch, name)) return rc;
+    if (n_updates < 1) { g_create_err = std::string(name) + ": need 1 <= n_updates"; return RS_EINVAL; }
+    return on_device(p->device, [&] { dqn_update_launch(p, ring, batch, seed, n_updates, loss_out, (hipStream_t)stream); });
+}
+template <class H> static int dqn_step(const char *name, H *p, void *stream) {
+    if (!p) { g_create_err = std::string(name) + ": NULL handle"; return RS_EINVAL; }
+    return on_device(p->device, [&] { dqn_step_launch(p, (hipStream_t)stream); });
+}
+template <class H> static int dqn_sync_target(const char *name, H *p, void *stream) {
+    if (!p) { g_create_err = std::string(name) + ": NULL handle"; return RS_EINVAL; }
+    return on_device(p->device, [&] { dqn_sync_launch(p, (hipStream_t)stream); });
 }
 
+extern "C" int rs_dqn_sample(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key, int32_t *idx_out, void *stream) {
+    return dqn_sample("rs_dqn_sample", p, ring, batch, seed, update_key, idx_out, stream);
+}
+extern "C" int rs_dqn_grad(rs_dqn_handle p, const rs_dqn_ring *ring, const int32_t *idx, int32_t batch, float *loss_out, void *stream) {
+    return dqn_grad("rs_dqn_grad", p, ring, idx, batch, loss_out, stream);
+}
+extern "C" int rs_dqn_step(rs_dqn_handle p, void *stream) { return dqn_step("rs_dqn_step", p, stream); }
+extern "C" int rs_dqn_update(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out, void *stream) {
+    return dqn_update("rs_dqn_update", p, ring, batch, seed, n_updates, loss_out, stream);
+}
+extern "C" int rs_dqn_sync_target(rs_dqn_handle p, void *stream) { return dqn_sync_target("rs_dqn_sync_target", p, stream); }
+extern "C" int64_t rs_dqn_steps(rs_dqn_handle p) { return p ? (int64_t)p->t : -1; }
+
+extern "C" int rs_mplight_dqn_sample(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key,
+                                     int32_t *idx_out, void *stream) {
+    return dqn_sample("rs_mplight_dqn_sample", p, ring, batch, seed, update_key, idx_out, stream);
+}
+extern "C" int rs_mplight_dqn_grad(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, const int32_t *idx, int32_t batch, float *loss_out, void *stream) {
+    return dqn_grad("rs_mplight_dqn_grad", p, ring, idx, batch, loss_out, stream);
+}
+extern "C" int rs_mplight_dqn_step(rs_mplight_dqn_handle p, void *stream) { return dqn_step("rs_mplight_dqn_step", p, stream); }
+extern "C" int rs_mplight_dqn_update(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out,
+                                     void *stream) {
+    return dqn_update("rs_mplight_dqn_update", p, ring, batch, seed, n_updates, loss_out, stream);
+}
+extern "C" int rs_mplight_dqn_sync_target(rs_mplight_dqn_handle p, void *stream) { return dqn_sync_target("rs_mplight_dqn_sync_target", p, stream); }
 extern "C" int64_t rs_mplight_dqn_steps(rs_mplight_dqn_handle p) { return p ? (int64_t)p->t : -1; }
+
+// ---- "does this policy fit this handle?" and "may this handle take part in a loop?": asked by rs_group_step, rs_group_rollout, the
+// three training loops and rs_fma2c_record.  Each returns NULL or the reason; the caller puts its own name in front.
+// The observation buffer the policy kernel of agent `kind` reads on handle h: where it is, its bit of out_mask, and what a caller
+// hears when rs_set_outputs has switched it off (stale rows, or zeros if it was never written).  p has been found to be of that kind.
+struct AgentObs { const void *ptr; uint32_t bit; const char *off; };
+static AgentObs agent_obs(const rs_sim *h, const rs_policy *p, int kind) {
+    if (kind == RS_AGENT_FMA2C) return {h->O.lane_agg(), OUT_LANE_AGG, "the agent reads RS_BUF_LANE_AGG, which rs_set_outputs has switched off"};
+    if (kind != RS_AGENT_MPLIGHT) return {h->O.drq_f16(), OUT_DRQ_F16, "the agent reads RS_BUF_DRQ_NORM_F16, which rs_set_outputs has switched off"};
+    if (p->F.D == 1) return {h->O.mplight(), OUT_MPLIGHT, "the agent reads RS_BUF_MPLIGHT, which rs_set_outputs has switched off"};
+    return {h->O.mplight_full(), OUT_MPLIGHT_FULL, "the agent reads RS_BUF_MPLIGHT_FULL, which rs_set_outputs has switched off"};
+}
+// kind: RS_AGENT_IDQN, RS_AGENT_IPPO (both act on an rs_idqn_create policy), RS_AGENT_MPLIGHT or RS_AGENT_FMA2C
+static const char *policy_fit_refusal(const rs_sim *h, const rs_policy *p, int kind) {
+    if (!p) return "the policy handle is NULL";
+    if (kind == RS_AGENT_FMA2C) {
+        if (p->kind != POLICY_FMA2C) return "the policy is not an rs_fma2c_create policy";
+        if (p->A.S != h->K.n_signals || p->A.O != h->K.n_obs) return "needs a policy built for this scenario (n_signals, n_obs)";
+        if (h->P.env_base < 0 || (int64_t)h->P.env_base + h->n_envs > p->A.max_envs) return "env_base + n_envs of the handle exceeds the policy's max_envs";
+    } else if (kind == RS_AGENT_MPLIGHT) {
+        if (p->kind != POLICY_MPLIGHT || p->F.S != h->K.n_signals) return "needs an rs_mplight_create policy built for this scenario (n_signals)";
+    } else if (p->kind != POLICY_IDQN || p->W.S != h->K.n_signals || p->W.lmax != h->K.lmax)
+        return "needs an rs_idqn_create policy built for this scenario (n_signals, lmax)";
+    if (p->device != h->device) return "the policy's weights live on another device than this handle";
+    const AgentObs obs = agent_obs(h, p, kind);
+    return (h->out_mask & obs.bit) ? nullptr : obs.off;
+}
+// The training loops put launches on the legacy stream and create no event or wait: only a blocking stream is ordered with it.
+static const char *loop_handle_refusal(const rs_sim *h) {
+    if (!h->blocking) return "this handle's stream is a non-blocking stream (RESCO_PLAIN_STREAMS, or hipExtStreamCreateWithCUMask failed at rs_create): "
+                             "nothing would order its launches with the loop's on the legacy stream";
+    if (h->timing) return "rs_timing is enabled on this handle: its events are not part of this loop";
+    return nullptr;
+}
 
 // ---- one env-step (or n of them) of a whole group of handles in ONE call (include/resco_sim.h: rs_group_step)
 extern "C" int rs_group_step(const rs_handle *hs, int32_t n_handles, const rs_group_agent *agent, int32_t n_steps) {
@@ -1709,30 +1735,11 @@ extern "C" int rs_group_step(const rs_handle *hs, int32_t n_handles, const rs_gr
         if (kind == RS_AGENT_MAXWAVE || kind == RS_AGENT_MAXPRESSURE) {
             if (!h->pairs) { h->err = "rs_group_step: the MAXWAVE / MAXPRESSURE tables are installed by a first rs_act_maxwave call"; return RS_EINVAL; }
             if (!(h->out_mask & (kind == RS_AGENT_MAXPRESSURE ? OUT_MPLIGHT : OUT_WAVE))) { h->err = "rs_group_step: the agent's input buffer is switched off (rs_set_outputs)"; return RS_EINVAL; }
-        } else if (kind == RS_AGENT_IDQN) {
-            if (!agent->policy || agent->policy->kind != POLICY_IDQN || agent->mode < 0 || agent->mode > 1 || agent->policy->W.S != h->K.n_signals || agent->policy->W.lmax != h->K.lmax) {
-                h->err = "rs_group_step: RS_AGENT_IDQN needs a policy built for this scenario (n_signals, lmax)"; return RS_EINVAL; }
-            if (agent->policy->device != h->device) { h->err = "rs_group_step: the policy's weights live on another device than this handle"; return RS_EINVAL; }
-            if (!(h->out_mask & OUT_DRQ_F16)) { h->err = "rs_group_step: RS_AGENT_IDQN reads RS_BUF_DRQ_NORM_F16, which rs_set_outputs has switched off"; return RS_EINVAL; }
-        } else if (kind == RS_AGENT_MPLIGHT) {
-            if (!agent->policy || agent->policy->kind != POLICY_MPLIGHT || agent->policy->F.S != h->K.n_signals) {
-                h->err = "rs_group_step: RS_AGENT_MPLIGHT needs an rs_mplight_create policy built for this scenario (n_signals)"; return RS_EINVAL; }
-            if (agent->mode != 0) { h->err = "rs_group_step: RS_AGENT_MPLIGHT has only mode 0 (epsilon-greedy)"; return RS_EINVAL; }
-            if (agent->policy->device != h->device) { h->err = "rs_group_step: the policy's weights live on another device than this handle"; return RS_EINVAL; }
-            if (!(h->out_mask & (agent->policy->F.D == 1 ? OUT_MPLIGHT : OUT_MPLIGHT_FULL))) {
-                h->err = agent->policy->F.D == 1 ? "rs_group_step: RS_AGENT_MPLIGHT reads RS_BUF_MPLIGHT, which rs_set_outputs has switched off"
-                                                 : "rs_group_step: RS_AGENT_MPLIGHT reads RS_BUF_MPLIGHT_FULL, which rs_set_outputs has switched off";
-                return RS_EINVAL;
-            }
-        } else if (kind == RS_AGENT_FMA2C) {
-            const rs_policy *pol = agent->policy;
-            if (!pol || pol->kind != POLICY_FMA2C) { h->err = "rs_group_step: RS_AGENT_FMA2C needs an rs_fma2c_create policy"; return RS_EINVAL; }
-            if (pol->A.S != h->K.n_signals || pol->A.O != h->K.n_obs) {
-                h->err = "rs_group_step: RS_AGENT_FMA2C needs a policy built for this scenario (n_signals, n_obs)"; return RS_EINVAL; }
-            if (pol->device != h->device) { h->err = "rs_group_step: the policy's weights live on another device than this handle"; return RS_EINVAL; }
-            if (h->P.env_base < 0 || (int64_t)h->P.env_base + h->n_envs > pol->A.max_envs) {
-                h->err = "rs_group_step: RS_AGENT_FMA2C: env_base + n_envs of the handle exceeds the policy's max_envs"; return RS_EINVAL; }
-            if (!(h->out_mask & OUT_LANE_AGG)) { h->err = "rs_group_step: RS_AGENT_FMA2C reads RS_BUF_LANE_AGG, which rs_set_outputs has switched off"; return RS_EINVAL; }
+        } else if (kind == RS_AGENT_IDQN || kind == RS_AGENT_MPLIGHT || kind == RS_AGENT_FMA2C) {
+            const char *why = policy_fit_refusal(h, agent->policy, kind);
+            if (!why && kind == RS_AGENT_IDQN && (agent->mode < 0 || agent->mode > 1)) why = "RS_AGENT_IDQN has modes 0 (epsilon-greedy) and 1 (softmax sampling)";
+            if (!why && kind == RS_AGENT_MPLIGHT && agent->mode != 0) why = "RS_AGENT_MPLIGHT has only mode 0 (epsilon-greedy)";
+            if (why) { h->err = std::string("rs_group_step: ") + why; return RS_EINVAL; }
         } else if (kind != RS_AGENT_NONE && kind != RS_AGENT_RANDOM) { h->err = "rs_group_step: unknown agent kind"; return RS_EINVAL; }
     }
     for (int k = 0; k < n_steps; ++k)
@@ -1743,16 +1750,16 @@ extern "C" int rs_group_step(const rs_handle *hs, int32_t n_handles, const rs_gr
             const uint32_t key = agent ? agent->step_key + (uint32_t)k : 0u;
             float eps = agent ? agent->epsilon + (float)k * agent->epsilon_step : 0.0f;
             if (eps < 0.0f) eps = 0.0f;
+            const bool fused = kind == RS_AGENT_IDQN || kind == RS_AGENT_MPLIGHT || kind == RS_AGENT_FMA2C;
+            const void *obs = fused ? agent_obs(h, agent->policy, kind).ptr : nullptr;
             if (kind == RS_AGENT_RANDOM) launch_random(h, st, key);
             else if (kind == RS_AGENT_MAXWAVE || kind == RS_AGENT_MAXPRESSURE) launch_maxwave(h, st, kind == RS_AGENT_MAXPRESSURE);
             else if (kind == RS_AGENT_IDQN)
-                idqn_launch(agent->policy->W, h->O.drq_f16(), h->n_envs, h->P.env_base, agent->mode, eps, agent->seed, key, nullptr, h->actions, nullptr, st);
-            else if (kind == RS_AGENT_MPLIGHT) {
-                const FrapTab &F = agent->policy->F;
-                const void *obs = F.D == 1 ? (const void *)h->O.mplight() : (const void *)h->O.mplight_full();
-                mplight_launch(F, obs, h->n_envs, h->P.env_base, eps, agent->seed, key, nullptr, h->actions, nullptr, nullptr, st);
-            } else if (kind == RS_AGENT_FMA2C)
-                fma2c_act_launch(agent->policy, h->O.lane_agg(), h->n_envs, h->P.env_base, agent->seed, key, nullptr, Fma2cOut{h->actions, nullptr, nullptr, nullptr}, st);
+                idqn_launch(agent->policy->W, obs, h->n_envs, h->P.env_base, agent->mode, eps, agent->seed, key, nullptr, h->actions, nullptr, st);
+            else if (kind == RS_AGENT_MPLIGHT)
+                mplight_launch(agent->policy->F, obs, h->n_envs, h->P.env_base, eps, agent->seed, key, nullptr, h->actions, nullptr, nullptr, st);
+            else if (kind == RS_AGENT_FMA2C)
+                fma2c_act_launch(agent->policy, (const float *)obs, h->n_envs, h->P.env_base, agent->seed, key, nullptr, Fma2cOut{h->actions, nullptr, nullptr, nullptr}, st);
             if (kind != RS_AGENT_NONE) HIPCHK(h, hipGetLastError());
             const int rc = launch_step(h, st, h->K.step_length * h->ratio, 1);
             if (rc != RS_OK) return rc;
@@ -1786,7 +1793,7 @@ rs_rollout_record_kernel(const float *__restrict__ rew_src, float *__restrict__ 
 static int rollout_step_launch(rs_sim *h, const rs_rollout &R, const rs_policy *pol, uint32_t seed, uint32_t key, int t_slot, bool first, bool next,
                                hipStream_t st) {
     const size_t ns = (size_t)h->n_envs * h->K.n_signals, no = ns * h->K.lmax * 5, t = (size_t)t_slot;
-    const uint16_t *obs = h->O.drq_f16();
+    const uint16_t *obs = (const uint16_t *)agent_obs(h, pol, RS_AGENT_IPPO).ptr;
     uint16_t *obs_t = (uint16_t *)R.obs + t * no;
     const int vec = (((uintptr_t)obs | (uintptr_t)obs_t | (no * 2)) & 15) == 0;      // (no * 2: the next slot is aligned as well)
     const size_t items = vec ? (no / 8 > ns ? no / 8 : ns) : no;
@@ -1809,10 +1816,7 @@ extern "C" int rs_group_rollout(const rs_handle *hs, int32_t n_handles, const rs
         if (!h) return RS_EINVAL;
         const rs_rollout &R = segs[i];
         if (!agent || agent->kind != RS_AGENT_IPPO) { h->err = "rs_group_rollout: the agent must be RS_AGENT_IPPO"; return RS_EINVAL; }
-        if (!agent->policy || agent->policy->kind != POLICY_IDQN || agent->policy->W.S != h->K.n_signals || agent->policy->W.lmax != h->K.lmax) {
-            h->err = "rs_group_rollout: RS_AGENT_IPPO needs an rs_idqn_create policy built for this scenario (n_signals, lmax)"; return RS_EINVAL; }
-        if (agent->policy->device != h->device) { h->err = "rs_group_rollout: the policy's weights live on another device than this handle"; return RS_EINVAL; }
-        if (!(h->out_mask & OUT_DRQ_F16)) { h->err = "rs_group_rollout: RS_AGENT_IPPO reads RS_BUF_DRQ_NORM_F16, which rs_set_outputs has switched off"; return RS_EINVAL; }
+        if (const char *why = policy_fit_refusal(h, agent->policy, RS_AGENT_IPPO)) { h->err = std::string("rs_group_rollout: ") + why; return RS_EINVAL; }
         if (!R.obs || !R.act || !R.logp || !R.value || !R.rew) { h->err = "rs_group_rollout: a segment buffer is NULL"; return RS_EINVAL; }
         if ((long long)t0 + n_steps > R.T) { h->err = "rs_group_rollout: t0 + n_steps exceeds the segment's T slots"; return RS_EINVAL; }
     }
@@ -1825,7 +1829,7 @@ extern "C" int rs_group_rollout(const rs_handle *hs, int32_t n_handles, const rs
     return RS_OK;
 }
 
-// ---- rs_idqn_pack_weights / rs_dqn_sync_target / rs_mplight_dqn_sync_target (resco_group_train.h): one launch each
+// ---- rs_idqn_pack_weights (resco_group_train.h): one launch
 static void idqn_pack_launch(const rs_policy *p, const float *fc1_w, const float *fc2_w, const float *fc3_w, const float *fc3_b, hipStream_t st) {
     const GtPack P{fc1_w, fc2_w, fc3_w, fc3_b, (uint16_t *)p->W.w1, (uint16_t *)p->W.w2, (uint16_t *)p->W.w3, (float *)p->W.b3, p->W.lmax, p->amax};
     hipLaunchKernelGGL(rs_idqn_pack_kernel, dim3((gt_pack_units(p->W.lmax) + 255) / 256, p->W.S), dim3(256), 0, st, P);
@@ -1840,42 +1844,7 @@ static const char *idqn_pack_refusal(const rs_policy *p) {
 extern "C" int rs_idqn_pack_weights(rs_policy_handle p, const rs_dqn_tensors *params, void *stream) {
     if (const char *why = idqn_pack_refusal(p)) { g_create_err = std::string("rs_idqn_pack_weights: ") + why; return RS_EINVAL; }
     if (!params || !params->fc1_w || !params->fc2_w || !params->fc3_w || !params->fc3_b) { g_create_err = "rs_idqn_pack_weights: a parameter pointer is NULL"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    idqn_pack_launch(p, params->fc1_w, params->fc2_w, params->fc3_w, params->fc3_b, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
-}
-
-static void sync_launch(const GtSync &Y, hipStream_t st) {
-    int64_t most = 1;
-    for (int i = 0; i < Y.count; ++i) most = Y.n[i] > most ? Y.n[i] : most;
-    const int64_t blocks = (most / 4 + 255) / 256 + 1;
-    hipLaunchKernelGGL(rs_sync_target_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024), Y.count), dim3(256), 0, st, Y);
-}
-// the element counts of a BatchedIDQN's eight tensors, in rs_dqn_tensors order
-static void dqn_sync_launch(const rs_dqn *p, hipStream_t st) {
-    const DqnTrainTab &T = p->T;
-    const int64_t S = T.S, n[8] = {S * 256, S * 64, S * 64 * T.H * 4 * 64, S * 64, S * 4096, S * 64, S * 64 * T.amax, S * T.amax};
-    GtSync Y{};
-    Y.count = 8;
-    for (int i = 0; i < 8; ++i) { Y.src[i] = T.par.p[i]; Y.dst[i] = T.tgt.p[i]; Y.n[i] = n[i]; }
-    sync_launch(Y, st);
-}
-static void mplight_dqn_sync_launch(const rs_mplight_dqn *p, hipStream_t st) {
-    GtSync Y{};
-    Y.count = 1; Y.src[0] = p->T.par; Y.dst[0] = (float *)p->T.tgt; Y.n[0] = p->T.n;      // (the writable alias of the vector the create call took as const)
-    sync_launch(Y, st);
-}
-extern "C" int rs_dqn_sync_target(rs_dqn_handle p, void *stream) {
-    if (!p) { g_create_err = "rs_dqn_sync_target: NULL handle"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    dqn_sync_launch(p, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
-}
-extern "C" int rs_mplight_dqn_sync_target(rs_mplight_dqn_handle p, void *stream) {
-    if (!p) { g_create_err = "rs_mplight_dqn_sync_target: NULL handle"; return RS_EINVAL; }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    mplight_dqn_sync_launch(p, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] { idqn_pack_launch(p, params->fc1_w, params->fc2_w, params->fc3_w, params->fc3_b, (hipStream_t)stream); });
 }
 
 // ---- rs_group_train: the --device-update loop of tools/idqn_train.py / tools/mplight_train.py, n_steps iterations enqueued by one call
@@ -1891,10 +1860,10 @@ static void record_launch(const GtRec &R, hipStream_t st) {
     hipLaunchKernelGGL(rs_train_record_kernel, dim3(grid), dim3(256), 0, st, R);
 }
 
-extern "C" int rs_group_train(const rs_handle *hs, int32_t n_handles, const rs_train *tr, int32_t n_steps) {
-    if (!hs || n_handles <= 0 || !hs[0]) return RS_EINVAL;
-    for (int i = 0; i < n_handles; ++i)
-        if (!hs[i]) return RS_EINVAL;
+// H / Ring: rs_dqn / rs_dqn_ring (tr->kind RS_AGENT_IDQN) or rs_mplight_dqn / rs_mplight_ring (RS_AGENT_MPLIGHT).  `idqn` decides only what
+// differs in substance: how the learner fits the policy, the ring's row, the recorder's sources and the pack after an IDQN update.
+template <class H, class Ring> static int group_train(const rs_handle *hs, int32_t n_handles, const rs_train *tr, int32_t n_steps) {
+    constexpr bool idqn = std::is_same<H, rs_dqn>::value;
     auto refuse = [&](int i, const std::string &why) { hs[i]->err = "rs_group_train: " + why; g_create_err = hs[i]->err; return RS_EINVAL; };
     if (!tr) return refuse(0, "NULL arguments");
     if (n_steps < 1) return refuse(0, "need n_steps >= 1");
@@ -1905,52 +1874,42 @@ extern "C" int rs_group_train(const rs_handle *hs, int32_t n_handles, const rs_t
     if (!tr->policy || !tr->learner) return refuse(0, "a policy and a learner handle are required");
     if (!tr->obs || !tr->act || !tr->rew || !tr->done) return refuse(0, "a ring pointer is NULL");
     if (tr->capacity < 2 || tr->head < 0 || tr->head >= tr->capacity || tr->count < 0 || tr->count > tr->capacity) return refuse(0, "the ring needs capacity >= 2, 0 <= head < capacity, 0 <= count <= capacity");
-    const bool idqn = tr->kind == RS_AGENT_IDQN;
     rs_policy *pol = tr->policy;
-    rs_dqn *dq = idqn ? (rs_dqn *)tr->learner : nullptr;
-    rs_mplight_dqn *mq = idqn ? nullptr : (rs_mplight_dqn *)tr->learner;
+    H *lq = (H *)tr->learner;
     rs_sim *h0 = hs[0];
     const int S = h0->K.n_signals, lmax = h0->K.lmax, dev = h0->device;
-    int width = 0;              // elements of one (environment, signal) row of the ring's obs
-    if (idqn) {
-        if (pol->kind != POLICY_IDQN || pol->W.S != S || pol->W.lmax != lmax) return refuse(0, "RS_AGENT_IDQN needs an rs_idqn_create policy built for this scenario (n_signals, lmax)");
-        if (dq->T.S != S || dq->T.lmax != lmax || dq->T.amax != pol->amax) return refuse(0, "the learner does not fit the policy and the scenario (n_signals, lmax, amax)");
-        if (const char *why = idqn_pack_refusal(pol)) return refuse(0, why);
-        width = lmax * 5;
-    } else {
-        if (pol->kind != POLICY_MPLIGHT || pol->F.S != S) return refuse(0, "RS_AGENT_MPLIGHT needs an rs_mplight_create policy built for this scenario (n_signals)");
-        if (mq->T.S != S || mq->T.D != pol->F.D || mq->T.P != pol->F.P) return refuse(0, "the learner does not fit the policy and the scenario (n_signals, demand_shape, n_pairs)");
-        if (pol->F.w != mq->T.par) return refuse(0, "the MPLight policy must read the learner's parameter vector (rs_mplight_set_device_weights): nothing re-packs it here");
-        width = 1 + FRAP_MV * pol->F.D;
-    }
-    if (pol->device != dev) return refuse(0, "the policy's weights live on another device than the handles");
-    if ((idqn ? dq->device : mq->device) != dev) return refuse(0, "the learner lives on another device than the handles");
-    const uint32_t need = idqn ? OUT_DRQ_F16 : (pol->F.D == 1 ? OUT_MPLIGHT : OUT_MPLIGHT_FULL);
     long long rows = 0;
     for (int i = 0; i < n_handles; ++i) {
         rs_sim *h = hs[i];
         if (h->device != dev || h->K.n_signals != S || h->K.lmax != lmax) return refuse(i, "the handles of a group share one device and one scenario");
-        if (!h->blocking) return refuse(i, "this handle's stream is a non-blocking stream (RESCO_PLAIN_STREAMS, or hipExtStreamCreateWithCUMask failed at rs_create): "
-                                           "nothing would order it with the learner's launches on the legacy stream");
-        if (h->timing) return refuse(i, "rs_timing is enabled on this handle: its events are not part of this loop");
-        if (!(h->out_mask & need)) return refuse(i, idqn ? "RS_AGENT_IDQN reads RS_BUF_DRQ_NORM_F16, which rs_set_outputs has switched off"
-                                                          : (pol->F.D == 1 ? "RS_AGENT_MPLIGHT reads RS_BUF_MPLIGHT, which rs_set_outputs has switched off"
-                                                                           : "RS_AGENT_MPLIGHT reads RS_BUF_MPLIGHT_FULL, which rs_set_outputs has switched off"));
+        if (const char *why = policy_fit_refusal(h, pol, tr->kind)) return refuse(i, why);
+        if (const char *why = loop_handle_refusal(h)) return refuse(i, why);
         if (h->env_base != h0->env_base + rows) return refuse(i, "the pipes' env_base values must be contiguous in group order (pipe i owns the ring rows behind those of pipes 0 .. i - 1)");
         rows += h->n_envs;
     }
     if (rows != tr->n_envs) return refuse(0, "the pipes' environments do not add up to the ring's n_envs");
-    // the learner's own checks of the ring (pointers on its device, batch within its workspace), at a position every ring can have
-    if (idqn) {
-        const rs_dqn_ring r0{tr->obs, tr->act, tr->rew, tr->done, tr->capacity, tr->n_envs, 0, 2};
-        if (dqn_check(dq, &r0, tr->batch, "rs_group_train")) { h0->err = g_create_err; return RS_EINVAL; }
+    int width = 0;              // elements of one (environment, signal) row of the ring's obs
+    if constexpr (idqn) {
+        if (lq->T.S != S || lq->T.lmax != lmax || lq->T.amax != pol->amax) return refuse(0, "the learner does not fit the policy and the scenario (n_signals, lmax, amax)");
+        if (const char *why = idqn_pack_refusal(pol)) return refuse(0, why);
+        width = lmax * 5;
     } else {
-        const rs_mplight_ring r0{(const float *)tr->obs, tr->act, tr->rew, tr->done, tr->capacity, tr->n_envs, S, width, 0, 2};
-        if (mplight_dqn_check(mq, &r0, tr->batch, "rs_group_train")) { h0->err = g_create_err; return RS_EINVAL; }
+        if (lq->T.S != S || lq->T.D != pol->F.D || lq->T.P != pol->F.P) return refuse(0, "the learner does not fit the policy and the scenario (n_signals, demand_shape, n_pairs)");
+        if (pol->F.w != lq->T.par) return refuse(0, "the MPLight policy must read the learner's parameter vector (rs_mplight_set_device_weights): nothing re-packs it here");
+        width = 1 + FRAP_MV * pol->F.D;
+    }
+    if (lq->device != dev) return refuse(0, "the learner lives on another device than the handles");
+    auto ring_at = [&](int head, int count) {
+        if constexpr (idqn) return Ring{tr->obs, tr->act, tr->rew, tr->done, tr->capacity, tr->n_envs, head, count};
+        else return Ring{(const float *)tr->obs, tr->act, tr->rew, tr->done, tr->capacity, tr->n_envs, S, width, head, count};
+    };
+    // the learner's own checks of the ring (pointers on its device, batch within its workspace), at a position every ring can have
+    const Ring r0 = ring_at(0, 2);
+    if (dqn_check(lq, &r0, tr->batch, "rs_group_train")) { h0->err = g_create_err; return RS_EINVAL; }
+    if constexpr (!idqn)
         for (int i = 0; i < n_handles; ++i)
             if (!hs[i]->pair)
                 if (int rc = dev_alloc(hs[i], &hs[i]->pair, (size_t)hs[i]->n_envs * S)) return rc;
-    }
     if (tr->ret && !dqn_on_device(tr->ret, dev)) return refuse(0, "ret is not device memory of the handles' device");
 
     GtLoop L{};
@@ -1970,13 +1929,13 @@ extern "C" int rs_group_train(const rs_handle *hs, int32_t n_handles, const rs_t
             hipStream_t st;
             if (int rc = enter(h, own_streams ? nullptr : (void *)hipStreamLegacy, &st)) return rc;
             const size_t ns = (size_t)h->n_envs * S, at = ((size_t)P.slot * tr->n_envs + row0) * S;
-            const void *obs = idqn ? (const void *)h->O.drq_f16() : (pol->F.D == 1 ? (const void *)h->O.mplight() : (const void *)h->O.mplight_full());
+            const void *obs = agent_obs(h, pol, tr->kind).ptr;
             GtRec R{};
             R.obs_src = obs; R.obs_dst = (char *)tr->obs + at * width * esz; R.n_obs = (int32_t)(ns * width);
             R.obs_kind = idqn ? GT_OBS_F16 : (pol->F.D == 1 ? GT_OBS_I32_F32 : GT_OBS_F32);
             R.vec = (((uintptr_t)R.obs_src | (uintptr_t)R.obs_dst) & 15) == 0;
             record_launch(R, st);
-            if (idqn) idqn_launch(pol->W, obs, h->n_envs, h->P.env_base, 0, P.epsilon, tr->policy_seed, P.key, nullptr, h->actions, nullptr, st);
+            if constexpr (idqn) idqn_launch(pol->W, obs, h->n_envs, h->P.env_base, 0, P.epsilon, tr->policy_seed, P.key, nullptr, h->actions, nullptr, st);
             else mplight_launch(pol->F, obs, h->n_envs, h->P.env_base, P.epsilon, tr->policy_seed, P.key, nullptr, h->actions, h->pair, nullptr, st);
             HIPCHK(h, hipGetLastError());
             if (int rc = launch_step(h, st, h->K.step_length * h->ratio, 1)) return rc;
@@ -1990,20 +1949,23 @@ extern "C" int rs_group_train(const rs_handle *hs, int32_t n_handles, const rs_t
             row0 += (size_t)h->n_envs;
         }
         // the learner's observe_step on the legacy stream: it waits for every pipe, and the pipes' next launches wait for it
-        if (P.sync) { if (idqn) dqn_sync_launch(dq, hipStreamLegacy); else mplight_dqn_sync_launch(mq, hipStreamLegacy); }
+        if (P.sync) dqn_sync_launch(lq, hipStreamLegacy);
         if (P.update) {
-            if (idqn) {
-                const rs_dqn_ring r{tr->obs, tr->act, tr->rew, tr->done, tr->capacity, tr->n_envs, P.head, P.count};
-                dqn_update_launch(dq, &r, tr->batch, tr->learner_seed, tr->updates_per_step, tr->loss_out, hipStreamLegacy);
-                idqn_pack_launch(pol, dq->T.par.p[PT_FC1_W], dq->T.par.p[PT_FC2_W], dq->T.par.p[PT_FC3_W], dq->T.par.p[PT_FC3_B], hipStreamLegacy);
-            } else {
-                const rs_mplight_ring r{(const float *)tr->obs, tr->act, tr->rew, tr->done, tr->capacity, tr->n_envs, S, width, P.head, P.count};
-                mplight_dqn_update_launch(mq, &r, tr->batch, tr->learner_seed, tr->updates_per_step, tr->loss_out, hipStreamLegacy);
-            }
+            const Ring r = ring_at(P.head, P.count);
+            dqn_update_launch(lq, &r, tr->batch, tr->learner_seed, tr->updates_per_step, tr->loss_out, hipStreamLegacy);
+            if constexpr (idqn)
+                idqn_pack_launch(pol, lq->T.par.p[PT_FC1_W], lq->T.par.p[PT_FC2_W], lq->T.par.p[PT_FC3_W], lq->T.par.p[PT_FC3_B], hipStreamLegacy);
         }
         if (P.sync || P.update) HIPCHK(h0, hipGetLastError());
     }
     return RS_OK;
+}
+extern "C" int rs_group_train(const rs_handle *hs, int32_t n_handles, const rs_train *tr, int32_t n_steps) {
+    if (!hs || n_handles <= 0 || !hs[0]) return RS_EINVAL;
+    for (int i = 0; i < n_handles; ++i)
+        if (!hs[i]) return RS_EINVAL;
+    if (tr && tr->kind == RS_AGENT_MPLIGHT) return group_train<rs_mplight_dqn, rs_mplight_ring>(hs, n_handles, tr, n_steps);
+    return group_train<rs_dqn, rs_dqn_ring>(hs, n_handles, tr, n_steps);      // (which refuses a NULL tr and any other kind)
 }
 
 // ---- rs_ippo_pack_weights: the actor-critic pack (resco_group_train.h: gt_pack_unit_value), one launch
@@ -2017,9 +1979,7 @@ extern "C" int rs_ippo_pack_weights(rs_policy_handle p, const rs_ppo_tensors *pa
     if (!params || !params->fc1_w || !params->fc2_w || !params->fc3_w || !params->fc3_b || !params->v_w || !params->v_b) {
         g_create_err = "rs_ippo_pack_weights: a parameter pointer is NULL"; return RS_EINVAL;
     }
-    if (hipSetDevice(p->device) != hipSuccess) return RS_EHIP;
-    ippo_pack_launch(p, train_tensors(params, PPT_NT), (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? RS_OK : RS_EHIP;
+    return on_device(p->device, [&] { ippo_pack_launch(p, train_tensors(params, PPT_NT), (hipStream_t)stream); });
 }
 
 // ---- rs_group_ppo_train: the --device-update loop of tools/ippo_train.py, n_steps iterations enqueued by one call (include/resco_sim.h).
@@ -2046,16 +2006,12 @@ extern "C" int rs_group_ppo_train(const rs_handle *hs, int32_t n_handles, const 
     rs_policy *pol = tr->policy;
     rs_ppo *pp = tr->learner;
     const int S = h->K.n_signals, N = h->n_envs;
-    if (pol->kind != POLICY_IDQN || pol->W.S != S || pol->W.lmax != h->K.lmax) return refuse("needs an rs_idqn_create policy built for this scenario (n_signals, lmax)");
+    if (const char *why = policy_fit_refusal(h, pol, RS_AGENT_IPPO)) return refuse(why);
     if (pp->T.S != S || pp->T.lmax != h->K.lmax || pp->T.amax != pol->amax) return refuse("the learner does not fit the policy and the scenario (n_signals, lmax, amax)");
     if (const char *why = idqn_pack_refusal(pol)) return refuse(why);
-    if (pol->device != h->device) return refuse("the policy's weights live on another device than the handle");
     if (pp->device != h->device) return refuse("the learner lives on another device than the handle");
     if (tr->minibatch < 1 || tr->minibatch > pp->max_batch) return refuse("need 1 <= minibatch <= max_minibatch of rs_ppo_create");
-    if (!h->blocking) return refuse("this handle's stream is a non-blocking stream (RESCO_PLAIN_STREAMS, or hipExtStreamCreateWithCUMask failed at rs_create): "
-                                    "nothing would order its other launches with this loop's on the legacy stream");
-    if (h->timing) return refuse("rs_timing is enabled on this handle: its events are not part of this loop");
-    if (!(h->out_mask & OUT_DRQ_F16)) return refuse("RS_AGENT_IPPO reads RS_BUF_DRQ_NORM_F16, which rs_set_outputs has switched off");
+    if (const char *why = loop_handle_refusal(h)) return refuse(why);
 
     const GpLoop L{T, tr->slot0, tr->done_step, tr->t0, tr->update0};
     const int n = T * N;
@@ -2066,11 +2022,11 @@ extern "C" int rs_group_ppo_train(const rs_handle *hs, int32_t n_handles, const 
         const bool first = k == 0 || P.slot == 0, next = k + 1 < n_steps && P.slot + 1 < T;
         if (first) {        // the done bytes of the slots this call fills from here to the segment's end
             const int m = T - P.slot < n_steps - k ? T - P.slot : n_steps - k;
-            hipLaunchKernelGGL(rs_ppo_done_kernel, dim3((m + 255) / 256), dim3(256), 0, st, tr->done + P.slot, m, tr->done_step - k);
+            hipLaunchKernelGGL(rs_done_kernel<uint8_t>, dim3((m + 255) / 256), dim3(256), 0, st, tr->done + P.slot, m, tr->done_step - k);
         }
         if (int rc = rollout_step_launch(h, R, pol, tr->policy_seed, P.key, P.slot, first, next, st)) return rc;
         if (!P.update) continue;
-        ippo_launch(pol->W, h->O.drq_f16(), N, 0, tr->policy_seed, 0u, nullptr, nullptr, nullptr, nullptr, tr->last_value, nullptr, st);
+        ippo_launch(pol->W, agent_obs(h, pol, RS_AGENT_IPPO).ptr, N, 0, tr->policy_seed, 0u, nullptr, nullptr, nullptr, nullptr, tr->last_value, nullptr, st);
         gae_launch(PpoArgs{R.rew, R.value, tr->last_value, tr->done, T, N, S, tr->gamma, tr->lambda, tr->adv, tr->ret, (float *)tr->gae_scratch}, st);
         ppo_perm_launch(n, tr->epochs, tr->learner_seed, P.update_key, tr->perm, st);
         ppo_fit_launch(pp, R.obs, R.act, R.logp, tr->adv, tr->ret, n, tr->perm, tr->epochs, tr->minibatch, tr->loss_out, st);
@@ -2083,15 +2039,10 @@ extern "C" int rs_group_ppo_train(const rs_handle *hs, int32_t n_handles, const 
 // ---- rs_fma2c_record: the reward of all agents and the recorder of a step (resco_fma2c_loop.h), one launch
 // why a call with this handle, policy and table is refused, or NULL
 static const char *fma2c_record_refusal(const rs_sim *h, const rs_policy *p, const rs_fma2c_reward_table *tab) {
-    if (!p) return "the policy handle is NULL";
     if (!tab || !tab->off || !tab->idx || !tab->w) return "the reward table or one of its pointers is NULL";
-    if (p->kind != POLICY_FMA2C) return "the policy is not an rs_fma2c_create policy";
-    if (p->A.S != h->K.n_signals || p->A.O != h->K.n_obs) return "needs a policy built for this scenario (n_signals, n_obs)";
-    if (p->device != h->device) return "the policy lives on another device than the handle";
-    if (h->P.env_base < 0 || (int64_t)h->P.env_base + h->n_envs > p->A.max_envs) return "env_base + n_envs of the handle exceeds the policy's max_envs";
+    if (const char *why = policy_fit_refusal(h, p, RS_AGENT_FMA2C)) return why;     // (RS_BUF_LANE_AGG: the reward reads what the agent reads)
     if (tab->K != p->A.K) return "the reward table's K is not the policy's K";
     if (tab->n_rows != 3 * h->K.n_obs + 2 * h->K.n_signals) return "the reward table's n_rows is not 3 n_obs + 2 S of this scenario";
-    if (!(h->out_mask & OUT_LANE_AGG)) return "the reward reads RS_BUF_LANE_AGG, which rs_set_outputs has switched off";
     if (!(h->out_mask & OUT_LANE_ARR)) return "the reward reads RS_BUF_LANE_ARRIVALS, which rs_set_outputs has switched off";
     return nullptr;
 }
@@ -2141,11 +2092,10 @@ extern "C" int rs_group_fma2c_train(const rs_handle *hs, int32_t n_handles, cons
     if (const char *why = fma2c_record_refusal(h, pol, &tr->table)) return refuse(why);
     if (pol->A.max_envs != h->n_envs || h->P.env_base != 0) return refuse("the policy's max_envs must be the handle's n_envs (and its env_base 0): the learner's segment is the policy's batch");
     if (l->pol != pol) return refuse("the learner was created for another policy");
-    if (!h->blocking) return refuse("this handle's stream is a non-blocking stream (RESCO_PLAIN_STREAMS, or hipExtStreamCreateWithCUMask failed at rs_create): "
-                                    "nothing would order its other launches with this loop's on the legacy stream");
-    if (h->timing) return refuse("rs_timing is enabled on this handle: its events are not part of this loop");
+    if (const char *why = loop_handle_refusal(h)) return refuse(why);
 
     const Fma2cTab &A = pol->A;
+    const float *lane_agg = (const float *)agent_obs(h, pol, RS_AGENT_FMA2C).ptr;
     const int N = h->n_envs;
     const size_t nk = (size_t)N * A.K, n_state = nk * 4 * FM_L;
     for (int k = 0; k < n_steps; ++k) {
@@ -2154,17 +2104,17 @@ extern "C" int rs_group_fma2c_train(const rs_handle *hs, int32_t n_handles, cons
         if (int rc = enter(h, (void *)hipStreamLegacy, &st)) return rc;
         if (k == 0 || P.slot == 0) {        // the post-step dones of the slots this call fills from here to the next update
             const int m = T - P.slot < n_steps - k ? T - P.slot : n_steps - k;
-            hipLaunchKernelGGL(rs_fma2c_done_kernel, dim3((m + 255) / 256), dim3(256), 0, st, tr->dones + P.slot + 1, m, tr->done_step - k);
+            hipLaunchKernelGGL(rs_done_kernel<int32_t>, dim3((m + 255) / 256), dim3(256), 0, st, tr->dones + P.slot + 1, m, tr->done_step - k);
         }
         const size_t at = (size_t)P.slot * nk;
-        fma2c_act_launch(pol, h->O.lane_agg(), N, 0, tr->policy_seed, P.key, nullptr, Fma2cOut{h->actions, nullptr, tr->vals + at, tr->rows + at * A.W}, st);
+        fma2c_act_launch(pol, lane_agg, N, 0, tr->policy_seed, P.key, nullptr, Fma2cOut{h->actions, nullptr, tr->vals + at, tr->rows + at * A.W}, st);
         HIPCHK(h, hipGetLastError());
         if (int rc = launch_step(h, st, h->K.step_length * h->ratio, 1)) return rc;
         fma2c_record_launch(h, pol, tr->table, tr->rews + at, tr->acts + at, tr->ret_acc, st);
         HIPCHK(h, hipGetLastError());
         if (!P.update) continue;
         if (P.done) hipLaunchKernelGGL(ft_fill_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, tr->R_boot, nk, 0.0f);
-        else fma2c_value_launch(pol, h->O.lane_agg(), N, 0, tr->R_boot, st);
+        else fma2c_value_launch(pol, lane_agg, N, 0, tr->R_boot, st);
         HIPCHK(h, hipGetLastError());
         if (ft_grad_launch(l, tr->rows, tr->acts, tr->rews, tr->vals, tr->dones, tr->R_boot, P.n_slots, tr->loss_out, st) != RS_OK ||
             ft_step_launch(l, st) != RS_OK) { h->err = "rs_group_fma2c_train: a launch of the update failed"; return RS_EHIP; }

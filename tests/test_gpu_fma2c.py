@@ -265,7 +265,7 @@ def test_refusals():
     grp = SimGroup([sim])
     before = sim.read('actions')
     herr = lambda: (lib.rs_last_error(sim._h) or b'').decode()
-    with pytest.raises(RuntimeError, match='needs an rs_fma2c_create policy'):
+    with pytest.raises(RuntimeError, match='not an rs_fma2c_create policy'):
         grp.step('fma2c', policy=mpl.handle)
     with pytest.raises(RuntimeError, match='rs_mplight_create policy'):
         grp.step('mplight', policy=pol.handle)
