@@ -399,7 +399,8 @@ int rs_ppo_gae(const float *rew, const float *value, const float *last_value, co
  * [n][S][lmax][5], act int32 / logp / adv / ret float [n][S]; the means are over B.  loss_out: NULL or device float [S][3] = the
  * policy term, (value - ret)^2 and the entropy of every signal, un-weighted.
  * rs_ppo_step: per signal min(1, max_grad_norm / (norm + 1e-6)), then Adam on what grads holds (grads itself stays un-scaled);
- * advances t.  rs_ppo_steps: t.
+ * advances t.  rs_ppo_steps: t.  rs_ppo_set_steps: t <- the argument (restoring a checkpoint): the host-side counter alone, so the next
+ * rs_ppo_step is Adam step t + 1; no launch and no synchronisation, what is enqueued afterwards sees it; RS_EINVAL for t < 0.
  * rs_ppo_fit: for e < epochs, for i = 0, minibatch, .. < n: rs_ppo_grad on perm[e][i : i + minibatch] (device int32 [epochs][n];
  * the last minibatch may be short), then rs_ppo_step -- the same launches, enqueued by one call; loss_out holds the last one's.
  * Fixed summation order, no atomics: the same state and data give the same bits.  Everything is launched on `stream`.
@@ -427,6 +428,7 @@ int rs_ppo_step(rs_ppo_handle p, void *stream);
 int rs_ppo_fit(rs_ppo_handle p, const void *obs, const int32_t *act, const float *logp, const float *adv, const float *ret, int32_t n,
                const int32_t *perm, int32_t epochs, int32_t minibatch, float *loss_out, void *stream);
 int64_t rs_ppo_steps(rs_ppo_handle p);
+int rs_ppo_set_steps(rs_ppo_handle p, int64_t t);
 void rs_ppo_destroy(rs_ppo_handle p);
 
 /* ---- IDQN: the DQN update on the device (resco_amd/csrc/resco_dqn_train.h) -------------------------------------------
@@ -445,6 +447,8 @@ void rs_ppo_destroy(rs_ppo_handle p);
  * tgt = rew[t][e][s] + gamma max_{a < A_s} Q_target(obs[(t + 1) mod capacity][e][s])[a], or rew alone where done[t] (the successor
  * is then not read); loss = mean over the batch of Huber(Q(obs[t][e][s])[act] - tgt, delta 1); loss_out: device float [S] or NULL.
  * rs_dqn_step: Adam (no gradient clipping, as PFRL's DQN) on what grads holds; advances the step count.  rs_dqn_steps: that count.
+ * rs_dqn_set_steps: the count <- t (restoring a checkpoint): the host-side counter alone, so the next Adam step is step t + 1 and the
+ * next rs_dqn_update draws with update_key = t; no launch and no synchronisation, what is enqueued afterwards sees it; RS_EINVAL for t < 0.
  * rs_dqn_update: for j < n_updates: rs_dqn_sample with update_key = the step count so far into the handle's own index array,
  * rs_dqn_grad, rs_dqn_step -- the same launches, all enqueued by one call without host synchronisation or copies.
  * All calls are asynchronous on `stream`; every sum has one fixed order (no float atomics): the same state gives the same bits.
@@ -478,6 +482,7 @@ int rs_dqn_step(rs_dqn_handle p, void *stream);
 int rs_dqn_update(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out,
                   void *stream);
 int64_t rs_dqn_steps(rs_dqn_handle p);
+int rs_dqn_set_steps(rs_dqn_handle p, int64_t t);
 void rs_dqn_destroy(rs_dqn_handle p);
 
 /* ---- MPLight: the shared-DQN update on the device (resco_amd/csrc/resco_frap_train.h) -------------------------------
@@ -499,7 +504,8 @@ void rs_dqn_destroy(rs_dqn_handle p);
  * valid pairs, as the reference -- or rew alone where done[t] (the successor is then not read); loss = mean over the batch of
  * Huber(Q(obs[t][e][s])[act] - tgt, delta 1), act clamped into 0 .. n_pairs - 1; loss_out: ONE device float or NULL.
  * rs_mplight_dqn_step: Adam (no gradient clipping, as PFRL's DQN) on what grads holds; advances the step count.
- * rs_mplight_dqn_steps: that count.
+ * rs_mplight_dqn_steps: that count.  rs_mplight_dqn_set_steps: the count <- t, as rs_dqn_set_steps (next Adam step t + 1, next
+ * rs_mplight_dqn_update draws with update_key = t; nothing launched; RS_EINVAL for t < 0).
  * rs_mplight_dqn_update: for j < n_updates: rs_mplight_dqn_sample with update_key = the step count so far into the handle's own
  * index array, rs_mplight_dqn_grad, rs_mplight_dqn_step -- the same launches, all enqueued by one call without host synchronisation
  * or copies.
@@ -531,6 +537,7 @@ int rs_mplight_dqn_step(rs_mplight_dqn_handle p, void *stream);
 int rs_mplight_dqn_update(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out,
                           void *stream);
 int64_t rs_mplight_dqn_steps(rs_mplight_dqn_handle p);
+int rs_mplight_dqn_set_steps(rs_mplight_dqn_handle p, int64_t t);
 void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p);
 
 /* ---- the DQN training loop of IDQN and MPLight in one call (resco_amd/csrc/resco_group_train.h) -------------------------------

@@ -346,6 +346,29 @@ class A2CLearner:
         self.last_loss = loss.detach()
         return self.last_loss
 
+    # ---- checkpoints (resco_amd/checkpoint.py), at an episode boundary: the segment is empty there (n = 0), so it is not carried
+    def signature(self):
+        return {'T': self.T, 'n_envs': self.N, 'K': int(self.net.layout.K)}
+
+    def state_dict(self):
+        return {'state': {'ms': list(self.ms), 'states_bw': self.states_bw, 'dones': [bool(d) for d in self.dones], 'n': int(self.n),
+                          'steps_done': int(self.steps_done), 'updates': int(self.updates)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        from . import _state
+        if weights_only:
+            return
+        st = sd['state']
+        if int(st['n']) != 0:
+            raise ValueError('A2CLearner: the checkpoint was taken inside a segment (n = %d)' % int(st['n']))
+        if len(st['ms']) != len(self.ms):
+            raise ValueError('A2CLearner: the checkpoint holds %d ms tensors, the learner %d' % (len(st['ms']), len(self.ms)))
+        for i, (dst, src) in enumerate(zip(self.ms, st['ms'])):
+            _state.copy_into(dst, src, 'A2CLearner.ms[%d]' % i)
+        _state.copy_into(self.states_bw, st['states_bw'], 'A2CLearner.states_bw')
+        self.dones, self.n = [bool(d) for d in st['dones']], 0
+        self.steps_done, self.updates = int(st['steps_done']), int(st['updates'])
+
     def observe(self, rows, actions, rewards, values, done, states_fw, bootstrap):
         """MA2CAgent.observe (ma2c.py:133-147): store, and every batch_size steps or at done update with R = 0 (done) or
         bootstrap() -> v [N, K] of the new observation.  At done the segment start state is zeroed (model.reset()); zeroing the
@@ -413,6 +436,26 @@ class FusedFMA2C:
             self._wdev = torch.empty_like(flat)
         self._wdev.copy_(flat)
         self._check(self._lib.rs_fma2c_set_device_weights(self._h, self._wdev.data_ptr()), 'rs_fma2c_set_device_weights')
+
+    # ---- checkpoints (resco_amd/checkpoint.py): the library-owned buffers the reference never clears between episodes (fingerprints,
+    # parity, the managers' last actions) and the LSTM state, written in place through their zero-copy tensors
+    def signature(self):
+        return {'max_envs': self.max_envs, 'K': int(self.L.K), 'M': int(self.L.M)}
+
+    def state_dict(self):
+        return {'state': dict({k: self.buffer(k) for k in self.BUF}, seed=int(self.seed))}
+
+    def load_state_dict(self, sd, weights_only=False):
+        """A policy whose learner is alive keeps acting with the learner's vector (the learner's load wrote into it); one without
+        a learner re-packs the network, so list the network first."""
+        from . import _state
+        if not weights_only:
+            for k in self.BUF:
+                _state.copy_into(self.buffer(k), sd['state'][k], 'FusedFMA2C.%s' % k)
+            self.seed = int(sd['state']['seed']) & 0xFFFFFFFF
+        learner = getattr(self, '_learner', None)
+        if learner is None or learner() is None or learner()._h is None:
+            self.refresh_on_device()
 
     def buffer(self, name):
         """zero-copy tensor over the library's state [max_envs, K, 4, 64], fingerprints [2, max_envs, K, 8], mgr_actions [max_envs, M]

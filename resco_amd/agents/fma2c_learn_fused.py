@@ -135,6 +135,33 @@ class FusedA2CLearner:
         self.last_loss = self._loss.clone()
         return self.last_loss
 
+    # ---- checkpoints (resco_amd/checkpoint.py), at an episode boundary (the segment is empty there): the library-owned weights, ms
+    # and states_bw are written in place through their zero-copy tensors.  The learner has no hidden counter: TF1's RMSProp has
+    # no bias correction and the rate is constant.
+    def signature(self):
+        return {'T': self.T, 'n_envs': self.N, 'K': int(self.net.layout.K)}
+
+    def state_dict(self):
+        return {'weights': {'weights': self.buffer('weights')},
+                'state': {'ms': self.buffer('ms'), 'states_bw': self.buffer('states_bw'), 'dones': [bool(d) for d in self.dones],
+                          'dones_dev0': int(self.dones_dev[0]), 'n': int(self.n), 'steps_done': int(self.steps_done), 'updates': int(self.updates)}}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, weights_only=False):
+        from . import _state
+        _state.copy_into(self.buffer('weights'), sd['weights']['weights'], 'FusedA2CLearner.weights')
+        self.pull()                             # the network mirrors the vector the policy acts with
+        if weights_only:
+            return
+        st = sd['state']
+        if int(st['n']) != 0:
+            raise ValueError('FusedA2CLearner: the checkpoint was taken inside a segment (n = %d)' % int(st['n']))
+        _state.copy_into(self.buffer('ms'), st['ms'], 'FusedA2CLearner.ms')
+        _state.copy_into(self.buffer('states_bw'), st['states_bw'], 'FusedA2CLearner.states_bw')
+        self.dones, self.n = [bool(d) for d in st['dones']], 0
+        self.dones_dev[0] = int(st['dones_dev0'])
+        self.steps_done, self.updates = int(st['steps_done']), int(st['updates'])
+
     def observe(self, rows, actions, rewards, values, done, states_fw, bootstrap):
         """A2CLearner.observe: store, and every batch_size steps or at done update with R = 0 (done) or bootstrap()"""
         from ..sim import torch_stream

@@ -153,6 +153,17 @@ class FusedIDQN:
         if rc != 0:
             raise RuntimeError('rs_idqn_set_device_weights failed (%d)' % rc)
 
+    # ---- checkpoints (resco_amd/checkpoint.py): the weights are the network's; after a load the packed buffers follow them
+    def state_dict(self):
+        return {'state': {'seed': int(self.seed)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        """list the network before its policy: this re-packs what the network holds NOW into the buffers the kernel reads"""
+        if not weights_only:
+            self.seed = int(sd['state']['seed']) & 0xFFFFFFFF
+        self._check_padded_rows_are_zero()
+        self.refresh_on_device()
+
     def close(self):
         if getattr(self, '_h', None):
             self._lib.rs_idqn_destroy(self._h)

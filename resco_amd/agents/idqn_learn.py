@@ -21,6 +21,7 @@ import copy
 
 import torch
 
+from . import _state
 from .idqn_rollout import BatchedIDQN
 from .trunk import fc1_row_mask
 
@@ -73,6 +74,17 @@ class DeviceReplay:
         """obs [N,S,L,5], act [N,S] int, rew [N,S] float, done bool (lock-step: one flag for all envs)."""
         self.stage(obs)
         self.commit(act, rew, done)
+
+    # ---- checkpoints (resco_amd/checkpoint.py): the ring IS training state; loaded in place, the library reads these arrays
+    def signature(self):
+        return _state.ring_signature(self)
+
+    def state_dict(self, replay=True):
+        return _state.ring_state(self, replay)
+
+    def load_state_dict(self, sd, weights_only=False):
+        if not weights_only:
+            _state.load_ring_state(self, sd, 'DeviceReplay')
 
     def sample(self, batch_size, generator=None):
         """Independent minibatch per signal: returns o [B,S,L,5], a [B,S] long, r [B,S], o2 [B,S,L,5], d [B,S] float."""
@@ -154,7 +166,10 @@ class BatchedDQNLearner:
         kernels of an update are launch-bound (S = 21 networks x batch 256 is little work each); replaying the graph
         removes the launch gaps.  Needs >= 2 slots in the ring and an Adam created with capturable=True (done here,
         optimiser state is carried over by re-creating it before any update has run)."""
-        assert self.n_updates == 0 and len(replay) >= 1
+        assert len(replay) >= 1
+        carried = _state.adam_state(self.opt)           # empty before the first update; a loaded checkpoint's otherwise
+        carried = dict(carried, exp_avg=[t.clone() for t in carried['exp_avg']], exp_avg_sq=[t.clone() for t in carried['exp_avg_sq']])
+        done_before = self.n_updates
         self.opt = torch.optim.Adam(self.q.parameters(), lr=self.opt.param_groups[0]['lr'], capturable=True)
         self._graph_replay = replay
 
@@ -183,10 +198,27 @@ class BatchedDQNLearner:
             for v in st_.values():
                 if torch.is_tensor(v):
                     v.zero_()
+        _state.load_adam_state(self.opt, carried, 'BatchedDQNLearner.opt')      # in place: the graph reads these tensors
+        self.n_updates = done_before
         return self
 
     def sync_target(self):
         self.target.load_state_dict(self.q.state_dict())
+
+    # ---- checkpoints (resco_amd/checkpoint.py).  Everything is loaded IN PLACE, so a learner whose update has been graph-captured
+    # (capture_update) keeps its graph: the graph reads the parameters, the gradients and the optimizer's state tensors by address.
+    def signature(self):
+        return {'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}
+
+    def state_dict(self):
+        return {'weights': {'target': _state.module_tensors(self.target)},
+                'state': {'opt': _state.adam_state(self.opt), 't': int(self.t), 'n_updates': int(self.n_updates)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        _state.load_module(self.target, sd['weights']['target'], 'BatchedDQNLearner.target')
+        if not weights_only:
+            _state.load_adam_state(self.opt, sd['state']['opt'], 'BatchedDQNLearner.opt')
+            self.t, self.n_updates = int(sd['state']['t']), int(sd['state']['n_updates'])
 
     def observe_step(self, replay, generator=None, updates=1):
         """One agent step of PFRL's DQN.observe(): count it, update once the buffer holds a minibatch, and copy

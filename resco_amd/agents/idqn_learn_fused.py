@@ -16,6 +16,7 @@ import ctypes as C
 import torch
 
 from ..sim import DQN_TENSORS, DQNConfig, DQNRing, DQNTensors, torch_stream
+from . import _state
 from .idqn_rollout import BatchedIDQN
 from .learn_fused import FusedLearnerBase
 
@@ -87,6 +88,24 @@ class FusedDQNLearner(FusedLearnerBase):
         """target <- parameters: device-to-device copies into the storages the library reads"""
         for k in DQN_TENSORS:
             getattr(self.target, k).copy_(getattr(self.net, k))
+
+    # ---- checkpoints (resco_amd/checkpoint.py): in place, the library has borrowed target, m and v; its step count goes back
+    # through rs_dqn_set_steps (the bias correction's t and the key of the next minibatch draw)
+    def signature(self):
+        return {'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}
+
+    def state_dict(self):
+        return {'weights': {'target': _state.module_tensors(self.target)},
+                'state': {'m': dict(self.m), 'v': dict(self.v), 't': int(self.t), 'steps': _state.fused_counter_state(self), 'seed': int(self.seed)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        _state.load_module(self.target, sd['weights']['target'], 'FusedDQNLearner.target')
+        if not weights_only:
+            st = sd['state']
+            _state.copy_dict_into(self.m, st['m'], 'FusedDQNLearner.m')
+            _state.copy_dict_into(self.v, st['v'], 'FusedDQNLearner.v')
+            _state.set_fused_counter(self, st['steps'], 'FusedDQNLearner')
+            self.t, self.seed = int(st['t']), int(st['seed']) & 0xFFFFFFFF
 
     def observe_step(self, replay, generator=None, updates=1):
         """One agent step of PFRL's DQN.observe(), in BatchedDQNLearner.observe_step's order: count it, copy the target network every

@@ -36,6 +36,17 @@ class BatchedIDQN(BatchedTrunk):
             self.load_head(s, m[7].weight, m[7].bias)
         return self
 
+    @torch.no_grad()
+    def to_reference_modules(self):
+        """The inverse of load_reference_modules: one reference_q_network(L_s, A_s) per signal (float32, on the CPU) holding signal
+        s's weights un-padded, e.g. for checkpoint.save_reference_idqn."""
+        with torch.random.fork_rng(devices=[]):         # (the constructors' initial draws are overwritten: the caller's generator stays)
+            mods = [reference_q_network(l, a) for l, a in zip(self.lanes, self.actions)]
+        for s, m in enumerate(mods):
+            self.export_trunk(s, m[0], m[3], m[5])
+            self.export_head(s, m[7])
+        return mods
+
     def forward(self, obs):
         """obs [N, S, Lmax, 5] (zero padded) -> Q [N, S, Amax] (padded actions = -inf)."""
         return self.head(self.features(obs))

@@ -27,6 +27,7 @@ import math
 import torch
 import torch.nn as nn
 
+from . import _state
 from .trunk import BatchedTrunk, fc1_row_mask
 
 
@@ -196,6 +197,18 @@ class BatchedPPOLearner:
         exp(logp_fp32 - logp_kernel) instead of exactly 1 (largest |difference| measured on a recorded segment: 1.4e-4 on cologne1,
         5.4e-4 on ingolstadt21, profiles/r08_ippo_device_rollout.txt); likewise V in the advantages is the kernel's value."""
         return self._fit(self.dataset_from_rollout(rollout, last_value, done), generator)
+
+    # ---- checkpoints (resco_amd/checkpoint.py): the optimizer's state is loaded in place
+    def signature(self):
+        return {'epochs': self.epochs, 'minibatch': self.minibatch, 'gamma': float(self.gamma), 'lambd': float(self.lambd)}
+
+    def state_dict(self):
+        return {'state': {'opt': _state.adam_state(self.opt), 'n_updates': int(self.n_updates)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        if not weights_only:
+            _state.load_adam_state(self.opt, sd['state']['opt'], 'BatchedPPOLearner.opt')
+            self.n_updates = int(sd['state']['n_updates'])
 
     def _fit(self, ds, generator=None):
         n = ds['act'].shape[0]

@@ -134,6 +134,22 @@ class DeviceRollout:
         assert [id(s) for s in sims] == [id(s) for s in self.sims], 'the rollout was allocated for other pipes'
         return self._segs
 
+    # ---- checkpoints (resco_amd/checkpoint.py): a segment spans episodes, so its filled slots are training state; in place
+    def signature(self):
+        return {'T': self.T, 'n_envs': [int(s.n_envs) for s in self.sims]}
+
+    def state_dict(self):
+        return {'state': {'pipes': [{k: p[k] for k in self.FIELDS} for p in self.pipes]}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        from . import _state
+        if weights_only:
+            return
+        if len(sd['state']['pipes']) != len(self.pipes):
+            raise ValueError('DeviceRollout: the checkpoint holds %d pipes, the rollout %d' % (len(sd['state']['pipes']), len(self.pipes)))
+        for i, (p, src) in enumerate(zip(self.pipes, sd['state']['pipes'])):
+            _state.copy_dict_into(p, src, 'DeviceRollout.pipes[%d]' % i)
+
     def cat(self, name):
         """[T, N, ...] over all pipes in order (the single pipe's own tensor, a copy otherwise)"""
         return self.pipes[0][name] if len(self.pipes) == 1 else torch.cat([p[name] for p in self.pipes], dim=1)

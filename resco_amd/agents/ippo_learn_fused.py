@@ -12,6 +12,7 @@ on what .grads holds -- are learn_fused.FusedLearnerBase's).  There is no CPU fa
 import torch
 
 from ..sim import PPO_TENSORS, PPOConfig, PPOTensors, torch_stream
+from . import _state
 from .ippo import BatchedIPPO, BatchedPPOLearner
 from .learn_fused import FusedLearnerBase
 
@@ -100,6 +101,24 @@ class FusedPPOLearner(FusedLearnerBase):
         if rc != 0:
             self._fail('rs_ppo_perm', rc)
         return perm
+
+    # ---- checkpoints (resco_amd/checkpoint.py): m and v in place (the library has borrowed them), the step count through
+    # rs_ppo_set_steps
+    def signature(self):
+        return {'epochs': self.epochs, 'minibatch': self.minibatch, 'gamma': float(self.gamma), 'lambd': float(self.lambd)}
+
+    def state_dict(self):
+        self._need_handle()
+        return {'state': {'m': dict(self.m), 'v': dict(self.v), 'steps': _state.fused_counter_state(self), 'seed': int(self.seed)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        if not weights_only:
+            self._need_handle()
+            st = sd['state']
+            _state.copy_dict_into(self.m, st['m'], 'FusedPPOLearner.m')
+            _state.copy_dict_into(self.v, st['v'], 'FusedPPOLearner.v')
+            _state.set_fused_counter(self, st['steps'], 'FusedPPOLearner')
+            self.seed = int(st['seed']) & 0xFFFFFFFF
 
     def update_from_rollout(self, rollout, last_value, done, generator=None, perm=None):
         """BatchedPPOLearner.update_from_rollout with the fused update: the same dataset (dataset_from_rollout: the recording and

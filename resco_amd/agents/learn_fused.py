@@ -12,7 +12,7 @@ from ..sim import load_library, torch_stream
 
 class FusedLearnerBase:
     NAME = None             # the learner's class name as its error texts give it
-    PREFIX = None           # 'rs_dqn' / 'rs_ppo': the symbols are PREFIX_create, _step, _steps, _destroy
+    PREFIX = None           # 'rs_dqn' / 'rs_ppo': the symbols are PREFIX_create, _step, _steps, _set_steps, _destroy
     TENSORS = None          # names of the parameters, in the order of the fields of
     TENSOR_SET = None       # the ctypes struct of one set of device pointers
     LOSS_SHAPE = ()         # .loss_out is float32 [S, *LOSS_SHAPE]

@@ -38,6 +38,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..sim import load_library, maxwave_tables, torch_stream
+from . import _state
 from .idqn_learn import linear_epsilon
 
 N_MOVEMENTS = 12
@@ -197,6 +198,17 @@ class FusedMPLight:
             raise RuntimeError('rs_mplight_set_device_weights failed (%d)' % rc)
         self._wdev = flat
 
+    # ---- checkpoints (resco_amd/checkpoint.py)
+    def state_dict(self):
+        return {'state': {'seed': int(self.seed)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        """list the network (and a fused learner) before the policy.  A policy that shares a learner's vector keeps sharing it --
+        the load wrote into that vector --; one on a create-time or re-packed copy re-packs the network on the device."""
+        if not weights_only:
+            self.seed = int(sd['state']['seed']) & 0xFFFFFFFF
+        self.refresh_on_device()
+
     def close(self):
         if getattr(self, '_h', None) is not None:
             self._lib.rs_mplight_destroy(self._h)
@@ -271,6 +283,16 @@ class MPLightReplay:
         self.stage(obs)
         self.commit(pair_index, rew, done)
 
+    def signature(self):
+        return dict(_state.ring_signature(self), width=int(self.obs.shape[-1]))
+
+    def state_dict(self, replay=True):
+        return _state.ring_state(self, replay)
+
+    def load_state_dict(self, sd, weights_only=False):
+        if not weights_only:
+            _state.load_ring_state(self, sd, 'MPLightReplay')
+
     def sample(self, batch_size, generator=None):
         """B transitions uniform over (slot with a successor, environment, signal): o [B, W], g [B] long, r [B], o2 [B, W], d [B]."""
         n_ok = self.count - 1
@@ -314,6 +336,20 @@ class MPLightLearner:
 
     def sync_target(self):
         self.target.load_state_dict(self.q.state_dict())
+
+    # ---- checkpoints (resco_amd/checkpoint.py): loaded in place
+    def signature(self):
+        return {'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}
+
+    def state_dict(self):
+        return {'weights': {'target': _state.module_tensors(self.target)},
+                'state': {'opt': _state.adam_state(self.opt), 't': int(self.t), 'n_updates': int(self.n_updates)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        _state.load_module(self.target, sd['weights']['target'], 'MPLightLearner.target')
+        if not weights_only:
+            _state.load_adam_state(self.opt, sd['state']['opt'], 'MPLightLearner.opt')
+            self.t, self.n_updates = int(sd['state']['t']), int(sd['state']['n_updates'])
 
     def observe_step(self, replay, generator=None):
         """One env-step of SharedDQN.batch_observe: the target copy every `target_update` env-steps (before the update, as PFRL

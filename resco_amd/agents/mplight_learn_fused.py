@@ -19,6 +19,7 @@ import ctypes as C
 import torch
 
 from ..sim import DQNConfig, MPLightRing, load_library, torch_stream
+from . import _state
 from .learn_fused import FusedLearnerBase
 from .mplight import FRAP
 
@@ -144,6 +145,26 @@ class FusedMPLightLearner(FusedLearnerBase):
     def sync_target(self):
         """target <- parameters: one device-to-device copy into the vector the library reads"""
         self.flat_target.copy_(self.flat)
+
+    # ---- checkpoints (resco_amd/checkpoint.py): the four flat vectors are loaded in place -- the library has borrowed them, the
+    # parameters of net and target are views of them and a policy may share .flat --; the step count goes back through
+    # rs_mplight_dqn_set_steps, so the handle has to exist (pass n_signals, or show the learner its ring first)
+    def signature(self):
+        return {'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}
+
+    def state_dict(self):
+        return {'weights': {'flat': self.flat, 'flat_target': self.flat_target},
+                'state': {'m': self._m, 'v': self._v, 't': int(self.t), 'steps': _state.fused_counter_state(self), 'seed': int(self.seed)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        _state.copy_into(self.flat, sd['weights']['flat'], 'FusedMPLightLearner.flat')
+        _state.copy_into(self.flat_target, sd['weights']['flat_target'], 'FusedMPLightLearner.flat_target')
+        if not weights_only:
+            st = sd['state']
+            _state.copy_into(self._m, st['m'], 'FusedMPLightLearner.m')
+            _state.copy_into(self._v, st['v'], 'FusedMPLightLearner.v')
+            _state.set_fused_counter(self, st['steps'], 'FusedMPLightLearner')
+            self.t, self.seed = int(st['t']), int(st['seed']) & 0xFFFFFFFF
 
     def observe_step(self, replay, generator=None):
         """One env-step in MPLightLearner.observe_step's order: count it, copy the target every ``target_update`` env-steps, then one

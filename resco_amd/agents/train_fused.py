@@ -51,6 +51,10 @@ class DeviceTrainer:
             raise ValueError('the environments (%d) are not the replay ring\'s (%d)' % (sum(e.n_envs for e in self.envs), replay.N))
         self.group = SimGroup([e.sim for e in self.envs])
 
+    def signature(self):
+        """what of the trajectory this object decides (resco_amd/checkpoint.py); it holds no counters of its own, so no state"""
+        return {'eps_start': self.eps_start, 'eps_end': self.eps_end, 'decay_steps': self.decay_steps, 'updates_per_step': self.updates_per_step}
+
     def epsilon(self, t):
         """the exploration rate of agent step t, as the loop evaluates it"""
         return linear_epsilon(t, self.eps_start, self.eps_end, self.decay_steps)
@@ -106,6 +110,19 @@ class DevicePPOTrainer:
         self.perm = torch.zeros(learner.epochs, T * N, dtype=torch.int32, device=dev)
         self.slot, self.t, self.updates = 0, 0, 0       # filled slots of the segment, env-steps and updates so far
 
+    # ---- checkpoints (resco_amd/checkpoint.py): a segment spans episodes, so where it stands is training state
+    def state_dict(self):
+        return {'state': {'done': self.done, 'slot': int(self.slot), 't': int(self.t), 'updates': int(self.updates)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        from . import _state
+        if not weights_only:
+            st = sd['state']
+            if not 0 <= int(st['slot']) < self.rollout.T:
+                raise ValueError('DevicePPOTrainer: slot %d lies outside a segment of %d' % (int(st['slot']), self.rollout.T))
+            _state.copy_into(self.done, st['done'], 'DevicePPOTrainer.done')
+            self.slot, self.t, self.updates = int(st['slot']), int(st['t']), int(st['updates'])
+
     def run(self, n_steps):
         """n_steps env-steps of training, enqueued by one call; asynchronous.  Advances the slot, the step and the update counter and
         the environment's step counter and returns done (the episode's horizon is reached)."""
@@ -146,6 +163,14 @@ class DeviceA2CTrainer:
         self.R_boot = torch.zeros(env.sim.n_envs, L.K, dtype=torch.float32, device=dev)
         self.ret = torch.zeros(env.sim.n_envs, L.K, dtype=torch.float32, device=dev)    # the episode's return: zero it at a reset
         self.t = 0                              # env-steps so far: the key of the next act
+
+    # ---- checkpoints (resco_amd/checkpoint.py): the key of the next act
+    def state_dict(self):
+        return {'state': {'t': int(self.t)}}
+
+    def load_state_dict(self, sd, weights_only=False):
+        if not weights_only:
+            self.t = int(sd['state']['t'])
 
     def run(self, n_steps):
         """n_steps env-steps of training, enqueued by one call; asynchronous.  Advances the step counter, the environment's step

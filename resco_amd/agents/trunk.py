@@ -78,6 +78,25 @@ class BatchedTrunk(nn.Module):
         self.fc3_b[s, :A] = bias.to(self.fc3_b)
 
     @torch.no_grad()
+    def export_trunk(self, s, conv, fc1, fc2):
+        """the inverse of load_trunk: the Conv2d and the two Linear modules of signal s's reference network <- signal s, un-padded"""
+        H, hs = self.lmax - 1, self.lanes[s] - 1
+        conv.weight.copy_(self.conv_w[s * 64:(s + 1) * 64])
+        conv.bias.copy_(self.conv_b[s * 64:(s + 1) * 64])
+        full = self.fc1_w[s].t().reshape(64, 64, H, 4)                # out, c, h, w
+        fc1.weight.copy_(full[:, :, :hs].reshape(64, 64 * hs * 4))
+        fc1.bias.copy_(self.fc1_b[s])
+        fc2.weight.copy_(self.fc2_w[s].t())
+        fc2.bias.copy_(self.fc2_b[s])
+
+    @torch.no_grad()
+    def export_head(self, s, linear):
+        """the inverse of load_head: weight [A_s, 64] and bias [A_s] of signal s's reference head <- fc3 of signal s"""
+        A = self.actions[s]
+        linear.weight.copy_(self.fc3_w[s, :, :A].t())
+        linear.bias.copy_(self.fc3_b[s, :A])
+
+    @torch.no_grad()
     def init_like_reference(self, seed=0):
         """PyTorch / PFRL default initialisation of every per-signal network (what an untrained agent starts from)."""
         g = torch.random.get_rng_state()

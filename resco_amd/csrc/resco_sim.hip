@@ -916,6 +916,13 @@ struct TrainHandle {
         return true;
     }
 };
+// rs_*_set_steps: the host-side counter alone (no launch, no synchronisation): what is enqueued afterwards sees step t + 1 / update_key t
+template <class H> static int train_set_steps(const char *name, H *p, int64_t t) {
+    if (!p) { g_create_err = std::string(name) + ": NULL handle"; return RS_EINVAL; }
+    if (t < 0) { g_create_err = std::string(name) + ": need t >= 0"; return RS_EINVAL; }
+    p->t = (long long)t;
+    return RS_OK;
+}
 template <class Handle> static void train_destroy(Handle *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
@@ -1072,6 +1079,7 @@ extern "C" int rs_ppo_perm(int32_t n, int32_t epochs, uint32_t seed, uint32_t up
 }
 
 extern "C" int64_t rs_ppo_steps(rs_ppo_handle p) { return p ? (int64_t)p->t : -1; }
+extern "C" int rs_ppo_set_steps(rs_ppo_handle p, int64_t t) { return train_set_steps("rs_ppo_set_steps", p, t); }
 
 // ---- The two DQN learners: what rs_dqn (IDQN) and rs_mplight_dqn (MPLight) share beside TrainHandle.  Each adds its table T and, as
 // overloads on its handle and ring type, what really differs: dqn_ring_refusal, dqn_batch, dqn_sample_launch / dqn_grad_launch /
@@ -1675,6 +1683,7 @@ extern "C" int rs_dqn_update(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t b
 }
 extern "C" int rs_dqn_sync_target(rs_dqn_handle p, void *stream) { return dqn_sync_target("rs_dqn_sync_target", p, stream); }
 extern "C" int64_t rs_dqn_steps(rs_dqn_handle p) { return p ? (int64_t)p->t : -1; }
+extern "C" int rs_dqn_set_steps(rs_dqn_handle p, int64_t t) { return train_set_steps("rs_dqn_set_steps", p, t); }
 
 extern "C" int rs_mplight_dqn_sample(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key,
                                      int32_t *idx_out, void *stream) {
@@ -1690,6 +1699,7 @@ extern "C" int rs_mplight_dqn_update(rs_mplight_dqn_handle p, const rs_mplight_r
 }
 extern "C" int rs_mplight_dqn_sync_target(rs_mplight_dqn_handle p, void *stream) { return dqn_sync_target("rs_mplight_dqn_sync_target", p, stream); }
 extern "C" int64_t rs_mplight_dqn_steps(rs_mplight_dqn_handle p) { return p ? (int64_t)p->t : -1; }
+extern "C" int rs_mplight_dqn_set_steps(rs_mplight_dqn_handle p, int64_t t) { return train_set_steps("rs_mplight_dqn_set_steps", p, t); }
 
 // ---- "does this policy fit this handle?" and "may this handle take part in a loop?": asked by rs_group_step, rs_group_rollout, the
 // three training loops and rs_fma2c_record.  Each returns NULL or the reason; the caller puts its own name in front.

@@ -34,10 +34,11 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_idqn_create', 'rs_idqn_act', 'rs_idqn_set_device_weights', 'rs_idqn_set_lanes', 'rs_idqn_destroy', 'rs_group_step',
                'rs_default_block', 'rs_mplight_create', 'rs_mplight_act', 'rs_mplight_set_device_weights', 'rs_mplight_destroy',
                'rs_ippo_act', 'rs_group_rollout', 'rs_ppo_gae',
-               'rs_ppo_create', 'rs_ppo_grad', 'rs_ppo_step', 'rs_ppo_fit', 'rs_ppo_steps', 'rs_ppo_destroy',
-               'rs_dqn_create', 'rs_dqn_sample', 'rs_dqn_grad', 'rs_dqn_step', 'rs_dqn_update', 'rs_dqn_steps', 'rs_dqn_destroy',
+               'rs_ppo_create', 'rs_ppo_grad', 'rs_ppo_step', 'rs_ppo_fit', 'rs_ppo_steps', 'rs_ppo_set_steps', 'rs_ppo_destroy',
+               'rs_dqn_create', 'rs_dqn_sample', 'rs_dqn_grad', 'rs_dqn_step', 'rs_dqn_update', 'rs_dqn_steps', 'rs_dqn_set_steps',
+               'rs_dqn_destroy',
                'rs_mplight_dqn_create', 'rs_mplight_dqn_sample', 'rs_mplight_dqn_grad', 'rs_mplight_dqn_step', 'rs_mplight_dqn_update',
-               'rs_mplight_dqn_steps', 'rs_mplight_dqn_destroy',
+               'rs_mplight_dqn_steps', 'rs_mplight_dqn_set_steps', 'rs_mplight_dqn_destroy',
                'rs_idqn_pack_weights', 'rs_dqn_sync_target', 'rs_mplight_dqn_sync_target', 'rs_group_train',
                'rs_ppo_perm', 'rs_ippo_pack_weights', 'rs_group_ppo_train', 'rs_info_kernel']
 
@@ -108,6 +109,8 @@ def bind(L):
         L.rs_ppo_fit.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp]
         L.rs_ppo_steps.argtypes = [vp]
         L.rs_ppo_steps.restype = C.c_int64
+        if hasattr(L, 'rs_ppo_set_steps'):      # (a host emulation may not have it)
+            L.rs_ppo_set_steps.argtypes = [vp, C.c_int64]
         L.rs_ppo_destroy.argtypes = [vp]
         L.rs_ppo_destroy.restype = None
     if hasattr(L, 'rs_dqn_create'):
@@ -118,6 +121,8 @@ def bind(L):
         L.rs_dqn_update.argtypes = [vp, vp, i32, u32, i32, vp, vp]
         L.rs_dqn_steps.argtypes = [vp]
         L.rs_dqn_steps.restype = C.c_int64
+        if hasattr(L, 'rs_dqn_set_steps'):      # (a host emulation may not have it)
+            L.rs_dqn_set_steps.argtypes = [vp, C.c_int64]
         L.rs_dqn_destroy.argtypes = [vp]
         L.rs_dqn_destroy.restype = None
     if hasattr(L, 'rs_mplight_dqn_create'):
@@ -128,6 +133,8 @@ def bind(L):
         L.rs_mplight_dqn_update.argtypes = [vp, vp, i32, u32, i32, vp, vp]
         L.rs_mplight_dqn_steps.argtypes = [vp]
         L.rs_mplight_dqn_steps.restype = C.c_int64
+        if hasattr(L, 'rs_mplight_dqn_set_steps'):      # (a host emulation may not have it)
+            L.rs_mplight_dqn_set_steps.argtypes = [vp, C.c_int64]
         L.rs_mplight_dqn_destroy.argtypes = [vp]
         L.rs_mplight_dqn_destroy.restype = None
     if hasattr(L, 'rs_group_train'):

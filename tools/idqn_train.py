@@ -10,7 +10,13 @@ as well (agents/train_fused.py: DeviceTrainer, rs_group_train), one call per epi
 
 Prints one JSON line per episode (mean episode return of rewards.wait_norm per signal, average trip delay as
 utils/readXML.py computes it, epsilon, env-steps/s including learning) and a final line comparing with the
-on-device random policy on the same demand.  Random-init weights, synthetic (rou.xml) demand."""
+on-device random policy on the same demand.  Random-init weights, synthetic (rou.xml) demand.
+
+Checkpoints (resco_amd/checkpoint.py), in every mode: --save PATH [--save-freq K] [--save-replay] writes the training state after every
+K-th episode and after the last (the replay ring only with --save-replay: it is the large part); --load PATH continues at the stored
+episode (`episodes` stays the planned total, so the epsilon schedule and the demand seeds go on where they stopped; bit-exact with the
+ring, a valid continuation without); --load PATH --eval loads the weights alone and runs the greedy evaluation; --stop-after K leaves
+after K episodes of the planned total, as a job that ran out of time would."""
 import json
 import os
 import sys
@@ -26,6 +32,7 @@ from resco_amd.agents.idqn_fused import FusedIDQN                               
 from resco_amd.agents.idqn_rollout import BatchedIDQN                                       # noqa: E402
 from resco_amd.agents.train_fused import DeviceTrainer                                      # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                                           # noqa: E402
+from resco_amd import checkpoint                                                            # noqa: E402
 
 
 def delay(env):
@@ -33,9 +40,25 @@ def delay(env):
     return float(env.sim.trip_delay().mean()), float(env.sim.stats()['arrived'].mean())
 
 
+def greedy_evaluation(env, policy, actions, steps, seeds):
+    """greedy episodes with the policy's present weights (no learning) -> {demand seed: average trip delay}"""
+    out = {}
+    for seed in seeds:
+        env.sim.set_seed(seed)
+        obs = env.reset()['drq_norm_f16']
+        for k in range(steps):
+            policy.act(obs, out=actions)
+            o, _, _, _ = env.step(None)
+            obs = o['drq_norm_f16']
+        out[seed] = round(delay(env)[0], 2)
+    return out
+
+
 def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_graph=True, replay_steps=0, eps_end=0.0, evaluate=True, quiet=False, seed=0, tls_expiry=True,
-         device_update=False, device_loop=False, chunk=0):
-    """device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one)"""
+         device_update=False, device_loop=False, chunk=0, save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0):
+    """device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
+    save / save_freq / save_replay / load / eval_only / stop_after: the checkpoint flags of the module docstring; a run that leaves
+    at stop_after returns (rows, None)."""
     device_update = device_update or device_loop
     rows = []
     env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0, tls_expiry=tls_expiry)
@@ -56,6 +79,18 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
     gen = torch.Generator(device='cuda').manual_seed(seed)
     decay = int(0.8 * episodes * steps)                 # the reference decays over config['steps'] agent steps
     trainer = DeviceTrainer(env, learner, policy, replay, 1.0, eps_end, decay, updates) if device_loop else None
+    # what a checkpoint holds (the network before the learner and the policy that read it) and what else shapes the trajectory
+    objects = dict(env=env, net=net, learner=learner, policy=policy, replay=replay)
+    if not device_update:
+        objects.update(gen=gen, default_gen=torch.cuda.default_generators[env.sim.device])     # (the graph-captured update draws from the default one)
+    hyper = dict(episodes=episodes, decay_steps=decay, updates_per_step=updates, eps_end=float(eps_end), seed=seed)
+    first_ep = 0
+    if load and eval_only:
+        rows = checkpoint.load(load, agent='IDQN', map_name=map_name, objects=dict(net=net, policy=policy), strict=False)['rows']
+        first_ep = episodes
+    elif load:
+        progress = checkpoint.load(load, agent='IDQN', map_name=map_name, objects=objects, hyper=hyper)
+        first_ep, rows = int(progress['episode']), list(progress['rows'])
 
     env.sim.set_seed(12345)                             # baseline: random policy on an evaluation demand seed
     env.reset()
@@ -64,7 +99,7 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
         env.step(None)
     rnd_delay, _ = delay(env)
 
-    for ep in range(episodes):
+    for ep in range(first_ep, episodes):
         env.sim.set_seed(1000 + ep + 7919 * seed)
         obs = env.reset()['drq_norm_f16']
         ret = torch.zeros(n, S, device='cuda')
@@ -81,7 +116,7 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
             rew = r['wait_norm']
             replay.commit(actions, rew, done)
             ret += rew
-            if use_graph and learner.n_updates == 0 and getattr(learner, '_graph', None) is None and len(replay) >= batch:
+            if use_graph and (learner.n_updates == 0 or first_ep > 0) and getattr(learner, '_graph', None) is None and len(replay) >= batch:
                 learner.capture_update(replay)      # [sample -> loss -> backward -> Adam] as one HIP graph
             if learner.observe_step(replay, gen, updates) is not None:
                 policy.refresh_on_device()
@@ -94,19 +129,21 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
                          env_steps_per_s=round(n * steps / dt), ms_per_step=round(dt / steps * 1e3, 3)))
         if not quiet:
             print(json.dumps(rows[-1]), flush=True)
+        write, stop = checkpoint.due(ep + 1, episodes, save, save_freq, stop_after)
+        if write:
+            checkpoint.save(save, agent='IDQN', map_name=map_name, objects=objects, hyper=hyper, replay=save_replay,
+                            progress=dict(episode=ep + 1, seed=seed, rows=rows))
+        if stop:
+            if device_update:
+                learner.close()
+            env.close()
+            return rows, None
 
     # greedy evaluation with the final weights (no further learning): on the baseline's seed and on the seed the last
     # training episode used - DQN keeps adapting within an episode, so a frozen copy can do worse than the last
     # training episodes did
     evals = {12345: None, 1000 + episodes - 1: None}
-    for seed in ((12345, 1000 + episodes - 1) if evaluate else ()):
-        env.sim.set_seed(seed)
-        obs = env.reset()['drq_norm_f16']
-        for k in range(steps):
-            policy.act(obs, out=actions)
-            o, _, _, _ = env.step(None)
-            obs = o['drq_norm_f16']
-        evals[seed] = round(delay(env)[0], 2)
+    evals.update(greedy_evaluation(env, policy, actions, steps, (12345, 1000 + episodes - 1) if evaluate or eval_only else ()))
     final = dict(map=map_name, envs=n, episodes=episodes, batch=batch, updates_per_step=updates, replay_steps=replay.T,
                  best_training_episode_delay_s=min(r['avg_delay_s'] for r in rows),
                  greedy_avg_delay_s=evals[12345], greedy_on_last_training_seed_s=evals[1000 + episodes - 1],
@@ -120,10 +157,10 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
 
 
 if __name__ == '__main__':
-    a = sys.argv[1:]
+    ckpt, a = checkpoint.tool_flags(sys.argv[1:])
     loop = a[:1] == ['--device-loop']
     dev = loop or a[:1] == ['--device-update']
     a = a[1:] if dev else a
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 12,
          int(a[3]) if len(a) > 3 else 256, int(a[4]) if len(a) > 4 else 1, (a[5] != 'nograph') if len(a) > 5 else True,
-         int(a[6]) if len(a) > 6 else 0, float(a[7]) if len(a) > 7 else 0.0, seed=int(a[8]) if len(a) > 8 else 0, device_update=dev, device_loop=loop)
+         int(a[6]) if len(a) > 6 else 0, float(a[7]) if len(a) > 7 else 0.0, seed=int(a[8]) if len(a) > 8 else 0, device_update=dev, device_loop=loop, **ckpt)

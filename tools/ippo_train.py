@@ -19,7 +19,13 @@ driven from Python, shuffle included, and gives the same bits.  Opt-in.
 
 Prints one JSON line per episode (average trip delay as utils/readXML.py computes it, env-steps/s including
 learning).  The reference's IPPO learns far more slowly than its IDQN (1400 published episodes); this tool shows the
-machinery end to end, not a converged policy.  Random-init weights, synthetic (rou.xml) demand."""
+machinery end to end, not a converged policy.  Random-init weights, synthetic (rou.xml) demand.
+
+Checkpoints (resco_amd/checkpoint.py), in every mode: --save PATH [--save-freq K] writes the training state -- the partly filled
+segment included, it spans episodes -- after every K-th episode and after the last; --load PATH continues at the stored episode
+(`episodes` stays the planned total, the demand seeds go on where they stopped); --load PATH --eval loads the weights alone and runs
+one episode without learning on demand seed 12345, printing its line; --stop-after K leaves after K episodes of the planned total, as
+a job that ran out of time would."""
 import json
 import os
 import sys
@@ -36,6 +42,7 @@ from resco_amd.agents.ippo_learn_fused import FusedPPOLearner         # noqa: E4
 from resco_amd.agents.train_fused import DevicePPOTrainer             # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                     # noqa: E402
 from resco_amd.sim import SimGroup                                    # noqa: E402
+from resco_amd import checkpoint                                      # noqa: E402
 
 
 def report(env, learner, ep, n, steps, dt):
@@ -44,7 +51,45 @@ def report(env, learner, ep, n, steps, dt):
                           env_steps_per_s=round(n * steps / dt), ms_per_step=round(dt / steps * 1e3, 3))), flush=True)
 
 
-def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, device_update=False, device_shuffle=False):
+class Checkpoints:
+    """the checkpoint flags of one run: load() before the first episode -> the episode to start at (`episodes` for --eval), after(ep)
+    behind every episode -> leave now"""
+
+    def __init__(self, map_name, episodes, seg, objects, weights, save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0):
+        self.map_name, self.episodes, self.objects, self.weights = map_name, episodes, objects, weights
+        self.hyper = dict(episodes=episodes, segment_steps=seg)
+        self.save, self.save_freq, self.path, self.eval_only, self.stop_after = save, save_freq, load, eval_only, stop_after
+
+    def load(self):
+        if self.path and self.eval_only:
+            checkpoint.load(self.path, agent='IPPO', map_name=self.map_name, objects=self.weights, strict=False)
+            return self.episodes
+        if self.path:
+            return int(checkpoint.load(self.path, agent='IPPO', map_name=self.map_name, objects=self.objects, hyper=self.hyper)['episode'])
+        return 0
+
+    def after(self, ep):
+        write, stop = checkpoint.due(ep + 1, self.episodes, self.save, self.save_freq, self.stop_after)
+        if write:
+            checkpoint.save(self.save, agent='IPPO', map_name=self.map_name, objects=self.objects, hyper=self.hyper, progress=dict(episode=ep + 1))
+        return stop
+
+
+def evaluation(env, act, map_name):
+    """--eval: one episode on demand seed 12345, actions drawn by the loaded policy, no learning; prints and returns its line"""
+    env.sim.set_seed(12345)
+    obs = env.reset()['drq_norm_f16']
+    for k in range(env.horizon_steps):
+        act(obs, k)
+        obs = env.step(None)[0]['drq_norm_f16']
+    torch.cuda.synchronize()
+    line = dict(map=map_name, agent='IPPO', eval_avg_delay_s=round(float(env.sim.trip_delay().mean()), 2),
+                arrived_per_env=round(float(env.sim.stats()['arrived'].mean()), 1))
+    print(json.dumps(line), flush=True)
+    return line
+
+
+def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, device_update=False, device_shuffle=False, **ckpt):
     env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0)
     steps = env.horizon_steps
     net = BatchedIPPO.from_scenario(env.scenario, dtype=torch.float32, device='cuda')
@@ -54,35 +99,40 @@ def main_device_rollout(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, 
     policy.refresh_on_device()
     grp, rec = SimGroup([env.sim]), DeviceRollout(seg, [env.sim])
     obs = env.tensor('drq_norm_f16')
-    done = [False] * seg
     gen = torch.Generator(device='cuda').manual_seed(0)
-    t_global, i, updates = 0, 0, 0
-    for ep in range(episodes):
+    c = checkpoint.Counters(done=[False] * seg, t_global=0, i=0, updates=0)     # the loop's own state: where the segment stands
+    ck = Checkpoints(map_name, episodes, seg, dict(env=env, net=net, learner=learner, policy=policy, rollout=rec, loop=c, gen=gen),
+                     dict(net=net, policy=policy), **ckpt)
+    for ep in range(ck.load(), episodes):
         env.sim.set_seed(1000 + ep)
         env.reset()
         torch.cuda.synchronize()                # (the rollout runs on the handle's own stream, the reset ran on torch's)
         t0 = time.perf_counter()
         k = 0
         while k < steps:
-            m = min(seg - i, steps - k)
-            grp.rollout(rec, policy.handle, t0=i, n_steps=m, step_key=t_global, seed=policy.seed)
-            k, i, t_global = k + m, i + m, t_global + m
-            done[i - 1] = env.advance(m)
-            if i == seg:
+            m = min(seg - c.i, steps - k)
+            grp.rollout(rec, policy.handle, t0=c.i, n_steps=m, step_key=c.t_global, seed=policy.seed)
+            k, c.i, c.t_global = k + m, c.i + m, c.t_global + m
+            c.done[c.i - 1] = env.advance(m)
+            if c.i == seg:
                 grp.sync()
-                kw = dict(perm=learner.device_perm(seg * n, updates)) if device_shuffle else dict(generator=gen)
-                learner.update_from_rollout(rec, policy.value(obs), torch.as_tensor(done, device='cuda'), **kw)
-                updates += 1
+                kw = dict(perm=learner.device_perm(seg * n, c.updates)) if device_shuffle else dict(generator=gen)
+                learner.update_from_rollout(rec, policy.value(obs), torch.as_tensor(c.done, device='cuda'), **kw)
+                c.updates += 1
                 policy.refresh_on_device()
                 torch.cuda.current_stream().synchronize()       # the next rollout reads the re-packed weights on another stream
-                done, i = [False] * seg, 0
+                c.done, c.i = [False] * seg, 0
         grp.sync()
         torch.cuda.synchronize()
         report(env, learner, ep, n, steps, time.perf_counter() - t0)
+        if ck.after(ep):
+            break
+    if ck.eval_only:
+        evaluation(env, lambda o, k: policy.act(o, step_key=k, out=env.tensor('actions')), map_name)
     env.close()
 
 
-def main_device_loop(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
+def main_device_loop(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, **ckpt):
     env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0)
     steps = env.horizon_steps
     net = BatchedIPPO.from_scenario(env.scenario, dtype=torch.float32, device='cuda')
@@ -90,8 +140,11 @@ def main_device_loop(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
     learner = FusedPPOLearner(net, minibatch=max(256, seg * n // mbs))
     policy = FusedIPPO(net, seed=3)
     policy.refresh_on_device()
-    trainer = DevicePPOTrainer(env, learner, policy, DeviceRollout(seg, [env.sim]))
-    for ep in range(episodes):
+    rollout = DeviceRollout(seg, [env.sim])
+    trainer = DevicePPOTrainer(env, learner, policy, rollout)
+    ck = Checkpoints(map_name, episodes, seg, dict(env=env, net=net, learner=learner, policy=policy, rollout=rollout, trainer=trainer),
+                     dict(net=net, policy=policy), **ckpt)
+    for ep in range(ck.load(), episodes):
         env.sim.set_seed(1000 + ep)
         env.reset()
         torch.cuda.synchronize()
@@ -99,11 +152,15 @@ def main_device_loop(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
         assert trainer.run(steps)               # the whole episode; a segment may span the reset
         torch.cuda.synchronize()
         report(env, learner, ep, n, steps, time.perf_counter() - t0)
+        if ck.after(ep):
+            break
+    if ck.eval_only:
+        evaluation(env, lambda o, k: policy.act(o, step_key=k, out=env.tensor('actions')), map_name)
     env.close()
     return trainer
 
 
-def main(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
+def main(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4, **ckpt):
     env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0)
     S, steps = env.n_signals, env.horizon_steps
     net = BatchedIPPO.from_scenario(env.scenario, dtype=torch.float32, device='cuda')
@@ -117,37 +174,43 @@ def main(map_name='cologne1', n=256, episodes=20, seg=30, mbs=4):
     rew_buf = torch.zeros(seg, n, S, dtype=torch.float32, device='cuda')
     done_buf = torch.zeros(seg, dtype=torch.bool, device='cuda')
     gen = torch.Generator(device='cuda').manual_seed(0)
-    t_global, i = 0, 0
-    for ep in range(episodes):
+    c = checkpoint.Counters(t_global=0, i=0, obs=obs_buf, act=act_buf, rew=rew_buf, done=done_buf)      # the loop's own state: the segment
+    ck = Checkpoints(map_name, episodes, seg, dict(env=env, net=net, learner=learner, policy=policy, loop=c, gen=gen), dict(net=net, policy=policy), **ckpt)
+    for ep in range(ck.load(), episodes):
         env.sim.set_seed(1000 + ep)
         obs = env.reset()['drq_norm_f16']
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for k in range(steps):
-            obs_buf[i].copy_(obs)
-            policy.act(obs, step_key=t_global, out=actions, sample=True)
+            obs_buf[c.i].copy_(obs)
+            policy.act(obs, step_key=c.t_global, out=actions, sample=True)
             o, r, done, _ = env.step(None)
-            act_buf[i].copy_(actions)
-            rew_buf[i].copy_(r['wait_norm'])
-            done_buf[i] = bool(done)
+            act_buf[c.i].copy_(actions)
+            rew_buf[c.i].copy_(r['wait_norm'])
+            done_buf[c.i] = bool(done)
             obs = o['drq_norm_f16']
-            t_global += 1
-            i += 1
-            if i == seg:
+            c.t_global += 1
+            c.i += 1
+            if c.i == seg:
                 learner.update(obs_buf, act_buf, rew_buf, done_buf, obs, generator=gen)
                 policy.refresh_on_device()
-                i = 0
+                c.i = 0
         torch.cuda.synchronize()
         report(env, learner, ep, n, steps, time.perf_counter() - t0)
+        if ck.after(ep):
+            break
+    if ck.eval_only:
+        evaluation(env, lambda o, k: policy.act(o, step_key=k, out=actions, sample=True), map_name)
     env.close()
 
 
 if __name__ == '__main__':
     flags = ('--device-rollout', '--device-update', '--device-shuffle', '--device-loop')
-    a = [x for x in sys.argv[1:] if x not in flags]
+    ckpt, rest = checkpoint.tool_flags(sys.argv[1:])
+    a = [x for x in rest if x not in flags]
     run = main_device_loop if '--device-loop' in sys.argv[1:] else (main_device_rollout if any(f in sys.argv[1:] for f in flags) else main)
     kw = dict(device_update=True) if '--device-update' in sys.argv[1:] and run is main_device_rollout else {}
     if '--device-shuffle' in sys.argv[1:] and run is main_device_rollout:       # (--device-update with the library loop's shuffles)
         kw = dict(device_update=True, device_shuffle=True)
     run(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 20,
-        int(a[3]) if len(a) > 3 else 30, int(a[4]) if len(a) > 4 else 4, **kw)
+        int(a[3]) if len(a) > 3 else 30, int(a[4]) if len(a) > 4 else 4, **kw, **ckpt)

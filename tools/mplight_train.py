@@ -10,7 +10,12 @@ resco_amd/agents/mplight.py).
 Prints one JSON line per episode (mean episode return of rewards.pressure per signal, average trip delay as utils/readXML.py
 computes it, epsilon, env-steps/s including learning) and a final line with the best training episode and the on-device random
 policy on the same demand.  --device-loop (implies --device-update): the loop itself in the library as well
-(agents/train_fused.py: DeviceTrainer, rs_group_train), one call per episode; the same rows.  `full`: MPLightFULL (states.mplight_full, demand_shape 4)."""
+(agents/train_fused.py: DeviceTrainer, rs_group_train), one call per episode; the same rows.  `full`: MPLightFULL (states.mplight_full, demand_shape 4).
+
+Checkpoints (resco_amd/checkpoint.py), in every mode: --save PATH [--save-freq K] [--save-replay] (the replay ring only with --save-replay: it is the large part; without it a resumed run is a valid continuation, not the same one) writes the training state after every K-th
+episode and after the last; --load PATH continues at the stored episode (`episodes` stays the planned total, so the schedules and the
+demand seeds go on where they stopped); --load PATH --eval loads the weights alone and runs one evaluation episode without learning on
+the baseline's demand seed; --stop-after K leaves after K episodes of the planned total, as a job that ran out of time would."""
 import json
 import os
 import sys
@@ -25,14 +30,28 @@ from resco_amd.agents.mplight import FusedMPLight, MPLightLearner, MPLightReplay
 from resco_amd.agents.mplight_learn_fused import FusedMPLightLearner                        # noqa: E402
 from resco_amd.agents.train_fused import DeviceTrainer                                      # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                                           # noqa: E402
+from resco_amd import checkpoint                                                            # noqa: E402
 
 
 def delay(env):
     return float(env.sim.trip_delay().mean()), float(env.sim.stats()['arrived'].mean())
 
 
-def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, seed=0, full=False, quiet=False, device_update=False, device_loop=False, chunk=0):
-    """device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one)"""
+def greedy_evaluation(env, policy, state, actions, steps, seed):
+    """one greedy episode with the policy's present weights (no learning) -> average trip delay"""
+    env.sim.set_seed(seed)
+    obs = env.reset()[state]
+    for k in range(steps):
+        policy.act(obs, out=actions)
+        obs = env.step(None)[0][state]
+    return round(delay(env)[0], 2)
+
+
+def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, seed=0, full=False, quiet=False, device_update=False, device_loop=False, chunk=0,
+         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0):
+    """device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
+    save / save_freq / save_replay / load / eval_only / stop_after: the checkpoint flags of the module docstring; a run that leaves
+    at stop_after returns (rows, None)."""
     device_update = device_update or device_loop
     state = 'mplight_full' if full else 'mplight'
     env = VecMultiSignal(map_name, n, states=(state,), rewards=('pressure',), seed=0, outputs=(state,))
@@ -52,6 +71,19 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
     gen = torch.Generator(device='cuda').manual_seed(seed)
     decay = int(0.8 * episodes * steps)     # the reference decays over config['steps'] env-steps
     trainer = DeviceTrainer(env, learner, policy, replay, 1.0, 0.0, decay) if device_loop else None
+    # what a checkpoint holds (the network before the learner and the policy that read it) and what else shapes the trajectory
+    agent = 'MPLightFULL' if full else 'MPLight'
+    objects = dict(env=env, net=net, learner=learner, policy=policy, replay=replay)
+    if not device_update:
+        objects['gen'] = gen
+    hyper = dict(episodes=episodes, decay_steps=decay, seed=seed)
+    first_ep, rows = 0, []
+    if load and eval_only:
+        rows = checkpoint.load(load, agent=agent, map_name=map_name, objects=dict(net=net, policy=policy), strict=False)['rows']
+        first_ep = episodes
+    elif load:
+        progress = checkpoint.load(load, agent=agent, map_name=map_name, objects=objects, hyper=hyper)
+        first_ep, rows = int(progress['episode']), list(progress['rows'])
 
     env.sim.set_seed(12345)
     env.reset()
@@ -60,8 +92,7 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
         env.step(None)
     rnd_delay, _ = delay(env)
 
-    rows = []
-    for ep in range(episodes):
+    for ep in range(first_ep, episodes):
         env.sim.set_seed(1000 + ep + 7919 * seed)
         obs = env.reset()[state]
         ret = torch.zeros(n, S, device='cuda')
@@ -88,8 +119,19 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
                          arrived_per_env=round(arrived, 1), updates=learner.n_updates, env_steps_per_s=round(n * steps / dt)))
         if not quiet:
             print(json.dumps(rows[-1]), flush=True)
+        write, stop = checkpoint.due(ep + 1, episodes, save, save_freq, stop_after)
+        if write:
+            checkpoint.save(save, agent=agent, map_name=map_name, objects=objects, hyper=hyper, replay=save_replay,
+                            progress=dict(episode=ep + 1, seed=seed, rows=rows))
+        if stop:
+            if device_update:
+                learner.close()
+            env.close()
+            return rows, None
     final = dict(map=map_name, agent='MPLightFULL' if full else 'MPLight', envs=n, episodes=episodes, batch=batch, replay_steps=replay.T,
                  seed=seed, best_training_episode_delay_s=min(r['avg_delay_s'] for r in rows), random_avg_delay_s=round(rnd_delay, 2))
+    if eval_only:
+        final['greedy_avg_delay_s'] = greedy_evaluation(env, policy, state, actions, steps, 12345)
     if not quiet:
         print(json.dumps(final), flush=True)
     if device_update:
@@ -99,10 +141,10 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
 
 
 if __name__ == '__main__':
-    a = sys.argv[1:]
+    ckpt, a = checkpoint.tool_flags(sys.argv[1:])
     device_loop = bool(a) and a[0] == '--device-loop'
     device_update = device_loop or (bool(a) and a[0] == '--device-update')
     a = a[1:] if device_update else a
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 30,
          int(a[3]) if len(a) > 3 else 256, int(a[4]) if len(a) > 4 else 2048, int(a[5]) if len(a) > 5 else 0,
-         full=len(a) > 6 and a[6] == 'full', device_update=device_update, device_loop=device_loop)
+         full=len(a) > 6 and a[6] == 'full', device_update=device_update, device_loop=device_loop, **ckpt)
