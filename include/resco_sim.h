@@ -540,6 +540,56 @@ int64_t rs_mplight_dqn_steps(rs_mplight_dqn_handle p);
 int rs_mplight_dqn_set_steps(rs_mplight_dqn_handle p, int64_t t);
 void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p);
 
+/* ---- MPLight on several maps: ONE shared FRAP trained on M replay rings at once (resco_amd/csrc/resco_frap_multi.h) ------------
+ * FRAP's parameter vector (1365 + 4 D floats) does not depend on a map's signal count or its number of phase pairs: it sees a map
+ * only through pairs [n_pairs][2] and a row's 12 movement demands.  rs_mplight_multi_* is rs_mplight_dqn_* over n_maps = 1 .. 8 maps,
+ * each with its own pairs, signal count and ring; the five vectors are caller-owned and borrowed exactly as rs_mplight_dqn_create
+ * borrows them, rs_mplight_ring and rs_dqn_config are reused as they are.  One policy per map pointed at params
+ * (rs_mplight_set_device_weights) acts on the updated weights without any copy.
+ * rs_mplight_multi_sample: the draw is uniform over ALL stored transitions of all maps that have a successor (one replay buffer
+ * shared by the maps would give the same): pool_m = (count_m - 1) n_envs_m n_signals_m, or 0 where count_m < 2; total = sum of the
+ * pools; for draw i < batch r = ((uint64) hash(seed ^ 0x7B1D5C33, update_key, i, 0, 3) << 32 | hash(.., 4)) % total; map m = the
+ * first with r < pool_0 + .. + pool_m, r' = r - the pools before it; s = r' % n_signals_m, e = (r' / n_signals_m) % n_envs_m, k =
+ * r' / (n_signals_m n_envs_m), t = (head_m - count_m + k) mod capacity_m.  idx_out (device int32 [batch][4] = (map, t, e, s)) holds
+ * the draws GROUPED by map, maps ascending, the draw order kept inside a map; counts_out (HOST int32 [n_maps]) the group sizes, which
+ * the library computes on the host from the same hash (every input is passed by value): no host synchronisation.
+ * rs_mplight_multi_grad: the gradient of the minibatch idx, whose rows are read BY GROUP -- rows counts[0] of map 0, then counts[1]
+ * of map 1, .. (counts: HOST int32 [n_maps], sum = batch); a row's map tag idx[i][0] is not read, so no table is indexed by a device
+ * value the host never saw.  Per row as rs_mplight_dqn_grad (t, e, s held inside the map's ring, act clamped into 0 .. n_pairs_m - 1,
+ * done cuts the bootstrap and the successor is not read), the target's max over ALL n_pairs_m outputs of the row's own map; loss =
+ * the mean over all `batch` rows of the Huber terms; loss_out: ONE device float or NULL.  A tile holds rows of one map, tiles run in
+ * group order: with n_maps = 1 every bit is rs_mplight_dqn_grad's.
+ * rs_mplight_multi_step / _steps / _set_steps / _sync_target: as rs_mplight_dqn_*.
+ * rs_mplight_multi_update: for j < n_updates: the draw with update_key = the step count so far into the handle's own index array,
+ * the gradient, the Adam step: four launches per update whatever n_maps is, all enqueued by one call.
+ * All calls are asynchronous on `stream` and create no stream, event or wait and use no asynchronous memcpy; every sum has one fixed
+ * order (no float atomics): the same state gives the same bits.  The gradient is evaluated in double and rounded once per element.
+ * Refusals (RS_EINVAL, text in rs_last_error(NULL), nothing launched): per ring what rs_mplight_dqn_* refuses of a ring or pointer
+ * (n_signals or width not map m's; capacity < 2; n_envs < 1; head or count outside the ring; an array that is not memory of the
+ * handle's device) -- except count < 2, which only empties that ring's pool --; total == 0; a pool >= 2^31; batch outside 1 ..
+ * max_batch; counts that do not sum to batch, or a negative count; n_updates < 1; a NULL handle or pointer; an index array that is
+ * not device memory; rs_mplight_multi_create: n_maps outside 1 .. 8 and, per map, what rs_mplight_dqn_create refuses. */
+typedef struct rs_mplight_multi *rs_mplight_multi_handle;
+typedef struct rs_mplight_map {
+    int32_t n_pairs;
+    const int32_t *pairs;        /* host [n_pairs][2] */
+    int32_t n_signals;
+} rs_mplight_map;
+int rs_mplight_multi_create(int32_t device_id, int32_t demand_shape, int32_t n_maps, const rs_mplight_map *maps /* [n_maps] */,
+                            const rs_dqn_config *config, float *params, const float *target, float *grads, float *m, float *v, int32_t max_batch,
+                            rs_mplight_multi_handle *out);
+int rs_mplight_multi_sample(rs_mplight_multi_handle p, const rs_mplight_ring *rings /* [n_maps] */, int32_t batch, uint32_t seed, uint32_t update_key,
+                            int32_t *idx_out, int32_t *counts_out, void *stream);
+int rs_mplight_multi_grad(rs_mplight_multi_handle p, const rs_mplight_ring *rings, const int32_t *idx, const int32_t *counts, int32_t batch,
+                          float *loss_out, void *stream);
+int rs_mplight_multi_step(rs_mplight_multi_handle p, void *stream);
+int rs_mplight_multi_update(rs_mplight_multi_handle p, const rs_mplight_ring *rings, int32_t batch, uint32_t seed, int32_t n_updates, float *loss_out,
+                            void *stream);
+int rs_mplight_multi_sync_target(rs_mplight_multi_handle p, void *stream);
+int64_t rs_mplight_multi_steps(rs_mplight_multi_handle p);
+int rs_mplight_multi_set_steps(rs_mplight_multi_handle p, int64_t t);
+void rs_mplight_multi_destroy(rs_mplight_multi_handle p);
+
 /* ---- the DQN training loop of IDQN and MPLight in one call (resco_amd/csrc/resco_group_train.h) -------------------------------
  * What the loops of tools/idqn_train.py and tools/mplight_train.py --device-update do per env-step in Python (policy.act,
  * replay.stage, env.step, replay.commit, ret += rew, learner.observe_step, policy.refresh_on_device: about thirty launches and four

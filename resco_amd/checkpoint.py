@@ -21,6 +21,11 @@ that names the field and both values.  strict=False (evaluation, fine-tuning): e
 networks' shapes must match and only weights are loaded.  Checkpoints are taken at an episode boundary: `save` refuses an
 environment inside an episode.  replay=False leaves the DQN ring out (ingolstadt21 x 1024 at 2048 slots is 7.5 GB); the loaded ring
 is then empty and the resumed run is a valid continuation, not the same one.
+
+    progress = load_frap_weights(path, net)
+
+takes FRAP weights ACROSS maps: a FRAP's tensors do not depend on its map, so the network of any MPLight, MPLightFULL or multi-map
+MPLight checkpoint loads into a FRAP of any number of phase pairs (only demand_shape and the tensor shapes are compared).
 """
 import os
 
@@ -166,6 +171,37 @@ def load(path, *, agent, map_name, objects, strict=True, hyper=None):
             _state.load_module(obj, sd['weights'], name)
         else:
             obj.load_state_dict(sd, weights_only=not strict)
+    return ck['progress']
+
+
+FRAP_AGENTS = ('MPLight', 'MPLightFULL', 'MPLightMulti', 'MPLightFULLMulti')
+
+
+def load_frap_weights(path, net):
+    """FRAP weights across maps: the network of any MPLight, MPLightFULL or multi-map MPLight checkpoint into `net`, a FRAP of ANY
+    number of phase pairs, in place (a net whose parameters are views of a learner's vector writes through to it).  FRAP's tensors
+    do not depend on the map, so only demand_shape and the tensor shapes are compared -- not oshape, which `load` refuses on.
+    Nothing is modified unless all of it matches.  Returns the file's progress dict."""
+    from .agents import _state
+    ck = torch.load(path, weights_only=True, map_location='cpu')
+    if not isinstance(ck, dict) or ck.get('format') != FORMAT:
+        raise _mismatch('format', ck.get('format') if isinstance(ck, dict) else type(ck).__name__, FORMAT)
+    theirs = ck['signature']
+    if theirs['agent'] not in FRAP_AGENTS:
+        raise _mismatch('agent', theirs['agent'], 'one of %s' % (FRAP_AGENTS,))
+    name = next((n for n in ('net', 'net0') if n in theirs['objects'] and 'weights' in ck['objects'].get(n, {})), None)
+    if name is None:
+        raise _mismatch('objects', theirs['objects'], "a FRAP network named 'net' or 'net0'")
+    d = theirs['fields'].get('%s.demand_shape' % name, '(absent)')
+    if _plain(d) != int(net.demand_shape):
+        raise _mismatch('%s.demand_shape' % name, d, int(net.demand_shape))
+    ours = {}
+    _walk({'weights': dict(net.state_dict())}, name, ours)
+    for k in sorted(set(ours) | {t for t in theirs['tensors'] if t.startswith(name + '/weights/')}):
+        a, b = theirs['tensors'].get(k, '(absent)'), ours.get(k, '(absent)')
+        if _plain(a) != _plain(b):
+            raise _mismatch(k, a, b)
+    _state.load_module(net, ck['objects'][name]['weights'], name)
     return ck['progress']
 
 

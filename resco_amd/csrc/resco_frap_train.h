@@ -147,7 +147,7 @@ RS_HD inline void frap_mv_forward(WP w, int D, const fpt_t *PE, int m, int bit, 
     }
 }
 // its backward from de: dpre = de (e > 0), dz = (LE[:, 4:]^T dpre) sd (1 - sd)
-template <class WP>
+template <int TAG = 0, class WP>
 RS_HD inline void frap_mv_backward(WP w, int D, const fpt_t de[FRAP_E], const fpt_t e[FRAP_E], const fpt_t sd[4], fpt_t dpre[FRAP_E], fpt_t dz[4]) {
     const FrapOff o(D);
 #pragma unroll
@@ -209,7 +209,7 @@ RS_HD inline fpt_t frap_item_forward(WP w, int D, const fpt_t *Ag, const fpt_t *
     return y.get();
 }
 // its backward from dy: dh = dy BM (h > 0), dx = H^T dh, drit = dx lc (the item's share of dR), dpx = dx R (lc > 0)
-template <class WP>
+template <int TAG = 0, class WP>
 RS_HD inline void frap_item_backward(WP w, int D, fpt_t dy, const fpt_t lc[FRAP_C], const fpt_t *Rc, const fpt_t *h, fpt_t dh[FRAP_C], fpt_t drit[FRAP_C],
                                      fpt_t dpx[FRAP_C]) {
     const FrapOff o(D);
@@ -228,6 +228,10 @@ RS_HD inline void frap_item_backward(WP w, int D, fpt_t dy, const fpt_t lc[FRAP_
 }
 
 // ------------------------------------------------------------------------------------------------ a tile's stage and its phases
+// The phases, the entries and the reduction below are called by the kernels of this file AND by those of resco_frap_multi.h, and each
+// takes a TAG: a caller instantiates its own copy (this file: TAG 0, the default).  The device build makes every function local, and
+// the compiler inlines a large local function for free only while it has ONE call site; a phase left as a real function takes its
+// weight pointer in vector registers, which FPT_UNIT cannot fence.  One copy per kernel keeps every copy at one call site.
 // The LDS image of a tile (the host build: a plain struct).  A phase is a function of (row r, lane j) that reads what earlier phases
 // left and writes its own lane's part; the kernel puts a barrier between two phases, the host build runs the lanes one after the
 // other.  Rows past the minibatch (ok = 0), lanes past P and the lane j = g hold zeros wherever an entry reads them.
@@ -253,6 +257,7 @@ RS_HD inline int frap_phase_of(float o0, int P) {
 }
 
 // the derived tables, value k < 144 of the stage
+template <int TAG = 0>
 RS_HD inline void fpt_prep(FrapStage &L, const float *w, const float *wt, int D, int k) {
     const int net = k / 72, kk = k - net * 72;
     const fpt_t v = frap_prep_once(net ? wt : w, D, kk);
@@ -261,7 +266,7 @@ RS_HD inline void fpt_prep(FrapStage &L, const float *w, const float *wt, int D,
 }
 
 // ---- the target: lane (r, j < P) A_j, B_j of the successor row under the target network
-template <class WP>
+template <int TAG = 0, class WP>
 RS_HD inline void fpt_target_ab(FrapStage &L, WP wt, int D, int P, const int32_t *pairs, int r, int j) {
     if (!L.boot[r] || j >= P) return;
     const float *ob = L.nxt[r];
@@ -281,7 +286,7 @@ RS_HD inline void fpt_target_ab(FrapStage &L, WP wt, int D, int P, const int32_t
     for (int c = 0; c < FRAP_C; ++c) { L.x[r][j][c] = A[c]; L.h[r][j][c] = B[c]; }
 }
 // lane (r, i < P): Q_i = sum_{j != i} y_ij, j ascending
-template <class WP>
+template <int TAG = 0, class WP>
 RS_HD inline void fpt_target_q(FrapStage &L, WP wt, int D, int P, const int32_t *pairs, int r, int i) {
     if (!L.boot[r] || i >= P) return;
     fpt_t q = 0.0;
@@ -293,6 +298,7 @@ RS_HD inline void fpt_target_q(FrapStage &L, WP wt, int D, int P, const int32_t 
     L.y[r][i] = q;
 }
 // lane (r, 0): tgt = rew + gamma max_i Q_i, or rew where the episode ended
+template <int TAG = 0>
 RS_HD inline void fpt_target_value(FrapStage &L, int P, double gamma, int r) {
     fpt_t t = L.rew[r];
     if (L.boot[r]) {
@@ -304,7 +310,7 @@ RS_HD inline void fpt_target_value(FrapStage &L, int P, double gamma, int r) {
 }
 
 // ---- the parameters' forward with saved activations.  Lane (r, m < 12): movement m
-template <class WP>
+template <int TAG = 0, class WP>
 RS_HD inline void fpt_mv_forward(FrapStage &L, WP w, int D, int P, const int32_t *pairs, int r, int m) {
     fpt_t sd[4] = {0.0, 0.0, 0.0, 0.0}, e[FRAP_E];
     int bit = 0;
@@ -323,7 +329,7 @@ RS_HD inline void fpt_mv_forward(FrapStage &L, WP w, int D, int P, const int32_t
     for (int u = 0; u < FRAP_E; ++u) L.e[r][m][u] = e[u];
 }
 // lane (r, j < P): pair_j, B_j (into dpx) and, on lane g, A_g
-template <class WP>
+template <int TAG = 0, class WP>
 RS_HD inline void fpt_pair_forward(FrapStage &L, WP w, int D, int P, const int32_t *pairs, int r, int j) {
     if (j >= P) return;
     const int a = pairs[2 * j], b = pairs[2 * j + 1];
@@ -341,7 +347,7 @@ RS_HD inline void fpt_pair_forward(FrapStage &L, WP w, int D, int P, const int32
     }
 }
 // lane (r, j < P): the item (g, j)
-template <class WP>
+template <int TAG = 0, class WP>
 RS_HD inline void fpt_item_forward(FrapStage &L, WP w, int D, int P, const int32_t *pairs, int r, int j) {
     if (j >= P) return;
     const int g = L.g[r];
@@ -360,6 +366,7 @@ RS_HD inline void fpt_item_forward(FrapStage &L, WP w, int D, int P, const int32
 }
 // lane (r, 0): delta = y - tgt with y = sum_{j != g} y_gj (j ascending); the Huber term and dy = d loss / d y under the mean over
 // `batch` rows: dqn_row_loss_grad's arithmetic (resco_dqn_train.h) in double
+template <int TAG = 0>
 RS_HD inline void fpt_row_loss(FrapStage &L, int P, int batch, int r) {
     L.dy[r] = 0.0; L.term[r] = 0.0;
     if (!L.ok[r]) return;
@@ -372,7 +379,7 @@ RS_HD inline void fpt_row_loss(FrapStage &L, int P, int batch, int r) {
     L.term[r] = ad < 1.0 ? 0.5 * delta * delta : ad - 0.5;
 }
 // lane (r, j < P): the item's backward; dpair_j = LC[:, 16:]^T dpx
-template <class WP>
+template <int TAG = 0, class WP>
 RS_HD inline void fpt_item_backward(FrapStage &L, WP w, int D, int P, int r, int j) {
     if (j >= P) return;
     fpt_t dh[FRAP_C], drit[FRAP_C], dpx[FRAP_C], dpair[FRAP_E];
@@ -384,7 +391,7 @@ RS_HD inline void fpt_item_backward(FrapStage &L, WP w, int D, int P, int r, int
         fpt_t lc[FRAP_C];
 #pragma unroll
         for (int c = 0; c < FRAP_C; ++c) lc[c] = L.drit[r][j][c];
-        frap_item_backward(w, D, L.dy[r], lc, L.R[0] + FRAP_C * L.comp[r][j], L.h[r][j], dh, drit, dpx);
+        frap_item_backward<TAG>(w, D, L.dy[r], lc, L.R[0] + FRAP_C * L.comp[r][j], L.h[r][j], dh, drit, dpx);
         frap_pair_backward(w, D, 1, dpx, dpair);
     }
 #pragma unroll
@@ -393,7 +400,7 @@ RS_HD inline void fpt_item_backward(FrapStage &L, WP w, int D, int P, int r, int
     for (int u = 0; u < FRAP_E; ++u) L.dpair[r][j][u] = dpair[u];
 }
 // lane (r, g): dA_g = sum_{j != g} dpx_j (j ascending), dpair_g = LC[:, :16]^T dA_g
-template <class WP>
+template <int TAG = 0, class WP>
 RS_HD inline void fpt_row_backward(FrapStage &L, WP w, int D, int P, int r) {
     const int g = L.g[r];
     fpt_t dA[FRAP_C], dpair[FRAP_E];
@@ -411,7 +418,7 @@ RS_HD inline void fpt_row_backward(FrapStage &L, WP w, int D, int P, int r) {
     for (int u = 0; u < FRAP_E; ++u) L.dpair[r][g][u] = dpair[u];
 }
 // lane (r, m < 12): de_m = the dpair of every pair that names m (twice where it names it twice), then the movement's backward
-template <class WP>
+template <int TAG = 0, class WP>
 RS_HD inline void fpt_mv_backward(FrapStage &L, WP w, int D, int P, const int32_t *pairs, int r, int m) {
     fpt_t de[FRAP_E], e[FRAP_E], sd[4], dpre[FRAP_E], dz[4];
 #pragma unroll
@@ -423,7 +430,7 @@ RS_HD inline void fpt_mv_backward(FrapStage &L, WP w, int D, int P, const int32_
 #pragma unroll
         for (int u = 0; u < FRAP_E; ++u) de[u] += L.dpair[r][i >> 1][u];
     }
-    frap_mv_backward(w, D, de, e, sd, dpre, dz);
+    frap_mv_backward<TAG>(w, D, de, e, sd, dpre, dz);
 #pragma unroll
     for (int u = 0; u < FRAP_E; ++u) L.e[r][m][u] = dpre[u];
 #pragma unroll
@@ -431,6 +438,7 @@ RS_HD inline void fpt_mv_backward(FrapStage &L, WP w, int D, int P, const int32_
 }
 
 // entry e of the tile: rows ascending, inside a row the items j or the movements m ascending
+template <int TAG = 0>
 RS_HD inline fpt_t frap_tile_entry(const FrapStage &L, int P, int D, int e) {
     FrapDot a(0.0);
     if (e < FG_HB) {
@@ -497,6 +505,7 @@ RS_HD inline fpt_t frap_reduce_entry(const fpt_t *part, int tiles, int e) {
 // applied once:
 //   PE[bit][u] = LE_b[u] + sum_t LE[u][t] sigmoid(p[bit][t])           -> lane_embedding.bias, lane_embedding.weight[:, :4], p.weight
 //   R[comp][c] = relu(RC_b[c] + sum_t RC[c][t] relu(RE[comp][t]))      -> relation_conv.bias, relation_conv.weight, relation_embedding.weight
+template <int TAG = 0>
 RS_HD inline float frap_grad_element(const float *w, int D, int i, const fpt_t *part, int tiles, const fpt_t *gPE, const fpt_t *gR) {
     const FrapOff o(D);
     FrapDot a(0.0);
@@ -538,6 +547,7 @@ RS_HD inline float frap_grad_element(const float *w, int D, int i, const fpt_t *
     return (float)frap_reduce_entry(part, tiles, entry);
 }
 // the mean loss of the minibatch
+template <int TAG = 0>
 RS_HD inline float frap_loss_mean(const fpt_t *part, int tiles, int B) {
     return (float)(frap_reduce_entry(part, tiles, FG_LOSS) / (fpt_t)B);
 }

@@ -117,6 +117,7 @@ __device__ unsigned long long *g_sec_prof;
 #include "resco_ppo_train.h"
 #include "resco_dqn_train.h"
 #include "resco_frap_train.h"
+#include "resco_frap_multi.h"
 #include "resco_group_train.h"
 #include "resco_ppo_loop.h"
 #include "resco_fma2c_train.h"
@@ -1581,11 +1582,13 @@ static void dqn_grad_launch(const rs_mplight_dqn *p, const FrapBatch &D, float *
     hipLaunchKernelGGL(frap_dqn_tile_kernel, dim3((D.B + FPT_TM - 1) / FPT_TM), dim3(FPT_T), 0, st, T, D);
     hipLaunchKernelGGL(frap_dqn_reduce_kernel, dim3((T.n + 255) / 256), dim3(256), 0, st, T, D.B, loss_out);
 }
-static void dqn_step_launch(rs_mplight_dqn *p, hipStream_t st) {
+// the Adam step and the target copy of a handle that holds a FrapTrainTab T (rs_mplight_dqn, rs_mplight_multi)
+template <class H> static void frap_step_launch(H *p, hipStream_t st) {
     const PpoStepConsts K = ppo_step_consts(p->cfg.lr, p->cfg.adam_eps, p->cfg.beta1, p->cfg.beta2, 0.0, p->t + 1);
     hipLaunchKernelGGL(frap_dqn_adam_kernel, dim3((p->T.n + 255) / 256), dim3(256), 0, st, p->T, K);
     if (hipPeekAtLastError() == hipSuccess) p->t += 1;      // a step that could not be launched is not counted
 }
+static void dqn_step_launch(rs_mplight_dqn *p, hipStream_t st) { frap_step_launch(p, st); }
 
 // target <- params (resco_group_train.h): one launch, the sources, destinations and element counts listed per learner
 static void sync_launch(const GtSync &Y, hipStream_t st) {
@@ -1603,11 +1606,12 @@ static void dqn_sync_launch(const rs_dqn *p, hipStream_t st) {
     for (int i = 0; i < 8; ++i) { Y.src[i] = T.par.p[i]; Y.dst[i] = T.tgt.p[i]; Y.n[i] = n[i]; }
     sync_launch(Y, st);
 }
-static void dqn_sync_launch(const rs_mplight_dqn *p, hipStream_t st) {
+template <class H> static void frap_sync_launch(const H *p, hipStream_t st) {
     GtSync Y{};
     Y.count = 1; Y.src[0] = p->T.par; Y.dst[0] = (float *)p->T.tgt; Y.n[0] = p->T.n;      // (the writable alias of the vector the create call took as const)
     sync_launch(Y, st);
 }
+static void dqn_sync_launch(const rs_mplight_dqn *p, hipStream_t st) { frap_sync_launch(p, st); }
 
 // ---- the DQN learners' entry points: one implementation for H = rs_dqn with Ring = rs_dqn_ring and H = rs_mplight_dqn with
 // Ring = rs_mplight_ring; `name`: the entry point, for the message
@@ -1700,6 +1704,158 @@ extern "C" int rs_mplight_dqn_update(rs_mplight_dqn_handle p, const rs_mplight_r
 extern "C" int rs_mplight_dqn_sync_target(rs_mplight_dqn_handle p, void *stream) { return dqn_sync_target("rs_mplight_dqn_sync_target", p, stream); }
 extern "C" int64_t rs_mplight_dqn_steps(rs_mplight_dqn_handle p) { return p ? (int64_t)p->t : -1; }
 extern "C" int rs_mplight_dqn_set_steps(rs_mplight_dqn_handle p, int64_t t) { return train_set_steps("rs_mplight_dqn_set_steps", p, t); }
+
+// ---- MPLight on several maps: the shared-DQN update over M rings (resco_frap_multi.h).  The five flat vectors are the caller's; the
+// library owns the per-tile partials, the maps' pair tables and the index array of rs_mplight_multi_update
+struct rs_mplight_multi : DqnHandle {
+    static constexpr const char *kCreate = "rs_mplight_multi_create";
+    FrapTrainTab T{};                   // (P, pairs and S are map 0's: the kernels take them from the minibatch's table)
+    int32_t n_maps = 0, P[FPM_MAPS] = {}, S[FPM_MAPS] = {};
+    const int32_t *pairs[FPM_MAPS] = {};
+    const void *rings_ok[FPM_MAPS][4] = {};     // per map, the ring arrays last found on this handle's device
+};
+
+extern "C" void rs_mplight_multi_destroy(rs_mplight_multi_handle p) { train_destroy(p); }
+
+extern "C" int rs_mplight_multi_create(int32_t device_id, int32_t demand_shape, int32_t n_maps, const rs_mplight_map *maps, const rs_dqn_config *cfg,
+                                       float *params, const float *target, float *grads, float *m, float *v, int32_t max_batch,
+                                       rs_mplight_multi_handle *out) {
+    if (!out) return RS_EINVAL;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_err = "no HIP device visible (this library has no CPU fallback)"; return RS_EHIP; }
+    if (device_id < 0 || device_id >= ndev || (demand_shape != 1 && demand_shape != 4) || n_maps < 1 || n_maps > FPM_MAPS || !maps || !cfg || max_batch < 1) {
+        g_create_err = "rs_mplight_multi_create: bad argument (a visible device, demand_shape 1 or 4, 1 <= n_maps <= 8, 1 <= max_batch)";
+        return RS_EINVAL;
+    }
+    if (!params || !target || !grads || !m || !v) { g_create_err = "rs_mplight_multi_create: a vector pointer is NULL"; return RS_EINVAL; }
+    for (int k = 0; k < n_maps; ++k) {
+        if (maps[k].n_pairs < 2 || maps[k].n_pairs > FRAP_PMAX || maps[k].n_signals < 1 || !maps[k].pairs) {
+            g_create_err = "rs_mplight_multi_create: every map needs 2 <= n_pairs <= 16, 1 <= n_signals and its pairs"; return RS_EINVAL;
+        }
+        for (int i = 0; i < 2 * maps[k].n_pairs; ++i)
+            if (maps[k].pairs[i] < 0 || maps[k].pairs[i] >= FRAP_MV) {
+                g_create_err = "rs_mplight_multi_create: a phase pair names a movement outside 0..11"; return RS_EINVAL;
+            }
+    }
+    if (hipSetDevice(device_id) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RS_EHIP; }
+    rs_mplight_multi *p = new (std::nothrow) rs_mplight_multi();
+    if (!p) return RS_ENOMEM;
+    p->device = device_id; p->max_batch = max_batch; p->cfg = *cfg; p->n_maps = n_maps;
+    FrapTrainTab &T = p->T;
+    T.par = params; T.tgt = target; T.grad = grads; T.m = m; T.v = v;
+    T.P = maps[0].n_pairs; T.D = demand_shape; T.S = maps[0].n_signals; T.n = FrapOff(demand_shape).n;
+    T.tiles_max = max_batch / FPT_TM + n_maps;      // whole tiles, and at most one ragged tile per map
+    T.gamma = cfg->gamma;
+    bool ok = p->alloc((void **)&T.part, (size_t)T.tiles_max * FG_N * sizeof(fpt_t)) && p->alloc((void **)&p->idx, (size_t)max_batch * 4 * sizeof(int32_t));
+    for (int k = 0; ok && k < n_maps; ++k) {
+        void *d = nullptr;
+        const size_t bytes = (size_t)maps[k].n_pairs * 2 * sizeof(int32_t);
+        ok = p->alloc(&d, bytes) && hipMemcpy(d, maps[k].pairs, bytes, hipMemcpyHostToDevice) == hipSuccess;
+        p->pairs[k] = (const int32_t *)d; p->P[k] = maps[k].n_pairs; p->S[k] = maps[k].n_signals;
+    }
+    if (!ok) {
+        g_create_err = "rs_mplight_multi_create: device allocation / upload failed";
+        (void)hipGetLastError();
+        train_destroy(p);
+        return RS_ENOMEM;
+    }
+    T.pairs = p->pairs[0];
+    *out = p;
+    return RS_OK;
+}
+
+// What every call that reads the rings checks before it launches anything: per ring what dqn_check asks of one (a ring with count < 2
+// is allowed here: its pool is empty and it is never drawn), then the pools.  Fills the draw's table Q and the rings of D.
+static int multi_check(rs_mplight_multi *p, const rs_mplight_ring *rings, int32_t batch, const char *name, FrapMultiPools &Q, FrapMultiBatch &D) {
+    auto refuse = [&](const std::string &why) { g_create_err = std::string(name) + ": " + why; return RS_EINVAL; };
+    if (!p) return refuse("NULL handle");
+    if (!rings) return refuse("the ring array is NULL");
+    if (batch < 1 || batch > p->max_batch) return refuse("need 1 <= batch <= max_batch of rs_mplight_multi_create");
+    Q = FrapMultiPools{}; D = FrapMultiBatch{};
+    Q.n_maps = D.n_maps = p->n_maps;
+    for (int k = 0; k < p->n_maps; ++k) {
+        const rs_mplight_ring *r = rings + k;
+        const std::string at = "map " + std::to_string(k) + ": ";
+        if (!r->obs || !r->act || !r->rew || !r->done) return refuse(at + "a ring pointer is NULL");
+        if (r->capacity < 2 || r->n_envs < 1) return refuse(at + "the ring needs capacity >= 2 and n_envs >= 1");
+        if (r->n_signals != p->S[k]) return refuse(at + "the ring's n_signals is not the map's");
+        if (r->width != 1 + FRAP_MV * p->T.D) return refuse(at + "the ring's width is not the handle's 1 + 12 demand_shape");
+        if (r->count < 0 || r->count > r->capacity || r->head < 0 || r->head >= r->capacity) return refuse(at + "head or count outside the ring");
+        const uint64_t pool = frap_multi_pool(r->n_envs, r->n_signals, r->count);
+        if (pool >= (1ull << 31)) return refuse(at + "the ring's pool (count - 1) n_envs n_signals must stay below 2^31");
+        const void *ring[4] = {r->obs, r->act, r->rew, r->done};
+        if (memcmp(ring, p->rings_ok[k], sizeof(ring)) != 0) {
+            for (const void *a : ring)
+                if (!dqn_on_device(a, p->device)) return refuse(at + "a ring array is not device memory of this handle's device (another device, or host memory)");
+            memcpy(p->rings_ok[k], ring, sizeof(ring));
+        }
+        Q.cum[k + 1] = Q.cum[k] + pool;
+        Q.T[k] = r->capacity; Q.N[k] = r->n_envs; Q.S[k] = r->n_signals; Q.head[k] = r->head; Q.count[k] = r->count;
+        D.map[k] = FrapMultiRing{r->obs, r->act, r->rew, r->done, p->pairs[k], r->capacity, r->n_envs, r->n_signals, r->width, p->P[k], 0, 0, 0};
+    }
+    if (Q.cum[p->n_maps] == 0) return refuse("total == 0: no ring holds a transition (a slot and its written successor, count >= 2)");
+    return RS_OK;
+}
+// the launches; the arguments have been checked.  counts: the group sizes of this draw (frap_multi_counts)
+static void multi_sample_launch(FrapMultiPools &Q, const int32_t *counts, int B, uint32_t seed, uint32_t key, int32_t *idx, hipStream_t st) {
+    for (int k = 0, row = 0; k < Q.n_maps; ++k) { Q.base[k] = row; row += counts[k]; }
+    hipLaunchKernelGGL(frap_multi_sample_kernel, dim3(1), dim3(FPM_CHUNK), 0, st, seed, key, Q, B, idx);
+}
+static void multi_grad_launch(const rs_mplight_multi *p, FrapMultiBatch &D, const int32_t *counts, const int32_t *idx, float *loss_out, hipStream_t st) {
+    const FrapTrainTab &T = p->T;
+    D.idx = idx;
+    const int tiles = frap_multi_layout(D, counts);     // <= tiles_max: sum(counts) <= max_batch has been checked
+    hipLaunchKernelGGL(frap_multi_tile_kernel, dim3(tiles), dim3(FPT_T), 0, st, T, D);
+    hipLaunchKernelGGL(frap_multi_reduce_kernel, dim3((T.n + 255) / 256), dim3(256), 0, st, T, tiles, D.B, loss_out);
+}
+static void dqn_step_launch(rs_mplight_multi *p, hipStream_t st) { frap_step_launch(p, st); }
+static void dqn_sync_launch(const rs_mplight_multi *p, hipStream_t st) { frap_sync_launch(p, st); }
+
+extern "C" int rs_mplight_multi_sample(rs_mplight_multi_handle p, const rs_mplight_ring *rings, int32_t batch, uint32_t seed, uint32_t update_key,
+                                       int32_t *idx_out, int32_t *counts_out, void *stream) {
+    FrapMultiPools Q; FrapMultiBatch D;
+    if (int rc = multi_check(p, rings, batch, "rs_mplight_multi_sample", Q, D)) return rc;
+    if (int rc = dqn_check_idx(p, idx_out, "idx_out", "rs_mplight_multi_sample")) return rc;
+    if (!counts_out) { g_create_err = "rs_mplight_multi_sample: counts_out is NULL"; return RS_EINVAL; }
+    frap_multi_counts(seed, update_key, batch, Q, counts_out);
+    return on_device(p->device, [&] { multi_sample_launch(Q, counts_out, batch, seed, update_key, idx_out, (hipStream_t)stream); });
+}
+extern "C" int rs_mplight_multi_grad(rs_mplight_multi_handle p, const rs_mplight_ring *rings, const int32_t *idx, const int32_t *counts, int32_t batch,
+                                     float *loss_out, void *stream) {
+    FrapMultiPools Q; FrapMultiBatch D;
+    if (int rc = multi_check(p, rings, batch, "rs_mplight_multi_grad", Q, D)) return rc;
+    if (int rc = dqn_check_idx(p, idx, "idx", "rs_mplight_multi_grad")) return rc;
+    if (!counts) { g_create_err = "rs_mplight_multi_grad: counts is NULL"; return RS_EINVAL; }
+    int64_t sum = 0;
+    for (int k = 0; k < p->n_maps; ++k) {
+        if (counts[k] < 0) { g_create_err = "rs_mplight_multi_grad: a negative count"; return RS_EINVAL; }
+        sum += counts[k];
+    }
+    if (sum != batch) { g_create_err = "rs_mplight_multi_grad: the counts do not sum to batch"; return RS_EINVAL; }
+    return on_device(p->device, [&] { multi_grad_launch(p, D, counts, idx, loss_out, (hipStream_t)stream); });
+}
+extern "C" int rs_mplight_multi_update(rs_mplight_multi_handle p, const rs_mplight_ring *rings, int32_t batch, uint32_t seed, int32_t n_updates,
+                                       float *loss_out, void *stream) {
+    FrapMultiPools Q; FrapMultiBatch D;
+    if (int rc = multi_check(p, rings, batch, "rs_mplight_multi_update", Q, D)) return rc;
+    if (n_updates < 1) { g_create_err = "rs_mplight_multi_update: need 1 <= n_updates"; return RS_EINVAL; }
+    return on_device(p->device, [&] {
+        const hipStream_t st = (hipStream_t)stream;
+        for (int j = 0; j < n_updates; ++j) {       // the launches of a stream run in order: update j + 1 may overwrite idx and the workspace
+            int32_t counts[FPM_MAPS];
+            frap_multi_counts(seed, (uint32_t)p->t, batch, Q, counts);
+            multi_sample_launch(Q, counts, batch, seed, (uint32_t)p->t, p->idx, st);
+            multi_grad_launch(p, D, counts, p->idx, loss_out, st);
+            dqn_step_launch(p, st);
+            if (hipPeekAtLastError() != hipSuccess) break;      // nothing more is enqueued behind a launch that failed
+        }
+    });
+}
+extern "C" int rs_mplight_multi_step(rs_mplight_multi_handle p, void *stream) { return dqn_step("rs_mplight_multi_step", p, stream); }
+extern "C" int rs_mplight_multi_sync_target(rs_mplight_multi_handle p, void *stream) { return dqn_sync_target("rs_mplight_multi_sync_target", p, stream); }
+extern "C" int64_t rs_mplight_multi_steps(rs_mplight_multi_handle p) { return p ? (int64_t)p->t : -1; }
+extern "C" int rs_mplight_multi_set_steps(rs_mplight_multi_handle p, int64_t t) { return train_set_steps("rs_mplight_multi_set_steps", p, t); }
 
 // ---- "does this policy fit this handle?" and "may this handle take part in a loop?": asked by rs_group_step, rs_group_rollout, the
 // three training loops and rs_fma2c_record.  Each returns NULL or the reason; the caller puts its own name in front.

@@ -39,6 +39,8 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_dqn_destroy',
                'rs_mplight_dqn_create', 'rs_mplight_dqn_sample', 'rs_mplight_dqn_grad', 'rs_mplight_dqn_step', 'rs_mplight_dqn_update',
                'rs_mplight_dqn_steps', 'rs_mplight_dqn_set_steps', 'rs_mplight_dqn_destroy',
+               'rs_mplight_multi_create', 'rs_mplight_multi_sample', 'rs_mplight_multi_grad', 'rs_mplight_multi_step', 'rs_mplight_multi_update',
+               'rs_mplight_multi_sync_target', 'rs_mplight_multi_steps', 'rs_mplight_multi_set_steps', 'rs_mplight_multi_destroy',
                'rs_idqn_pack_weights', 'rs_dqn_sync_target', 'rs_mplight_dqn_sync_target', 'rs_group_train',
                'rs_ppo_perm', 'rs_ippo_pack_weights', 'rs_group_ppo_train', 'rs_info_kernel']
 
@@ -137,6 +139,18 @@ def bind(L):
             L.rs_mplight_dqn_set_steps.argtypes = [vp, C.c_int64]
         L.rs_mplight_dqn_destroy.argtypes = [vp]
         L.rs_mplight_dqn_destroy.restype = None
+    if hasattr(L, 'rs_mplight_multi_create'):
+        L.rs_mplight_multi_create.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)]
+        L.rs_mplight_multi_sample.argtypes = [vp, vp, i32, u32, u32, vp, vp, vp]
+        L.rs_mplight_multi_grad.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+        L.rs_mplight_multi_step.argtypes = [vp, vp]
+        L.rs_mplight_multi_update.argtypes = [vp, vp, i32, u32, i32, vp, vp]
+        L.rs_mplight_multi_sync_target.argtypes = [vp, vp]
+        L.rs_mplight_multi_steps.argtypes = [vp]
+        L.rs_mplight_multi_steps.restype = C.c_int64
+        L.rs_mplight_multi_set_steps.argtypes = [vp, C.c_int64]
+        L.rs_mplight_multi_destroy.argtypes = [vp]
+        L.rs_mplight_multi_destroy.restype = None
     if hasattr(L, 'rs_group_train'):
         L.rs_idqn_pack_weights.argtypes = [vp, vp, vp]
         L.rs_dqn_sync_target.argtypes = [vp, vp]
@@ -276,6 +290,11 @@ class MPLightRing(C.Structure):
     """ctypes mirror of rs_mplight_ring (include/resco_sim.h): the device arrays of an MPLightReplay and its position"""
     _fields_ = [(k, C.c_void_p) for k in ('obs', 'act', 'rew', 'done')] + \
                [(k, C.c_int32) for k in ('capacity', 'n_envs', 'n_signals', 'width', 'head', 'count')]
+
+
+class MPLightMap(C.Structure):
+    """ctypes mirror of rs_mplight_map (include/resco_sim.h): one map of a multi-map MPLight learner"""
+    _fields_ = [('n_pairs', C.c_int32), ('pairs', C.c_void_p), ('n_signals', C.c_int32)]
 
 
 class SimGroup:
