@@ -64,7 +64,7 @@ typedef struct rs_scenario {
     const int32_t *route_start, *route_edge;
     const float *route_tlsdist;
     const float *route_cont;            /* [n_route_steps][kmax]: metres drivable along the route without a lane change (bestLanes) */
-    /* demand (identical in every environment) */
+    /* demand: the trips every environment of a handle runs until rs_set_demand gives the environments trip tables of their own */
     const int32_t *trip_depart, *trip_route, *trip_vtype, *trips_cum;
     const float *vtype_params;          /* [n_vtypes][10]: length minGap accel decel tau sigma maxSpeed sfMean sfDev emergencyDecel */
     /* controlled signals: program installed by Signal.__init__ (greens + generated yellows) */
@@ -250,6 +250,27 @@ int rs_timing_read(rs_handle h, float *total_ms, int32_t *launches);   /* syncs;
  * for whoever reads it), so a new seed without a reset would change the speed factors of the vehicles already on the network.
  * rs_snapshot stores the seed and rs_restore brings it back with the state. */
 int rs_set_seed(rs_handle h, uint32_t seed);
+
+/* ---- per-environment demand: K variants of the scenario's trip tables and a map environment -> variant ------------------
+ * The reference varies demand per run (MultiSignal(route=<prefix>) reads <prefix>_<run>.rou.xml, multi_signal.py:33-38,123-124); a
+ * batch does it per ENVIRONMENT: the handle keeps its scenario (net, routes, signals, capacity), and environment e inserts the trips
+ * of variants[env_variant[e]] instead of the scenario's.  A variant is three host arrays of the scenario's n_trips entries each
+ * (resco_amd/demand.py builds them); a trip that shall never enter is scheduled at horizon + 1.  RS_BUF_TRIP_LOG keeps its shape:
+ * row k of environment e is trip k of e's variant.  The library derives per variant what it derives for the scenario's trips (the
+ * backlog chains of the departure lanes, trips_cum) and copies the tables to the device.
+ * rs_set_demand is synchronous (it waits for the handle's stream and the stream of the last launch) and takes effect with the NEXT
+ * rs_reset: the vehicles on the network hold trip indices, so call it right before rs_reset(), as rs_set_seed.  n_variants = 0
+ * (variants and env_variant are then not read) returns the handle to its scenario's own trips.  Every successful call -- but the one
+ * that asks for no variants while none are in force, which does nothing -- starts a new demand GENERATION: rs_snapshot records it, and rs_restore refuses a snapshot taken under another one (RS_EINVAL).
+ * Refusals (RS_EINVAL, text in rs_last_error, nothing changed): a NULL handle or pointer; n_variants < 0; an env_variant entry outside
+ * 0 .. n_variants - 1; per variant: departs that decrease, are negative or above 65534, a route outside 0 .. n_routes - 1, a vehicle
+ * type outside 0 .. n_vtypes - 1, a most common vehicle type other than the scenario's (the queue unit of the lane occupancy is a
+ * constant of the handle, and the reference model derives it from the trips); more than 4 GiB of tables.  Everything a kernel
+ * indexes with is checked here, on the host.
+ * rs_demand_info: the number of variants in force (0: none) and, if env_variant_out is not NULL and there are variants, the map. */
+typedef struct rs_demand { const int32_t *trip_depart, *trip_route, *trip_vtype; } rs_demand;   /* host, n_trips of the handle's scenario each */
+int rs_set_demand(rs_handle h, int32_t n_variants, const rs_demand *variants, const int32_t *env_variant /* host [n_envs] */);
+int rs_demand_info(rs_handle h, int32_t *n_variants, int32_t *env_variant_out /* host [n_envs] or NULL */);
 
 /* in-kernel phase timers (development aid): enable, run steps, then read 16 accumulators of wall_clock64 ticks
  * (100 MHz).  Slots 0-2, 4-6, 11-14: one per phase of the step kernel, summed over all workgroups, barrier wait included

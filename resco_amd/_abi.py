@@ -1,4 +1,4 @@
-"""ctypes mirror of the C-ABI structs in include/resco_sim.h (rs_scenario / rs_params / rs_train / rs_rollout / rs_ppo_train / rs_fma2c_reward_table / rs_fma2c_train)."""
+"""ctypes mirror of the C-ABI structs in include/resco_sim.h (rs_scenario / rs_params / rs_demand / rs_train / rs_rollout / rs_ppo_train / rs_fma2c_reward_table / rs_fma2c_train)."""
 import ctypes as C
 
 import numpy as np
@@ -46,6 +46,11 @@ class ParamsStruct(C.Structure):
     _fields_ = [('seed', C.c_uint32), ('max_distance', C.c_float), ('sigma', C.c_float),
                 ('speed_dev', C.c_int32), ('fixed_program', C.c_int32), ('trip_log', C.c_int32), ('step_ratio', C.c_int32),
                 ('tls_hold', C.c_int32)]
+
+
+class DemandStruct(C.Structure):
+    """rs_demand: the trip tables of one demand variant (host int32 arrays of the scenario's n_trips entries each)"""
+    _fields_ = [('trip_depart', _I32P), ('trip_route', _I32P), ('trip_vtype', _I32P)]
 
 
 class TrainStruct(C.Structure):

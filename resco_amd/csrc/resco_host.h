@@ -4,6 +4,8 @@
 // supplies the qualifier macros, nothing here calls HIP.  The library wraps the bodies in kernels and uploads the tables; the
 // emulation calls the bodies in loops and keeps the tables in host memory.
 #pragma once
+#include <stdio.h>
+
 #include "resco_step.h"
 
 // ------------------------------------------------------------------------------------------------ reset / re-init (device or host)
@@ -26,7 +28,9 @@ RS_DEV void rs_reset_env(const KTab &T, const State &G, const KParams &P, int en
         else { ph = T.cold.tls_init_phase[s]; left = T.cold.tls_dur[T.cold.tls_dur_off[s] + ph]; }
         G.tls[(env * S + s) * TLS_W + 0] = ph; G.tls[(env * S + s) * TLS_W + 1] = left; G.tls[(env * S + s) * TLS_W + 2] = 0; G.tls[(env * S + s) * TLS_W + 3] = 0;
     }
-    for (int d = first; d < T.n_dep; d += stride) G.dep_next[(size_t)env * T.n_dep + d] = T.cold.dep_first[d];
+    // (every backlog starts at the first trip of the environment's OWN demand: rs_set_demand)
+    const uint16_t *dep_first = T.dem_ ? Demand<true, KTab>(T, env).dep_first() : T.cold.dep_first;
+    for (int d = first; d < T.n_dep; d += stride) G.dep_next[(size_t)env * T.n_dep + d] = dep_first[d];
     for (int i = first; i < (C + 31) / 32; i += stride) G.mail[(size_t)env * ((C + 31) / 32) + i] = 0u;
     for (int i = first; i < 4; i += stride) G.env[env * 4 + i] = 0;
     for (int i = first; i < ST_N; i += stride) G.stats[(size_t)env * ST_N + i] = 0;
@@ -219,6 +223,74 @@ static inline bool rs_scn_consts_of(const rs_scenario *sc, int ratio, ScnConsts 
     rs_scn_consts_from(PT, sc, ratio, c);
     return true;
 }
+// ---- demand variants (rs_set_demand): what a handle remembers of its scenario for them, and the check + packing of a call.  The library
+// uploads what pack() builds and points KTab::dem_ / dem_env_ at it; the emulation keeps it in host memory.
+struct DemandHost {
+    std::vector<int16_t> route_dep;     // RouteRec::dep_idx of every route
+    int n_trips = 0, n_dep = 1, n_vtypes = 0, horizon = 0, common_vt = 0;
+    uint32_t generation = 0;            // bumped by every successful rs_set_demand; a snapshot records it
+    int n_variants = 0;                 // in force (0: the scenario's own trips)
+    std::vector<int32_t> env_variant;   // [n_envs] in force
+    void init(const PackedTables &PT, const rs_scenario *sc) {
+        route_dep = PT.route_dep; n_trips = sc->n_trips; n_dep = PT.n_dep; n_vtypes = sc->n_vtypes; horizon = sc->horizon; common_vt = PT.common_vt;
+    }
+    // Checks a call's arguments (n_variants > 0) -- everything a kernel will index with -- and builds the variants' tables (`arena`:
+    // n_variants blocks in the layout of resco_tables.h: dem_off_*) and every environment's block offset.  Returns the refusal's text,
+    // empty: fine.  Changes nothing of *this: the caller commits (n_variants, env_variant, generation) once its copies succeeded.
+    std::string pack(int n_envs, int n_var, const rs_demand *variants, const int32_t *env_var, std::vector<char> &arena, std::vector<uint32_t> &env_off) const {
+        char msg[192];
+        if (!variants || !env_var) return "rs_set_demand: NULL variants / env_variant";
+        const uint32_t stride = dem_stride(n_trips, n_dep, horizon);
+        if ((uint64_t)stride * (uint64_t)n_var >= ((uint64_t)1 << 32)) return "rs_set_demand: the variants' tables exceed 4 GiB";
+        for (int e = 0; e < n_envs; ++e)
+            if (env_var[e] < 0 || env_var[e] >= n_var) {
+                snprintf(msg, sizeof(msg), "rs_set_demand: env_variant[%d] = %d is outside 0 .. %d", e, env_var[e], n_var - 1); return msg;
+            }
+        for (int v = 0; v < n_var; ++v) {
+            const rs_demand &V = variants[v];
+            if (!V.trip_depart || !V.trip_route || !V.trip_vtype) { snprintf(msg, sizeof(msg), "rs_set_demand: variant %d has a NULL table", v); return msg; }
+            for (int k = 0; k < n_trips; ++k) {
+                const int dp = V.trip_depart[k];
+                if (dp < 0 || dp > 65534 || (k > 0 && dp < V.trip_depart[k - 1])) {
+                    snprintf(msg, sizeof(msg), "rs_set_demand: variant %d, trip %d: depart %d (departs must be non-decreasing in 0 .. 65534)", v, k, dp); return msg;
+                }
+                if (V.trip_route[k] < 0 || V.trip_route[k] >= (int)route_dep.size()) {
+                    snprintf(msg, sizeof(msg), "rs_set_demand: variant %d, trip %d: route %d is outside 0 .. %d", v, k, V.trip_route[k], (int)route_dep.size() - 1); return msg;
+                }
+                if (V.trip_vtype[k] < 0 || V.trip_vtype[k] >= n_vtypes) {
+                    snprintf(msg, sizeof(msg), "rs_set_demand: variant %d, trip %d: vehicle type %d is outside 0 .. %d", v, k, V.trip_vtype[k], n_vtypes - 1); return msg;
+                }
+            }
+            const int cv = PackedTables::common_vtype(n_vtypes, n_trips, V.trip_vtype);
+            if (cv != common_vt) {
+                snprintf(msg, sizeof(msg), "rs_set_demand: variant %d: its most common vehicle type is %d, the scenario's is %d (the queue unit of the lane occupancy is a constant of the handle)", v, cv, common_vt);
+                return msg;
+            }
+        }
+        arena.assign((size_t)stride * (size_t)n_var, 0);
+        for (int v = 0; v < n_var; ++v) {
+            const rs_demand &V = variants[v];
+            char *b = arena.data() + (size_t)stride * (size_t)v;
+            int32_t *depart = (int32_t *)(b + dem_off_depart(n_trips, n_dep, horizon)), *cum = (int32_t *)(b + dem_off_cum(n_trips, n_dep, horizon));
+            if (n_trips) memcpy(depart, V.trip_depart, (size_t)n_trips * 4);
+            for (int t = 0, k = 0; t < horizon + 2; ++t) {      // trips_cum[t] = trips with depart <= t (scenario.py: compile_scenario)
+                while (k < n_trips && V.trip_depart[k] <= t) ++k;
+                cum[t] = k;
+            }
+            PackedTables::pack_trips(route_dep.data(), n_dep, n_trips, V.trip_route, V.trip_vtype, (uint16_t *)(b + dem_off_route(n_trips, n_dep, horizon)),
+                                     (uint8_t *)(b + dem_off_vtype(n_trips, n_dep, horizon)), (uint16_t *)(b + dem_off_next(n_trips, n_dep, horizon)),
+                                     (uint16_t *)(b + dem_off_first(n_trips, n_dep, horizon)));
+        }
+        env_off.resize((size_t)n_envs);
+        for (int e = 0; e < n_envs; ++e) env_off[(size_t)e] = stride * (uint32_t)env_var[e];
+        return std::string();
+    }
+    // the body of rs_demand_info behind the argument checks
+    void describe(int32_t *n_var, int32_t *env_variant_out) const {
+        if (n_var) *n_var = n_variants;
+        if (env_variant_out && n_variants > 0) memcpy(env_variant_out, env_variant.data(), env_variant.size() * 4);
+    }
+};
 // the parameters of a handle that every launch starts from (launch_step / run_step fill in the per-launch members)
 static inline KParams rs_kparams(const rs_params *p, int32_t env_base, int32_t n_envs) {
     KParams P{};

@@ -176,28 +176,30 @@ template <bool PROF> struct DevExec {
 };
 // Register budgets: 64 VGPRs (eight waves per SIMD: FOUR 512-thread workgroups per CU -- the default where the working memory of an
 // environment fits four times, round 6) and 80 VGPRs (three 512-thread workgroups per CU; `_v128` is the same code under a third
-// launch bound); CAP = the slot capacity as a compile-time constant (0: any).
-template <int CAP, bool PROF> __device__ __forceinline__ void rs_step_kernel_body(StepArgsPtr Ac, const KParams &P, const int32_t *__restrict__ actions) {
+// launch bound); CAP = the slot capacity as a compile-time constant (0: any).  DEM: every kernel exists twice -- for handles without
+// demand variants (false: the scenario's trip tables, no selection in the code) and for handles with them (true: rs_set_demand); the
+// profiling kernel decides at run time.
+template <int CAP, bool PROF, int DEM> __device__ __forceinline__ void rs_step_kernel_body(StepArgsPtr Ac, const KParams &P, const int32_t *__restrict__ actions) {
     if ((int)blockIdx.x >= P.n_envs) return;
     const StepArgs *A = (const StepArgs *)Ac;
 #ifdef RS_STUDY_SECTIONS
     if (threadIdx.x == 0) g_sec_prof = P.prof;
 #endif
     DevExec<PROF> ex{(int)blockDim.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), PROF ? P.prof : nullptr, (PROF && P.prof) ? wall_clock64() : 0ull};
-    rs_step_body<CAP>(ex, A->L, A->T, A->GP, A->O, P, actions, (int)blockIdx.x);
+    rs_step_body<CAP, DEM>(ex, A->L, A->T, A->GP, A->O, P, actions, (int)blockIdx.x);
 }
-template <int CAP>
+template <int CAP, bool DEM>
 __global__ void __launch_bounds__(1024, 8)
-rs_step_kernel_v64(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false>(Ac, P, actions); }
-template <int CAP>
+rs_step_kernel_v64(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false, DEM ? RS_DEM_ON : RS_DEM_OFF>(Ac, P, actions); }
+template <int CAP, bool DEM>
 __global__ void __launch_bounds__(768, 6)
-rs_step_kernel_v80(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false>(Ac, P, actions); }
-template <int CAP>
+rs_step_kernel_v80(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false, DEM ? RS_DEM_ON : RS_DEM_OFF>(Ac, P, actions); }
+template <int CAP, bool DEM>
 __global__ void __launch_bounds__(512, 4)
-rs_step_kernel_v128(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false>(Ac, P, actions); }
+rs_step_kernel_v128(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<CAP, false, DEM ? RS_DEM_ON : RS_DEM_OFF>(Ac, P, actions); }
 // the profiling build (rs_phase_profile / RS_STUDY_SECTIONS): any capacity, 80 VGPRs
 __global__ void __launch_bounds__(768, 6)
-rs_step_kernel_prof(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<0, true>(Ac, P, actions); }
+rs_step_kernel_prof(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_body<0, true, RS_DEM_ANY>(Ac, P, actions); }
 
 // ONE step kernel per shipped map, at the register budget rs_create chooses for it: F = ScnFix_<map> of the generated header
 // (resco_amd/build.py), every scalar of the tables and every offset of the working memory a literal (resco_step.h: KTabFix / LdsScn).
@@ -212,18 +214,18 @@ rs_step_kernel_prof(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actio
 #else
 #define RS_SCN_MAPS(X)
 #endif
-template <class F> __device__ __forceinline__ void rs_step_kernel_fix_body(StepArgsPtr Ac, const KParams &P, const int32_t *__restrict__ actions) {
+template <class F, bool DEM> __device__ __forceinline__ void rs_step_kernel_fix_body(StepArgsPtr Ac, const KParams &P, const int32_t *__restrict__ actions) {
     if ((int)blockIdx.x >= P.n_envs) return;
     const StepArgs *A = (const StepArgs *)Ac;
     DevExec<false> ex{(int)blockDim.x, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), nullptr, 0ull};
-    rs_step_body_fix<F>(ex, A->T, A->GP, A->O, P, actions, (int)blockIdx.x);
+    rs_step_body_fix<F, DEM>(ex, A->T, A->GP, A->O, P, actions, (int)blockIdx.x);
 }
-template <class F>
+template <class F, bool DEM>
 __global__ void __launch_bounds__(1024, 8)
-rs_step_kernel_fix_v64(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_fix_body<F>(Ac, P, actions); }
-template <class F>
+rs_step_kernel_fix_v64(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_fix_body<F, DEM>(Ac, P, actions); }
+template <class F, bool DEM>
 __global__ void __launch_bounds__(768, 6)
-rs_step_kernel_fix_v80(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_fix_body<F>(Ac, P, actions); }
+rs_step_kernel_fix_v80(StepArgsPtr Ac, KParams P, const int32_t *__restrict__ actions) { rs_step_kernel_fix_body<F, DEM>(Ac, P, actions); }
 
 // reset / fresh Signal objects / the static agents: the bodies are in resco_host.h (shared with the host emulation)
 __global__ void rs_reset_kernel(KTab T, State G, KParams P) { rs_reset_env(T, G, P, (int)blockIdx.x, (int)threadIdx.x, blockDim.x); }
@@ -251,6 +253,11 @@ struct rs_sim {
     ScnConsts consts{};             // every constant of this handle (resco_step.h): what decides whether a per-map kernel fits
     const FixKernel *fix = nullptr; // the per-map step kernel this handle launches (NULL: the generic kernel of its capacity)
     std::string kernel;             // the name of the step kernel launch_step launches (rs_info_kernel)
+    std::string kernel_dem;         // ... while demand variants are in force
+    DemandHost dem;                 // demand variants (rs_set_demand): what is in force, and what of the scenario their check needs
+    Lds layout{};                   // the layout of the working memory in the constant argument block (rs_set_demand writes the block again)
+    char *dem_arena = nullptr;      // device: the variants' tables (K.dem_)
+    uint32_t *dem_env = nullptr;    // device: [n_envs] block offsets (K.dem_env_)
     State G{};
     Out O{};
     KParams P{};
@@ -315,11 +322,20 @@ static int dev_upload(rs_sim *h, const Tp **dst, const Tp *src, size_t count) {
 typedef void (*step_kernel_fn)(StepArgsPtr, KParams, const int32_t *);
 static const int kStepCaps[] = {0, 128, 256, 512, 768, 896, 1024};
 // regs (a RegBudget): 64 VGPRs (blocks up to 1024 threads), 128 VGPRs (up to 512), 80 VGPRs (up to 768)
-#define RS_PICK(cap_) (regs == V128 ? rs_step_kernel_v128<cap_> : (regs == V80 ? rs_step_kernel_v80<cap_> : rs_step_kernel_v64<cap_>))
-static step_kernel_fn step_kernel_for(int regs, int capacity) {
+// dem: the kernel for handles with demand variants (rs_set_demand)
+#define RS_PICK_(cap_, dem_) (regs == V128 ? rs_step_kernel_v128<cap_, dem_> : (regs == V80 ? rs_step_kernel_v80<cap_, dem_> : rs_step_kernel_v64<cap_, dem_>))
+#ifdef RS_DEM_RUNTIME       // study build (the other side of the A/B in profiles/r21_demand_variants.txt): ONE kernel per shape that asks the tables
+#define RS_PICK(cap_) ((void)dem, RS_PICK_(cap_, false))
+#else
+#define RS_PICK(cap_) (dem ? RS_PICK_(cap_, true) : RS_PICK_(cap_, false))
+#endif
+static step_kernel_fn step_kernel_for(int regs, int capacity, bool dem) {
 #ifdef RS_ONE_CAP       // study builds (seconds instead of minutes to compile): one capacity, the 64- and the 80-VGPR kernel only
     (void)capacity;
-    return regs == V64 ? rs_step_kernel_v64<RS_ONE_CAP> : rs_step_kernel_v80<RS_ONE_CAP>;
+#ifndef RS_DEM_RUNTIME
+    if (dem) return regs == V64 ? rs_step_kernel_v64<RS_ONE_CAP, true> : rs_step_kernel_v80<RS_ONE_CAP, true>;
+#endif
+    return regs == V64 ? rs_step_kernel_v64<RS_ONE_CAP, false> : rs_step_kernel_v80<RS_ONE_CAP, false>;
 #else
     switch (capacity) {
         case 128: return RS_PICK(128);
@@ -335,18 +351,23 @@ static step_kernel_fn step_kernel_for(int regs, int capacity) {
 
 // the per-map kernels: the one of a map's register budget is the only one instantiated
 typedef bool (*scn_match_fn)(const ScnConsts &);
-struct FixKernel { const char *name; step_kernel_fn fn; scn_match_fn matches; };
-template <class F> static step_kernel_fn fix_kernel_fn() {
-    if constexpr (F::budget == V64) return rs_step_kernel_fix_v64<F>;
-    else return rs_step_kernel_fix_v80<F>;
+struct FixKernel { const char *name; step_kernel_fn fn, fn_dem; scn_match_fn matches; };      // fn_dem: for handles with demand variants
+template <class F, bool DEM> static step_kernel_fn fix_kernel_fn() {
+    if constexpr (F::budget == V64) return rs_step_kernel_fix_v64<F, DEM>;
+    else return rs_step_kernel_fix_v80<F, DEM>;
 }
+#ifdef RS_DEM_RUNTIME
+#define RS_FIX_DEM false
+#else
+#define RS_FIX_DEM true
+#endif
 static const FixKernel kFixKernels[] = {
 #define RS_FIX_ENTRY(m) RS_FIX_ENTRY_(m)
-#define RS_FIX_ENTRY_(m) {ScnFix_##m::budget == V64 ? "rs_step_kernel_fix_v64<" #m ">" : "rs_step_kernel_fix_v80<" #m ">", fix_kernel_fn<ScnFix_##m>(), scn_fix_matches<ScnFix_##m>},
+#define RS_FIX_ENTRY_(m) {ScnFix_##m::budget == V64 ? "rs_step_kernel_fix_v64<" #m ">" : "rs_step_kernel_fix_v80<" #m ">", fix_kernel_fn<ScnFix_##m, false>(), fix_kernel_fn<ScnFix_##m, RS_FIX_DEM>(), scn_fix_matches<ScnFix_##m>},
     RS_SCN_MAPS(RS_FIX_ENTRY)
 #undef RS_FIX_ENTRY
 #undef RS_FIX_ENTRY_
-    {nullptr, nullptr, nullptr}};
+    {nullptr, nullptr, nullptr, nullptr}};
 static const FixKernel *fix_kernel_for(const ScnConsts &c) {
     for (const FixKernel *k = kFixKernels; k->fn; ++k)
         if (k->matches(c)) return k;
@@ -430,6 +451,7 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
 #undef UP
     h->ratio = rs_step_ratio(p);
     rs_ktab_scalars(h->K, PT, sc, h->ratio);
+    h->dem.init(PT, sc);
     const int lmax = PT.lmax;
     h->P = rs_kparams(p, env_base, n_envs);
     const size_t N = (size_t)n_envs, NC = N * C, S = (size_t)sc->n_signals;
@@ -480,6 +502,7 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
             snprintf(nm, sizeof(nm), "rs_step_kernel_v%d<%d>", h->budget == V64 ? 64 : (h->budget == V80 ? 80 : 128), kcap);
             h->kernel = nm;
         }
+        h->kernel_dem = h->kernel.substr(0, h->kernel.size() - 1) + ", demand>";
     }
     {
         // the dynamic-LDS ceiling is an attribute of the kernel (per device), not of a launch: only ever raise it,
@@ -491,13 +514,15 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
         if (h->lds > cur) {
             for (int v = V64; v <= V80; ++v)
                 for (int cp : kStepCaps)        // every instantiation: the ceiling is per kernel function
-                    if (hipFuncSetAttribute((const void *)step_kernel_for(v, cp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess) {
+                    for (int dem = 0; dem < 2; ++dem)
+                        if (hipFuncSetAttribute((const void *)step_kernel_for(v, cp, dem != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess) {
+                            h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return fail(RS_EHIP);
+                        }
+            for (const FixKernel *k = kFixKernels; k->fn; ++k)
+                for (step_kernel_fn fn : {k->fn, k->fn_dem})
+                    if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess) {
                         h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return fail(RS_EHIP);
                     }
-            for (const FixKernel *k = kFixKernels; k->fn; ++k)
-                if (hipFuncSetAttribute((const void *)k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess) {
-                    h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return fail(RS_EHIP);
-                }
             if (hipFuncSetAttribute((const void *)rs_step_kernel_prof, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess) {
                 h->err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"; return fail(RS_EHIP);
             }
@@ -505,6 +530,7 @@ extern "C" int rs_create(const rs_scenario *sc, const rs_params *p, int32_t n_en
         }
     }
     {
+        h->layout = layout;
         StepArgs sa{h->K, h->G, h->O, layout, StateP(h->G)};
         if (!lds_fix_matches(sa.L, C)) { h->err = "the layout of the working memory does not match the kernel's literals (lds_carve / LdsFix)"; return fail(RS_EINVAL); }
         if ((rc = dev_alloc(h, &h->args, 1, false))) return fail(rc);
@@ -535,6 +561,8 @@ extern "C" void rs_destroy(rs_handle h) {
     if (h->stream) { (void)wait_idle(h); (void)hipStreamDestroy(h->stream); }
     for (auto &e : h->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (void *p : h->allocs) (void)hipFree(p);
+    if (h->dem_arena) (void)hipFree(h->dem_arena);
+    if (h->dem_env) (void)hipFree(h->dem_env);
     delete h;
 }
 
@@ -556,7 +584,9 @@ static int launch_step(rs_sim *h, hipStream_t st, int n_ticks, int do_fsm, int d
         HIPCHK(h, hipEventRecord(e0, st));
     }
     // (the in-kernel timers live in a kernel of their own: any capacity, 80 VGPRs, at most 768 threads)
-    const step_kernel_fn fn = (h->prof && h->block <= 768) ? (step_kernel_fn)rs_step_kernel_prof : (h->fix ? h->fix->fn : step_kernel_for(h->budget, h->K.capacity));
+    const bool dem = h->K.dem_ != nullptr;      // demand variants in force (rs_set_demand): the kernels that read an environment's own trip tables
+    const step_kernel_fn fn = (h->prof && h->block <= 768) ? (step_kernel_fn)rs_step_kernel_prof
+                                                            : (h->fix ? (dem ? h->fix->fn_dem : h->fix->fn) : step_kernel_for(h->budget, h->K.capacity, dem));
     hipLaunchKernelGGL(fn, dim3(h->n_envs), dim3(h->block), h->lds, st, (StepArgsPtr)h->args, P, (const int32_t *)h->actions);
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(e1, st));
@@ -696,7 +726,9 @@ extern "C" int rs_stats(rs_handle h, int64_t *host_out) {
     return rs_read_buffer(h, RS_BUF_STATS, host_out, (int64_t)h->n_envs * ST_N * 8);
 }
 
-struct Snapshot { std::vector<void *> ptrs; uint32_t seed = 0; };     // the seed: the speed factors are recomputed from (seed, env, trip) at every load
+// the seed: the speed factors are recomputed from (seed, env, trip) at every load; the demand generation: the vehicles hold trip indices
+// of the demand set (rs_set_demand) the snapshot was taken under
+struct Snapshot { std::vector<void *> ptrs; uint32_t seed = 0, dem_generation = 0; };
 // state AND the observation buffers: re-running observe would advance Signal.waiting_times
 static const int kSnapBufs[] = {RS_BUF_LANE_AGG, RS_BUF_DRQ_NORM, RS_BUF_PHASE, RS_BUF_MPLIGHT, RS_BUF_WAVE, RS_BUF_WAIT,
                                 RS_BUF_WAIT_NORM, RS_BUF_PRESSURE, RS_BUF_QUEUE_SUM, RS_BUF_QUEUE_MAX, RS_BUF_DRQ_NORM_F16,
@@ -710,7 +742,7 @@ extern "C" int rs_snapshot(rs_handle h, void **snap) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, wait_idle(h));
     Snapshot *S = new Snapshot();
-    S->seed = h->P.seed;
+    S->seed = h->P.seed; S->dem_generation = h->dem.generation;
     for (int b : kSnapBufs) {
         void *d = nullptr;
         if (h->bufs[b].bytes == 0) { S->ptrs.push_back(nullptr); continue; }
@@ -726,6 +758,7 @@ extern "C" int rs_restore(rs_handle h, const void *snap) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, wait_idle(h));
     const Snapshot *S = (const Snapshot *)snap;
+    if (S->dem_generation != h->dem.generation) { h->err = "rs_restore: the snapshot was taken under another demand set (rs_set_demand since)"; return RS_EINVAL; }
     size_t i = 0;
     for (int b : kSnapBufs) { if (h->bufs[b].bytes) HIPCHK(h, hipMemcpy(h->bufs[b].ptr, S->ptrs[i], h->bufs[b].bytes, hipMemcpyDeviceToDevice)); ++i; }
     h->P.seed = S->seed;        // the vehicles on the network keep the speed factors they were inserted with
@@ -776,8 +809,53 @@ extern "C" int rs_set_seed(rs_handle h, uint32_t seed) {
     return RS_OK;
 }
 
+// ---- per-environment demand (include/resco_sim.h).  Synchronous: nothing of the handle is in flight while the tables are exchanged.
+extern "C" int rs_set_demand(rs_handle h, int32_t n_variants, const rs_demand *variants, const int32_t *env_variant) {
+    if (!h) return RS_EINVAL;
+    if (n_variants < 0) { h->err = "rs_set_demand: n_variants < 0"; return RS_EINVAL; }
+    if (n_variants == 0 && h->dem.n_variants == 0) return RS_OK;       // nothing in force, nothing asked for: the demand (and its generation) stays
+    std::vector<char> arena;
+    std::vector<uint32_t> env_off;
+    if (n_variants > 0) {
+        const std::string msg = h->dem.pack(h->n_envs, n_variants, variants, env_variant, arena, env_off);
+        if (!msg.empty()) { h->err = msg; return RS_EINVAL; }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, wait_idle(h));
+    char *d_arena = nullptr;
+    uint32_t *d_env = nullptr;
+    if (n_variants > 0) {       // the new tables first: a failure leaves the handle as it was
+        if (hipMalloc((void **)&d_arena, arena.size()) != hipSuccess) { (void)hipGetLastError(); h->err = "rs_set_demand: hipMalloc failed"; return RS_ENOMEM; }
+        if (hipMalloc((void **)&d_env, env_off.size() * 4) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_arena); h->err = "rs_set_demand: hipMalloc failed"; return RS_ENOMEM; }
+        if (hipMemcpy(d_arena, arena.data(), arena.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_env, env_off.data(), env_off.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipFree(d_arena); (void)hipFree(d_env); h->err = "rs_set_demand: hipMemcpy failed"; return RS_EHIP;
+        }
+    }
+    KTab K = h->K;
+    K.dem_ = d_arena; K.dem_env_ = d_env;
+    StepArgs sa{K, h->G, h->O, h->layout, StateP(h->G)};
+    if (hipMemcpy(h->args, &sa, sizeof(sa), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(d_arena); (void)hipFree(d_env); h->err = "rs_set_demand: hipMemcpy(StepArgs) failed"; return RS_EHIP;
+    }
+    h->K = K;
+    if (h->dem_arena) (void)hipFree(h->dem_arena);
+    if (h->dem_env) (void)hipFree(h->dem_env);
+    h->dem_arena = d_arena; h->dem_env = d_env;
+    h->dem.n_variants = n_variants;
+    if (n_variants > 0) h->dem.env_variant.assign(env_variant, env_variant + h->n_envs);
+    else h->dem.env_variant.clear();
+    h->dem.generation += 1;
+    return RS_OK;
+}
+extern "C" int rs_demand_info(rs_handle h, int32_t *n_variants, int32_t *env_variant_out) {
+    if (!h) return RS_EINVAL;
+    h->dem.describe(n_variants, env_variant_out);
+    return RS_OK;
+}
+
 // (with the in-kernel timers switched on -- rs_phase_profile, blocks up to 768 threads -- launch_step launches rs_step_kernel_prof instead)
-extern "C" const char *rs_info_kernel(rs_handle h) { return h ? h->kernel.c_str() : ""; }
+extern "C" const char *rs_info_kernel(rs_handle h) { return h ? (h->K.dem_ ? h->kernel_dem.c_str() : h->kernel.c_str()) : ""; }
 extern "C" int rs_info(rs_handle h, int32_t *n_envs, int32_t *block_threads, int32_t *lds_bytes, int32_t *max_lanes_per_signal) {
     if (!h) return RS_EINVAL;
     rs_info_describe(h->n_envs, h->block, h->lds, h->K.lmax, n_envs, block_threads, lds_bytes, max_lanes_per_signal);

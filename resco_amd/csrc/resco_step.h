@@ -489,6 +489,27 @@ template <class F> RS_CARVE bool scn_fix_matches(const ScnConsts &c) {
 // as the other kernels take it, the outputs, the layout of the working memory and the field addresses of the state
 struct StepArgs { KTab T; State G; Out O; Lds L; StateP GP; };
 
+// ------------------------------------------------------------------------------------------------ the demand of an environment
+// The trip tables ONE environment reads: those of its variant (rs_set_demand; resco_tables.h: dem_off_*) or the scenario's.  Resolved
+// once at the entry of the step and of the reset from the environment's index -- wave-uniform: the offset of the variant's block is ONE
+// scalar load, and a table is the block's address plus an offset that follows from (n_trips, n_dep, horizon), literals to the kernel of
+// a shipped map.  DEM = 0 is the handle WITHOUT variants: every accessor is the scenario's table pointer, exactly what the phases
+// read before this view existed -- the step kernels are instantiated for either case (rs_step_body), so the no-variant kernels carry
+// nothing of the selection.  DEM = 1: variants.  DEM = 2: ONE body that asks the tables at every access (the run-time form: the other
+// side of the A/B that decided for the two instantiations, -DRS_DEM_RUNTIME, profiles/r21_demand_variants.txt).  TT: KTab or KTabFix<map>.
+template <int DEM, class TT> struct Demand {
+    const TT &T;
+    const uint32_t off;         // byte offset of this environment's block in T.dem() (no variants: 0)
+    RS_MEM Demand(const TT &T_, int env) : T(T_), off(DEM == 1 || (DEM == 2 && T_.dem()) ? rs_at(T_.dem_env(), env) : 0u) {}
+    template <class Tp> RS_MEM const Tp *at(uint32_t o) const { return (const Tp *)(T.dem() + (off + o)); }
+    RS_MEM const int32_t *trip_depart() const { if constexpr (DEM == 1) return at<int32_t>(dem_off_depart(T.n_trips, T.n_dep, T.horizon)); else if constexpr (DEM == 2) return T.dem() ? at<int32_t>(dem_off_depart(T.n_trips, T.n_dep, T.horizon)) : T.cold.trip_depart; else return T.cold.trip_depart; }
+    RS_MEM const int32_t *trips_cum() const { if constexpr (DEM == 1) return at<int32_t>(dem_off_cum(T.n_trips, T.n_dep, T.horizon)); else if constexpr (DEM == 2) return T.dem() ? at<int32_t>(dem_off_cum(T.n_trips, T.n_dep, T.horizon)) : T.cold.trips_cum; else return T.cold.trips_cum; }
+    RS_MEM const uint16_t *trip_next() const { if constexpr (DEM == 1) return at<uint16_t>(dem_off_next(T.n_trips, T.n_dep, T.horizon)); else if constexpr (DEM == 2) return T.dem() ? at<uint16_t>(dem_off_next(T.n_trips, T.n_dep, T.horizon)) : T.cold.trip_next; else return T.cold.trip_next; }
+    RS_MEM const uint16_t *trip_route() const { if constexpr (DEM == 1) return at<uint16_t>(dem_off_route(T.n_trips, T.n_dep, T.horizon)); else if constexpr (DEM == 2) return T.dem() ? at<uint16_t>(dem_off_route(T.n_trips, T.n_dep, T.horizon)) : T.trip_route(); else return T.trip_route(); }
+    RS_MEM const uint16_t *dep_first() const { if constexpr (DEM == 1) return at<uint16_t>(dem_off_first(T.n_trips, T.n_dep, T.horizon)); else if constexpr (DEM == 2) return T.dem() ? at<uint16_t>(dem_off_first(T.n_trips, T.n_dep, T.horizon)) : T.cold.dep_first; else return T.cold.dep_first; }
+    RS_MEM const uint8_t *trip_vtype() const { if constexpr (DEM == 1) return at<uint8_t>(dem_off_vtype(T.n_trips, T.n_dep, T.horizon)); else if constexpr (DEM == 2) return T.dem() ? at<uint8_t>(dem_off_vtype(T.n_trips, T.n_dep, T.horizon)) : T.trip_vtype(); else return T.trip_vtype(); }
+};
+
 #ifndef RS_LAYOUT_ONLY      // (a host-only includer that wants the layout and the constants alone -- resco_scn_consts.cpp -- stops here: what
                             //  follows needs the includer's atomics and working memory)
 // The tables and the working memory as a kernel of ONE MAP sees them: the phases are written against `T.<scalar>`, `T.<table>()`,
@@ -515,6 +536,8 @@ template <class F> struct KTabFix {
     RS_MEM const RouteRec *routes() const { return K.routes(); }
     RS_MEM const uint16_t *trip_route() const { return K.trip_route(); }
     RS_MEM const uint8_t *trip_vtype() const { return K.trip_vtype(); }
+    RS_MEM const char *dem() const { return K.dem(); }
+    RS_MEM const uint32_t *dem_env() const { return K.dem_env(); }
 };
 template <class F> struct LdsScn {
 #define X(n, tp) CPtr<tp, F::o_##n> n;
@@ -1336,12 +1359,12 @@ template <class TT, class LT, class GT> RS_DEV int phase_lc_decide(const TT &T, 
 
 // C: does the oldest waiting trip of departure lane d get onto the network in tick t?  The space on its lane is judged
 // AFTER this tick's move of the vehicles that are on it now -- their next speeds are known (oracle: insertion_check)
-template <class TT, class LT> RS_DEV bool phase_insert_decide(const TT &T, const LT &L, const Grid &grid, int t, int d) {
+template <class TT, class DT, class LT> RS_DEV bool phase_insert_decide(const TT &T, const DT &D, const LT &L, const Grid &grid, int t, int d) {
     if ((int)L.dep_t[d] > t) return false;           // nothing due on this lane (the common case: no global access)
     const int k = L.dep[d];
     // (one 8-byte record per departure lane instead of lane id -> lane record: the two loads of this check are independent)
     const DepInfo LR = rec_load8(T.cold.dep_info, d);
-    const float *vt = L.vtp + rs_at(T.trip_vtype(), k) * VT_COLS;
+    const float *vt = L.vtp + rs_at(D.trip_vtype(), k) * VT_COLS;
     const float mypos = vt[VT_LENGTH] < LR.len ? vt[VT_LENGTH] : LR.len;
     // only vehicles with pos - length < mypos + minGap can be in the way
     const int nc = (int)(LR.len * L.cell_inv) + 1;      // lane_cells(L, )
@@ -1384,9 +1407,15 @@ struct ExecInline {};
 
 // ------------------------------------------------------------------------------------------------ the step
 // CAP: the slot capacity as a compile-time constant (0: read it from the tables at run time)
-template <int CAP, class Exec, class LT, class TT, class GT>
+// DEM: the handle has demand variants, the trip tables are those of this environment's variant (Demand above)
+template <int CAP, bool DEM, class Exec, class LT, class TT, class GT>
 RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const TT &T, const GT &G, const Out &O, const KParams &P,
                             const int32_t *actions, int env) {
+#ifdef RS_DEM_RUNTIME       // (study build: the run-time form in every kernel, whatever DEM says)
+    const Demand<2, TT> D(T, env);
+#else
+    const Demand<DEM, TT> D(T, env);
+#endif
     const int B = ex.B;
     const int C = CAP ? CAP : T.capacity, S = T.n_signals, NO = T.n_obs;
     const int genv = P.env_base + env;
@@ -1406,7 +1435,7 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const TT &T, const GT &G, con
         for (int i = tid; i < T.n_dep; i += B) {
             const int k = G.dep_next[(size_t)env * T.n_dep + i];
             L.dep[i] = (uint16_t)k;
-            L.dep_t[i] = k == (int)TRIP_NONE ? (uint16_t)0xFFFF : (uint16_t)T.cold.trip_depart[k];
+            L.dep_t[i] = k == (int)TRIP_NONE ? (uint16_t)0xFFFF : (uint16_t)D.trip_depart()[k];
         }
         for (int i = tid; i < S; i += B) {
             const int ph = G.tls[(env * S + i) * TLS_W + 0];
@@ -1427,13 +1456,13 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const TT &T, const GT &G, con
             Aux ax; ax.lane = ln; ax.rq = 0; ax.nlink = NLINK_NONE; ax.swait = 0;
             if (ln == LANE_NONE) { L.aux[s] = ax; L.node[s].trip = TRIP_NONE; continue; }
             const float sp = G.speed()[eo + s], x = G.pos()[eo + s];
-            const int rq = (int)T.routes()[T.trip_route()[tr]].start + (int)G.cursor()[eo + s];
+            const int rq = (int)T.routes()[D.trip_route()[tr]].start + (int)G.cursor()[eo + s];
             const LaneRec LR0 = rec_load16(T.lanes(), ln);
             ax.rq = (uint16_t)rq;
             ax.nlink = cache_link(T, LR0, ln, rq, tr);
             ax.swait = G.swait()[eo + s];
             L.aux[s] = ax;
-            Node nn; nn.pos = x; nn.speed = sp; nn.trip = tr; nn.vt = T.trip_vtype()[tr];
+            Node nn; nn.pos = x; nn.speed = sp; nn.trip = tr; nn.vt = D.trip_vtype()[tr];
             // the speed factor is a function of (seed, environment, trip): recomputed here (four hashes per vehicle and ENV-STEP) instead of
             // read back -- 4 B per slot and step less from HBM; RS_BUF_VEH_SF is written at the insertion, for whoever reads it
             nn.fl = 0; nn.sfq = (uint16_t)speed_factor_q(P, genv, tr, L.vtp + nn.vt * VT_COLS);
@@ -1544,7 +1573,7 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const TT &T, const GT &G, con
                 if (st) { const unsigned long long m = st * 0xFFFFull; *q = (w & ~m) | ((0x07FF07FF07FF07FFull | grid_tag4(gold)) & m); }
             }
             for (int d = B - 1 - tid; d < T.n_dep; d += B)
-                if (phase_insert_decide(T, L, gold, t, d)) rs_atomic_or(&L.insm[d >> 5], 1u << (d & 31));
+                if (phase_insert_decide(T, D, L, gold, t, d)) rs_atomic_or(&L.insm[d >> 5], 1u << (d & 31));
             if (more)
                 for (int sg = B - 1 - tid; sg < S; sg += B) tls_begin_of_tick(T, L, P, sg, tick + 1);
             if (tid == 0) {
@@ -1586,9 +1615,9 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const TT &T, const GT &G, con
                         const int s = nth_free_slot(L, C, rank);
                         if (s < 0) continue;
                         const int k = L.dep[d];
-                        const int v = rs_at(T.trip_vtype(), k);
+                        const int v = rs_at(D.trip_vtype(), k);
                         const float *vt = L.vtp + v * VT_COLS;
-                        const RouteRec RR = rec_load16(T.routes(), T.trip_route()[k]);
+                        const RouteRec RR = rec_load16(T.routes(), D.trip_route()[k]);
                         const LaneRec LRd = rec_load16(T.lanes(), RR.depart_lane);
                         const int sfq = speed_factor_q(P, genv, k, vt);
                         const float sfn = sf_of(sfq);
@@ -1603,15 +1632,15 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const TT &T, const GT &G, con
                         G.sf()[eo + s] = sfn; G.tloss()[eo + s] = 0.0f; G.cooplead(0)[eo + s] = COOP_NONE; G.cooplead(1)[eo + s] = COOP_NONE; G.coop(0)[eo + s] = COOP_NONE; G.coop(1)[eo + s] = COOP_NONE;
                         G.rwait()[eo + s] = 0; G.owner()[eo + s] = OWNER_NONE; G.depart()[eo + s] = (uint16_t)(t + 1); G.accel()[eo + s] = 0.0f; G.wtot()[eo + s] = 0;
                         {
-                            const int k2 = T.cold.trip_next[k];
+                            const int k2 = D.trip_next()[k];
                             L.dep[d] = (uint16_t)k2;
-                            L.dep_t[d] = k2 == (int)TRIP_NONE ? (uint16_t)0xFFFF : (uint16_t)T.cold.trip_depart[k2];
+                            L.dep_t[d] = k2 == (int)TRIP_NONE ? (uint16_t)0xFFFF : (uint16_t)D.trip_depart()[k2];
                         }
                         rs_atomic_or(&L.alive[s >> 5], 1u << (s & 31));
                         rs_atomic_add(&L.sc[SC_NACT], 1);
                         rs_atomic_add(&L.sc[SC_NINS], 1);
                         rs_atomic_add(&L.sc[SC_STATS + ST_INSERTED], 1);
-                        rs_atomic_add(&L.sc[SC_STATS + ST_DEPDELAY], t - T.cold.trip_depart[k]);
+                        rs_atomic_add(&L.sc[SC_STATS + ST_DEPDELAY], t - D.trip_depart()[k]);
                         if (s + 1 > top) top = s + 1;
                         // (a standing vehicle does not register an approach)
                     }
@@ -1653,7 +1682,7 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const TT &T, const GT &G, con
             // store the slab back (once per env-step)
             const int rq = L.aux[s].rq;
             G.pos()[eo + s] = L.node[s].pos; G.speed()[eo + s] = L.node[s].speed; G.swait()[eo + s] = L.aux[s].swait;
-            G.cursor()[eo + s] = (uint16_t)(rq - (int)T.routes()[T.trip_route()[L.node[s].trip]].start);
+            G.cursor()[eo + s] = (uint16_t)(rq - (int)T.routes()[D.trip_route()[L.node[s].trip]].start);
             if (!obs) continue;
             const int prev_owner = G.owner()[eo + s];
             const LaneRec LR = T.lanes()[lane];         // (only its length is used: one dword)
@@ -1777,26 +1806,38 @@ RS_DEV void rs_step_body_on(Exec &ex, const LT &L, const TT &T, const GT &G, con
                 // trips whose insertion has been tried and failed so far: departed before the last tick, not on the network
                 const int t = L.sc[SC_T];
                 const int hz = t - 1 <= T.horizon ? t - 1 : T.horizon;
-                st[tid] = (t >= 1 ? T.cold.trips_cum[hz] : 0) - L.sc[SC_NINS];
+                st[tid] = (t >= 1 ? D.trips_cum()[hz] : 0) - L.sc[SC_NINS];
             } else st[tid] += L.sc[SC_STATS + tid];
         }
     });
 }
 
-// the step for a capacity known at compile time (CAP: the offsets that follow from it are literals) or at run time (CAP = 0)
-template <int CAP, class Exec, class GT>
-RS_DEV void rs_step_body(Exec &ex, const Lds &L, const KTab &T, const GT &G, const Out &O, const KParams &P,
-                         const int32_t *actions, int env) {
+// the step for a capacity known at compile time (CAP: the offsets that follow from it are literals) or at run time (CAP = 0).
+// DEM: RS_DEM_OFF / RS_DEM_ON -- the includer knows whether the handle has demand variants and instantiates the step for that case alone
+// (the HIP library: one kernel each, so that a handle without variants launches a kernel without the selection); RS_DEM_ANY, the
+// default -- the tables decide at run time (the host emulation, the profiling kernel)
+enum { RS_DEM_OFF = 0, RS_DEM_ON = 1, RS_DEM_ANY = 2 };
+template <int CAP, bool DEM, class Exec, class GT>
+RS_DEV void rs_step_body_cap(Exec &ex, const Lds &L, const KTab &T, const GT &G, const Out &O, const KParams &P,
+                             const int32_t *actions, int env) {
     if constexpr (CAP != 0) {
         const LdsFix<CAP> Lf(L);
-        rs_step_body_on<CAP>(ex, Lf, T, G, O, P, actions, env);
-    } else rs_step_body_on<CAP>(ex, L, T, G, O, P, actions, env);
+        rs_step_body_on<CAP, DEM>(ex, Lf, T, G, O, P, actions, env);
+    } else rs_step_body_on<CAP, DEM>(ex, L, T, G, O, P, actions, env);
+}
+template <int CAP, int DEM = RS_DEM_ANY, class Exec, class GT>
+RS_DEV void rs_step_body(Exec &ex, const Lds &L, const KTab &T, const GT &G, const Out &O, const KParams &P,
+                         const int32_t *actions, int env) {
+    if constexpr (DEM == RS_DEM_ANY) {
+        if (T.dem_) rs_step_body_cap<CAP, true>(ex, L, T, G, O, P, actions, env);
+        else rs_step_body_cap<CAP, false>(ex, L, T, G, O, P, actions, env);
+    } else rs_step_body_cap<CAP, DEM == RS_DEM_ON>(ex, L, T, G, O, P, actions, env);
 }
 // the step of one map: F = ScnFix_<map>, every scalar and every offset a literal (the host's Lds table is not read at all)
-template <class F, class Exec, class GT>
+template <class F, bool DEM = false, class Exec, class GT>
 RS_DEV void rs_step_body_fix(Exec &ex, const KTab &T, const GT &G, const Out &O, const KParams &P, const int32_t *actions, int env) {
     const KTabFix<F> Tf(T);
     const LdsScn<F> Lf{};
-    rs_step_body_on<F::capacity>(ex, Lf, Tf, G, O, P, actions, env);
+    rs_step_body_on<F::capacity, DEM>(ex, Lf, Tf, G, O, P, actions, env);
 }
 #endif      // RS_LAYOUT_ONLY

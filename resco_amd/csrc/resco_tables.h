@@ -178,6 +178,23 @@ template <class I> RS_MEM LinkRec link_load(const LinkRec *tab, I i) {
 }
 #endif
 
+// ---- demand variants (rs_set_demand): the trip tables of K variants, one block of `stride` bytes per variant in ONE allocation, every
+// table at an offset that follows from (n_trips, n_dep, horizon) -- literals to the step kernel of a shipped map:
+//   trip_depart i32 [n_trips] | trips_cum i32 [horizon + 2] | trip_next u16 [n_trips] | trip_route u16 [n_trips] | dep_first u16 [n_dep] |
+//   trip_vtype u8 [n_trips] | padding to 16 bytes
+// An environment reads the block at KTab::dem_env_[env] bytes from KTab::dem_; a handle without variants (both NULL: a zero-initialised
+// KTab) reads the tables of its scenario through the pointers above, as ever.
+#ifndef RS_CARVE
+#define RS_CARVE static inline
+#endif
+RS_CARVE uint32_t dem_off_depart(int, int, int) { return 0u; }
+RS_CARVE uint32_t dem_off_cum(int n_trips, int, int) { return 4u * (uint32_t)n_trips; }
+RS_CARVE uint32_t dem_off_next(int n_trips, int, int horizon) { return 4u * (uint32_t)n_trips + 4u * (uint32_t)(horizon + 2); }
+RS_CARVE uint32_t dem_off_route(int n_trips, int n_dep, int horizon) { return dem_off_next(n_trips, n_dep, horizon) + 2u * (uint32_t)n_trips; }
+RS_CARVE uint32_t dem_off_first(int n_trips, int n_dep, int horizon) { return dem_off_route(n_trips, n_dep, horizon) + 2u * (uint32_t)n_trips; }
+RS_CARVE uint32_t dem_off_vtype(int n_trips, int n_dep, int horizon) { return dem_off_first(n_trips, n_dep, horizon) + 2u * (uint32_t)n_dep; }
+RS_CARVE uint32_t dem_stride(int n_trips, int n_dep, int horizon) { return (dem_off_vtype(n_trips, n_dep, horizon) + (uint32_t)n_trips + 15u) & ~15u; }
+
 struct KTab {
     const LaneRec *lanes_;
     const LinkRec *links_;
@@ -194,6 +211,12 @@ struct KTab {
     float occ_unit;                 // length + minGap of the most common vehicle type (oracle: occ_unit)
     int32_t n_trips, tls_maxl, kmax;
     int32_t n_lanes, n_cells, n_signals, n_obs, n_vtypes, horizon, capacity, step_length, yellow_length, lmax, n_arr, n_dep;
+    // demand variants (rs_set_demand; both NULL: none, every environment runs the scenario's own trips).  Last, so that every member
+    // above stays where it was in the constant argument block
+    const char *dem_;               // the variants' tables, dem_stride() bytes each (layout: dem_off_* above)
+    const uint32_t *dem_env_;       // [n_envs] byte offset of the environment's variant in dem_
+    RS_MEM const char *dem() const { return RS_G(dem_); }
+    RS_MEM const uint32_t *dem_env() const { return RS_G(dem_env_); }
     RS_MEM const LaneRec *lanes() const { return RS_G(lanes_); }
     RS_MEM const LinkRec *links() const { return RS_G(links_); }
     RS_MEM const FoeRec *foes() const { return RS_G(foes_); }
@@ -244,9 +267,11 @@ struct PackedTables {
     std::vector<DepInfo> dep_info;
     std::vector<int32_t> tls_off_p, fix_off_p;      // byte offset of signal s's first row in tls8 / fix8 (rows padded to tls_maxl bytes)
     std::vector<int16_t> lane_obs16;
+    std::vector<int16_t> route_dep;         // RouteRec::dep_idx of every route (pack_trips)
     std::vector<int32_t> obs_sig;
     std::vector<float> route_cont;          // sc->route_cont with the sign bit set where the lane is not one of the best of its route step (resco_step.h: cont_notbest)
     int n_cells = 0, n_arr = 1, n_dep = 1, kmax = 1, lmax = 1, tls_maxl = 1;
+    int common_vt = 0;                      // the most common vehicle type of the scenario's trips (occ_unit)
     float maxlen = 0.0f, occ_unit = 0.0f;
     float cell_len = 30.0f, cell_inv = 1.0f / 30.0f;       // grid cell length of this build of the tables (pick_cell_len)
     std::string err;
@@ -272,6 +297,28 @@ struct PackedTables {
             if (c >= bc - RM_CONT_EPS || c >= RM_GOOD_CONT) out[n++] = l;
         }
         if (n == 1) out[1] = out[0];
+    }
+
+    // the trip tables the kernels read, of the scenario's own trips (build) or of a demand variant (resco_host.h: DemandHost::pack):
+    // route u16, vtype u8, the backlog chains -- trip_next[k] = the next trip with k's departure lane, dep_first[d] = the lane's first
+    // (TRIP_NONE: none).  route_dep[r] = RouteRec::dep_idx of route r.  The caller has checked route < n_routes and vtype < n_vtypes
+    static void pack_trips(const int16_t *route_dep, int n_dep, int n_trips, const int32_t *route, const int32_t *vtype, uint16_t *trip_route,
+                           uint8_t *trip_vtype, uint16_t *trip_next, uint16_t *dep_first) {
+        for (int d = 0; d < n_dep; ++d) dep_first[d] = (uint16_t)TRIP_NONE;
+        for (int k = n_trips - 1; k >= 0; --k) {
+            trip_route[k] = (uint16_t)route[k]; trip_vtype[k] = (uint8_t)vtype[k];
+            const int d = route_dep[route[k]];
+            trip_next[k] = dep_first[d];
+            dep_first[d] = (uint16_t)k;
+        }
+    }
+    // the most common vehicle type of a demand (ties: the lower index): what one queued vehicle occupies is its length + minGap (occ_unit)
+    static int common_vtype(int n_vtypes, int n_trips, const int32_t *vtype) {
+        std::vector<int> cnt((size_t)(n_vtypes > 0 ? n_vtypes : 1), 0);
+        for (int k = 0; k < n_trips; ++k) cnt[vtype[k]] += 1;
+        int best = 0;
+        for (int v = 1; v < n_vtypes; ++v) if (cnt[v] > cnt[best]) best = v;
+        return best;
     }
 
     // grid cells of the whole network for a given cell length (what build() lays out)
@@ -311,11 +358,8 @@ struct PackedTables {
         for (int v = 0; v < sc->n_vtypes; ++v)
             if (sc->vtype_params[v * VT_COLS + VT_LENGTH] > maxlen) maxlen = sc->vtype_params[v * VT_COLS + VT_LENGTH];
         {   // what one queued vehicle occupies: the most common vehicle type (ties: the lower index)
-            std::vector<int> cnt((size_t)(sc->n_vtypes > 0 ? sc->n_vtypes : 1), 0);
-            for (int k = 0; k < sc->n_trips; ++k) cnt[sc->trip_vtype[k]] += 1;
-            int best = 0;
-            for (int v = 1; v < sc->n_vtypes; ++v) if (cnt[v] > cnt[best]) best = v;
-            occ_unit = (sc->vtype_params[best * VT_COLS + VT_LENGTH] + sc->vtype_params[best * VT_COLS + VT_MINGAP]) * RM_OCC_FACTOR;
+            const int best = common_vt = common_vtype(sc->n_vtypes, sc->n_trips, sc->trip_vtype);
+            occ_unit =(sc->vtype_params[best * VT_COLS + VT_LENGTH] + sc->vtype_params[best * VT_COLS + VT_MINGAP]) * RM_OCC_FACTOR;
         }
         if (sc->capacity >= NIL) { err = "capacity exceeds the 11-bit slot ids of the grid cells"; return false; }
         if (!cell_len_ok(sc, cell_len)) {
@@ -435,14 +479,11 @@ struct PackedTables {
             routes[r].start = (uint32_t)rs; routes[r].depart_lane = (uint16_t)dl; routes[r].dep_idx = lane_dep[dl];
             routes[r].depart_cell0 = lanes[dl].cell0; routes[r].pad = 0; routes[r].depart_len = sc->lane_len[dl];
         }
-        trip_route.resize((size_t)sc->n_trips); trip_vtype.resize((size_t)sc->n_trips); trip_next.assign((size_t)sc->n_trips, (uint16_t)TRIP_NONE);
-        dep_first.assign((size_t)n_dep, (uint16_t)TRIP_NONE);
-        for (int k = sc->n_trips - 1; k >= 0; --k) {
-            trip_route[k] = (uint16_t)sc->trip_route[k]; trip_vtype[k] = (uint8_t)sc->trip_vtype[k];
-            const int d = routes[sc->trip_route[k]].dep_idx;
-            trip_next[k] = dep_first[d];
-            dep_first[d] = (uint16_t)k;
-        }
+        route_dep.resize((size_t)sc->n_routes);
+        for (int r = 0; r < sc->n_routes; ++r) route_dep[(size_t)r] = routes[r].dep_idx;
+        trip_route.resize((size_t)sc->n_trips); trip_vtype.resize((size_t)sc->n_trips); trip_next.resize((size_t)sc->n_trips);
+        dep_first.resize((size_t)n_dep);
+        pack_trips(route_dep.data(), n_dep, sc->n_trips, sc->trip_route, sc->trip_vtype, trip_route.data(), trip_vtype.data(), trip_next.data(), dep_first.data());
         // link states per (signal, phase): one row of tls_maxl bytes (a multiple of 4, zero padded) per phase, so that a phase
         // change copies a row into the working memory with a handful of independent 32-bit loads instead of one byte at a time
         tls_maxl = (tls_maxl + 3) & ~3;

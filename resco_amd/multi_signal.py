@@ -354,7 +354,8 @@ class MultiSignal(_EnvBase):
             return []
         e = self.view_env
         rd = self.sim.read
-        return tripinfo_records(self.scenario, rd('trip_log')[e], int(rd('env')[e, 0]), rd('veh_lane')[e], rd('veh_trip')[e],
+        # (the trips of the viewed environment's own demand variant, if the handle has variants: BatchedSim.set_demand)
+        return tripinfo_records(self.sim.env_scenarios()[e], rd('trip_log')[e], int(rd('env')[e, 0]), rd('veh_lane')[e], rd('veh_trip')[e],
                                 rd('veh_depart')[e], rd('veh_tloss')[e], rd('veh_wtot')[e], self.sim.seed,
                                 self.sim.env_base + e, self.sim.speed_dev)
 
@@ -508,7 +509,7 @@ class VecMultiSignal:
 
     def __init__(self, map_name, n_envs, states=('drq_norm',), rewards=('wait',), net=None, device=0, seed=0,
                  max_distance=200, step_length=10, yellow_length=3, sigma=-1.0, speed_dev=1, fixed_program=False,
-                 env_base=0, block_threads=0, scenario=None, outputs=None, step_ratio=1, tls_expiry=True):
+                 env_base=0, block_threads=0, scenario=None, outputs=None, step_ratio=1, tls_expiry=True, demand=None):
         mc = map_configs.get(map_name, {})
         self.scenario = scenario if scenario is not None else load_scenario(map_name, net, mc.get('lights', ()),
                                                                             yellow_length)
@@ -526,6 +527,17 @@ class VecMultiSignal:
         self._tensors = {}
         if outputs is not None:         # only these per-lane / per-movement buffers are written (BatchedSim.set_outputs)
             self.sim.set_outputs(outputs)
+        if demand:                      # demand variants, one per environment ((env_base + e) % K): in force from the first reset()
+            self.set_demand(demand)
+            self.sim.reset()
+
+    def set_demand(self, scenarios, env_variant=None):
+        """Every environment runs the trips of its own demand variant from the next reset() on (BatchedSim.set_demand; resco_amd/demand.py
+        builds variants); an empty list or None returns to the scenario's own trips."""
+        if scenarios:
+            self.sim.set_demand(scenarios, env_variant)
+        else:
+            self.sim.clear_demand()
 
     # registry names that are not a device buffer of their own but a cheap arrangement of buffers (torch ops on the stream)
     DERIVED = ('drq', 'fma2c', 'fma2c_full')

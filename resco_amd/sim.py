@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from ._abi import Fma2cRewardTableStruct, Fma2cTrainStruct, ParamsStruct, PPOTrainStruct, RolloutStruct, TrainStruct, pack_scenario
+from ._abi import DemandStruct, Fma2cRewardTableStruct, Fma2cTrainStruct, ParamsStruct, PPOTrainStruct, RolloutStruct, TrainStruct, pack_scenario
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RESCO_SIM_LIB: another build of the same HIP library (A/B variants compiled with different -D switches, tools/ab.py)
@@ -42,7 +42,7 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_mplight_multi_create', 'rs_mplight_multi_sample', 'rs_mplight_multi_grad', 'rs_mplight_multi_step', 'rs_mplight_multi_update',
                'rs_mplight_multi_sync_target', 'rs_mplight_multi_steps', 'rs_mplight_multi_set_steps', 'rs_mplight_multi_destroy',
                'rs_idqn_pack_weights', 'rs_dqn_sync_target', 'rs_mplight_dqn_sync_target', 'rs_group_train',
-               'rs_ppo_perm', 'rs_ippo_pack_weights', 'rs_group_ppo_train', 'rs_info_kernel']
+               'rs_ppo_perm', 'rs_ippo_pack_weights', 'rs_group_ppo_train', 'rs_info_kernel', 'rs_set_demand', 'rs_demand_info']
 
 # the FMA2C entry points (include/resco_sim.h: rs_fma2c_*)
 FMA2C_SYMBOLS = ['rs_fma2c_create', 'rs_fma2c_act', 'rs_fma2c_value', 'rs_fma2c_reset', 'rs_fma2c_set_device_weights', 'rs_fma2c_buffer',
@@ -87,6 +87,9 @@ def bind(L):
     if hasattr(L, 'rs_info_kernel'):
         L.rs_info_kernel.argtypes = [vp]
         L.rs_info_kernel.restype = C.c_char_p
+    if hasattr(L, 'rs_set_demand'):         # (tests/hostemu exports no per-environment demand)
+        L.rs_set_demand.argtypes = [vp, i32, vp, vp]
+        L.rs_demand_info.argtypes = [vp, C.POINTER(i32), vp]
     if hasattr(L, 'rs_idqn_create'):
         L.rs_idqn_create.argtypes = [i32, i32, i32] + [vp] * 9 + [C.POINTER(vp)]
         L.rs_idqn_act.argtypes = [vp, vp, i32, i32, i32, f32, u32, u32, vp, vp, vp, vp]
@@ -478,6 +481,7 @@ class BatchedSim:
         self._maxwave_ready = False
         self._masked_off = frozenset()          # maskable output buffers the observe does not write at present (set_outputs)
         self._dep_cache = None
+        self._demand = None                     # the variants in force (set_demand): (scenarios, env_variant)
         self._meta = {}
         for name, bid in BUF_ID.items():
             ptr, shape, nd, dt = C.c_void_p(), (C.c_int64 * 4)(), C.c_int32(), C.c_int32()
@@ -568,6 +572,78 @@ class BatchedSim:
     def sync(self):
         self._check(self._lib.rs_sync(self._h))
 
+    # ------------------------------------------------------------------ per-environment demand
+    def set_demand(self, scenarios, env_variant=None):
+        """Every environment runs the trips of its own demand variant from the NEXT reset() on (rs_set_demand): call it right before
+        reset(), as set_seed.  scenarios: K Scenarios that differ from this handle's in their trips alone (demand.with_trips,
+        demand.demand_variant, demand.demand_set); env_variant: int [n_envs] in 0 .. K - 1, default (env_base + e) % K
+        (demand.env_variants).  The host-side figures (backlog, trip_metrics, ...) follow each environment's variant.  An empty list
+        is clear_demand()."""
+        from .demand import env_variants
+        if not hasattr(self._lib, 'rs_set_demand'):
+            raise RuntimeError('the loaded library has no rs_set_demand: rebuild it (there is no CPU fallback)')
+        scenarios = list(scenarios)
+        K = len(scenarios)
+        if K == 0:
+            return self.clear_demand()
+        A = self.sc.arrays
+        for k, v in enumerate(scenarios):
+            if v.n_trips != self.sc.n_trips:
+                raise ValueError('demand variant %d has %d trips, the scenario %d (demand.with_trips keeps the number)' % (k, v.n_trips, self.sc.n_trips))
+            if v.n_routes != self.sc.n_routes or not np.array_equal(v.arrays['route_edge'], A['route_edge']) or v.horizon != self.sc.horizon:
+                raise ValueError('demand variant %d is not a variant of this scenario (other routes or horizon)' % k)
+        ev = env_variants(self.n_envs, self.env_base, K) if env_variant is None else np.ascontiguousarray(env_variant, dtype=np.int32)
+        if ev.shape != (self.n_envs,):
+            raise ValueError('env_variant must have one entry per environment (%d), got shape %s' % (self.n_envs, ev.shape))
+        structs, keep = (DemandStruct * K)(), []
+        for k, v in enumerate(scenarios):
+            for name in ('trip_depart', 'trip_route', 'trip_vtype'):
+                a = np.ascontiguousarray(v.arrays[name], dtype=np.int32)
+                keep.append(a)
+                setattr(structs[k], name, a.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._check(self._lib.rs_set_demand(self._h, K, structs, ev.ctypes.data))
+        del keep
+        self._demand = (scenarios, ev.copy())
+        self._dep_cache = None
+
+    def clear_demand(self):
+        """back to the scenario's own trips in every environment, from the next reset() on; nothing happens (no call, no new demand
+        generation: earlier snapshots stay valid) when no variants are in force"""
+        if self._demand is None:
+            return
+        self._check(self._lib.rs_set_demand(self._h, 0, None, None))
+        self._demand = None
+        self._dep_cache = None
+
+    def demand_info(self):
+        """(K, env_variant) as the library holds them; (0, None) without variants"""
+        if not hasattr(self._lib, 'rs_demand_info'):
+            return 0, None
+        k, ev = C.c_int32(), np.zeros(self.n_envs, np.int32)
+        self._check(self._lib.rs_demand_info(self._h, C.byref(k), ev.ctypes.data))
+        return k.value, (ev if k.value else None)
+
+    def env_scenarios(self):
+        """the scenario whose trips each environment runs: [n_envs] (its variant's, or the handle's own)"""
+        if self._demand is None:
+            return [self.sc] * self.n_envs
+        scenarios, ev = self._demand
+        return [scenarios[int(k)] for k in ev]
+
+    def _demand_groups(self):
+        """[(scenario, environments that run its trips)]: one group per variant in use, or the handle's scenario and everyone"""
+        if self._demand is None:
+            return [(self.sc, np.arange(self.n_envs))]
+        scenarios, ev = self._demand
+        return [(scenarios[k], np.nonzero(ev == k)[0]) for k in range(len(scenarios)) if bool((ev == k).any())]
+
+    def scheduled(self):
+        """the demand of every environment: the trips of its variant with depart <= horizon (padding trips are not demand)"""
+        out = np.zeros(self.n_envs, np.int64)
+        for sc, envs in self._demand_groups():
+            out[envs] = int((sc.arrays['trip_depart'] <= sc.horizon).sum())
+        return out
+
     def fma2c_record(self, policy, table, rew_out, acts_out=None, ret_acc=None, stream=None):
         """rs_fma2c_record: the FMA2C rewards of all agents (RAW) into rew_out f32 [N, K]; acts_out int32 [N, K] = the managers' and
         the workers' actions of the step; ret_acc f32 [N, K] += the reward.  policy: an rs_policy_handle (FusedFMA2C.handle); table:
@@ -631,11 +707,15 @@ class BatchedSim:
     def time(self):
         return self.read('env')[:, 0]
 
-    def _dep_lanes(self):
+    def _dep_lanes(self, sc=None):
         """The departure lanes in the kernel's numbering (resco_tables.h: the first allowed lane of the first edge of every
-        ROUTE, ascending) and, per lane, its trips in FIFO order with their departure seconds and running sums."""
+        ROUTE, ascending) and, per lane, its trips in FIFO order with their departure seconds and running sums -- of the handle's
+        scenario or of a demand variant (the lanes are the same: they come from the routes; a lane may have no trip)."""
+        sc = self.sc if sc is None else sc
         if self._dep_cache is None:
-            A = self.sc.arrays
+            self._dep_cache = {}
+        if id(sc) not in self._dep_cache:
+            A = sc.arrays
             lane_of_route = A['edge_lane0'][A['route_edge'][A['route_start'][:-1]]]
             lanes = np.unique(lane_of_route)
             n_dep = self._meta['dep_next'][1][1]
@@ -648,8 +728,8 @@ class BatchedSim:
                 trips = np.nonzero(lane_of_trip == lane)[0]          # ascending trip index = FIFO order = departure order
                 dep = depart[trips]
                 tabs.append((trips, dep, np.concatenate([[0], np.cumsum(dep)])))
-            self._dep_cache = tabs
-        return self._dep_cache
+            self._dep_cache[id(sc)] = (sc, tabs)                     # (the scenario is held: its id stays its own)
+        return self._dep_cache[id(sc)][1]
 
     def backlog(self):
         """Trips that have departed (depart < now) but are not on the network yet, per environment: (count, seconds
@@ -659,12 +739,16 @@ class BatchedSim:
         now = self.time().astype(np.int64)
         cnt = np.zeros(self.n_envs, np.int64)
         waited = np.zeros(self.n_envs, np.int64)
-        for d, (trips, dep, csum) in enumerate(self._dep_lanes()):
-            h = head[:, d]
-            first = np.where(h == TRIP_NONE, len(trips), np.searchsorted(trips, h))
-            last = np.maximum(first, np.searchsorted(dep, now, side='left'))      # trips [first, last) are due and waiting
-            cnt += last - first
-            waited += (last - first) * now - (csum[last] - csum[first])
+        for sc, envs in self._demand_groups():           # every environment against the trips of its own demand variant
+            for d, (trips, dep, csum) in enumerate(self._dep_lanes(sc)):
+                h, t = head[envs, d], now[envs]
+                first = np.where(h == TRIP_NONE, len(trips), np.searchsorted(trips, h))
+                due = np.searchsorted(dep, t, side='left')
+                if self._demand is not None:        # (a trip of a VARIANT scheduled beyond the horizon is padding, not demand; a handle without variants counts as ever)
+                    due = np.minimum(due, np.searchsorted(dep, sc.horizon, side='right'))
+                last = np.maximum(first, due)                                     # trips [first, last) are due and waiting
+                cnt[envs] += last - first
+                waited[envs] += (last - first) * t - (csum[last] - csum[first])
         return cnt, waited
 
     def trip_delay(self):
@@ -708,14 +792,15 @@ class BatchedSim:
         in arrival order; the unfinished ones follow in id order), looks up that vehicle's SCHEDULED departure in the rou.xml and
         charges end_time - depart for every <vehicle> scheduled later.  Arrived vehicles are considered when the handle keeps
         per-trip records (trip_log=1); without them the latest departure is taken from the vehicles still on the network."""
-        sched = self.sc.arrays['trip_depart'].astype(np.int64)
         horizon = int(self.sc.horizon)
         trips = self.read('veh_trip').astype(np.int64)
-        ids = getattr(self.sc, 'trip_ids', None)
+        env_sc = self.env_scenarios()           # the schedule and the ids of every environment's own demand variant
         log = self.read('trip_log') if self._p.trip_log else None
         n_nd = np.zeros(self.n_envs, np.int64)
         charged = np.zeros(self.n_envs, np.float64)
         for e in range(self.n_envs):
+            sched = env_sc[e].arrays['trip_depart'].astype(np.int64)
+            ids = getattr(env_sc[e], 'trip_ids', None)
             best_t, best_k = -1, -1
             if log is not None and log.size:
                 arr = np.nonzero(log[e, :, 1] > 0)[0]
@@ -734,6 +819,8 @@ class BatchedSim:
             if best_k < 0:
                 continue
             late = sched > sched[best_k]
+            if self._demand is not None:
+                late &= sched <= horizon        # (beyond the horizon: padding of a demand variant, charged nowhere)
             n_nd[e] = int(late.sum())
             charged[e] = float((horizon - sched[late]).sum())
         return n_nd, charged

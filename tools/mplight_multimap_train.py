@@ -17,7 +17,12 @@ for every --eval-on map, the greedy delay of the shared weights (zero-shot) besi
 Checkpoints (resco_amd/checkpoint.py, the flags of tools/mplight_train.py): --save PATH [--save-freq K] [--save-replay], --load PATH,
 --stop-after K; the checkpoint's map is '+'.join(maps).  --load PATH --eval loads the weights alone -- from a multi-map checkpoint or
 from a SINGLE-map one of tools/mplight_train.py, whatever its map was (checkpoint.load_frap_weights) -- and evaluates greedily on
-the maps given and on the --eval-on maps."""
+the maps given and on the --eval-on maps.
+
+Demand variants (the flags of tools/mplight_train.py): --demand-variants K[,jitter_s[,keep_lo,keep_hi]] gives the environments of every
+training map K variants of that map's demand, drawn anew per episode from (seed, episode, map); the spec is part of the checkpoint's
+signature.  --eval-demand K[,...]: the greedy evaluation of every training map (and of every --eval-on map) also runs on K held-out
+variants and reports the mean delay per variant beside the figure of the map's own demand."""
 import json
 import os
 import sys
@@ -31,8 +36,8 @@ from resco_amd.agents.idqn_learn import linear_epsilon                          
 from resco_amd.agents.mplight import FusedMPLight, MPLightReplay, frap_from_scenario        # noqa: E402
 from resco_amd.agents.mplight_multi import MultiMapMPLightLearner                           # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                                           # noqa: E402
-from resco_amd import checkpoint                                                            # noqa: E402
-from tools.mplight_train import delay, greedy_evaluation                                    # noqa: E402
+from resco_amd import checkpoint, demand                                                    # noqa: E402
+from tools.mplight_train import delay, greedy_evaluation, greedy_on_variants                # noqa: E402
 
 
 def random_delay(env, steps):
@@ -46,9 +51,12 @@ def random_delay(env, steps):
 
 
 def main(maps=('cologne3', 'ingolstadt7'), n_envs=(256,), episodes=30, batch=256, replay_steps=2048, seed=0, full=False, eval_on=(), quiet=False, made=None,
-         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0):
+         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, demand_variants=None, eval_demand=0):
     """-> (rows, final); a run that leaves at stop_after returns (rows, None).  made: a dict that receives the learner (closed when
-    the call returns; its vectors stay readable)."""
+    the call returns; its vectors stay readable).  demand_variants / eval_demand: the demand flags of the module docstring."""
+    n_var, var_kw = demand.parse_spec(demand_variants)
+    n_eval, eval_kw = demand.parse_spec(eval_demand)
+    eval_kw = eval_kw or var_kw
     maps, eval_on = [str(m) for m in maps], [str(m) for m in eval_on]
     n_envs = [int(n) for n in n_envs]
     n_envs = n_envs * len(maps) if len(n_envs) == 1 else n_envs
@@ -81,6 +89,8 @@ def main(maps=('cologne3', 'ingolstadt7'), n_envs=(256,), episodes=30, batch=256
     for kind, seq in (('policy', policies), ('replay', replays)):
         objects.update({'%s%d' % (kind, m): o for m, o in enumerate(seq)})
     hyper = dict(episodes=episodes, decay_steps=decay, seed=seed)
+    if n_var:
+        hyper['demand_variants'] = str(demand_variants)     # (a resume under another spec is another run: refused)
     map_name = '+'.join(maps)
     first_ep, rows = 0, []
     if load and eval_only:
@@ -98,8 +108,10 @@ def main(maps=('cologne3', 'ingolstadt7'), n_envs=(256,), episodes=30, batch=256
     rnd = {name: random_delay(e, steps) for name, e in zip(maps, envs)}
     for ep in range(first_ep, episodes):
         obs = []
-        for e in envs:
+        for m, e in enumerate(envs):
             e.sim.set_seed(1000 + ep + 7919 * seed)
+            if n_var:
+                e.set_demand(demand.demand_set(e.scenario, n_var, (demand.TRAIN_STREAM, seed, ep, m), **var_kw))
             obs.append(e.reset()[state])
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -128,8 +140,16 @@ def main(maps=('cologne3', 'ingolstadt7'), n_envs=(256,), episodes=30, batch=256
     final = dict(maps=maps, agent=agent, envs=n_envs, episodes=episodes, batch=batch, replay_steps=replay_steps, seed=seed, random_avg_delay_s=rnd)
     if not eval_only:       # (the rows of a checkpoint loaded for evaluation may be another tool's)
         final['best_training_episode_delay_s'] = {name: min(r['avg_delay_s'][name] for r in rows) for name in maps}
-    if eval_only:
+    for e in envs:
+        e.set_demand(None)      # the evaluations below start from every map's own demand
+    if n_var:
+        final['demand_variants'] = str(demand_variants)
+    held_out = lambda e, m: demand.demand_set(e.scenario, n_eval, (demand.EVAL_STREAM, seed, m), **eval_kw)
+    if eval_only or n_eval > 0:
         final['greedy_avg_delay_s'] = {name: greedy_evaluation(e, p, state, a, steps, 12345) for name, e, p, a in zip(maps, envs, policies, actions)}
+    if n_eval > 0:              # reported, not judged
+        final['greedy_variant_delay_s'] = {name: greedy_on_variants(e, p, state, a, steps, 12345, held_out(e, m))
+                                           for m, (name, e, p, a) in enumerate(zip(maps, envs, policies, actions))}
     zero = {}
     for m, name in enumerate(eval_on):          # a map the weights never saw: its own pairs, the shared vector
         e = make_env(name, n_envs[0])
@@ -139,6 +159,8 @@ def main(maps=('cologne3', 'ingolstadt7'), n_envs=(256,), episodes=30, batch=256
         p = FusedMPLight(frap_from_scenario(e.scenario, D).cuda(), e.scenario, seed=7 + seed + 101 * (len(maps) + m))
         p.share_weights(learner.flat)
         zero[name] = dict(random_avg_delay_s=random_delay(e, steps), greedy_avg_delay_s=greedy_evaluation(e, p, state, e.tensor('actions'), steps, 12345))
+        if n_eval > 0:
+            zero[name]['greedy_variant_delay_s'] = greedy_on_variants(e, p, state, e.tensor('actions'), steps, 12345, held_out(e, len(maps) + m))
         p.close()
         e.close()
     if eval_on:
@@ -151,6 +173,7 @@ def main(maps=('cologne3', 'ingolstadt7'), n_envs=(256,), episodes=30, batch=256
 
 if __name__ == '__main__':
     ckpt, a = checkpoint.tool_flags(sys.argv[1:])
+    dem, a = demand.tool_flags(a)
     eval_on = ()
     if '--eval-on' in a:
         i = a.index('--eval-on')
@@ -162,4 +185,4 @@ if __name__ == '__main__':
         raise SystemExit(__doc__)
     main(tuple(x for x in a[0][len('maps='):].split(',') if x), tuple(int(x) for x in a[1].split(',')) if len(a) > 1 else (256,),
          int(a[2]) if len(a) > 2 else 30, int(a[3]) if len(a) > 3 else 256, int(a[4]) if len(a) > 4 else 2048, int(a[5]) if len(a) > 5 else 0,
-         full=len(a) > 6 and a[6] == 'full', eval_on=eval_on, **ckpt)
+         full=len(a) > 6 and a[6] == 'full', eval_on=eval_on, **ckpt, **dem)

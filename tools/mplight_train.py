@@ -15,7 +15,13 @@ policy on the same demand.  --device-loop (implies --device-update): the loop it
 Checkpoints (resco_amd/checkpoint.py), in every mode: --save PATH [--save-freq K] [--save-replay] (the replay ring only with --save-replay: it is the large part; without it a resumed run is a valid continuation, not the same one) writes the training state after every K-th
 episode and after the last; --load PATH continues at the stored episode (`episodes` stays the planned total, so the schedules and the
 demand seeds go on where they stopped); --load PATH --eval loads the weights alone and runs one evaluation episode without learning on
-the baseline's demand seed; --stop-after K leaves after K episodes of the planned total, as a job that ran out of time would."""
+the baseline's demand seed; --stop-after K leaves after K episodes of the planned total, as a job that ran out of time would.
+
+Demand variants (resco_amd/demand.py), in every mode: --demand-variants K[,jitter_s[,keep_lo,keep_hi]] gives the environments of the batch
+K variants of the map's demand (environment e runs variant e % K), drawn anew for every episode from (seed, episode); the spec is part of a
+checkpoint's signature, and a resumed run draws the same sets.  --eval-demand K[,jitter_s[,keep_lo,keep_hi]]: after training, one greedy
+episode on the map's own demand and one on K held-out variants (K alone: the training spec's jitter and keep; seeds no training episode
+uses); the final line reports both, per variant."""
 import json
 import os
 import sys
@@ -30,7 +36,7 @@ from resco_amd.agents.mplight import FusedMPLight, MPLightLearner, MPLightReplay
 from resco_amd.agents.mplight_learn_fused import FusedMPLightLearner                        # noqa: E402
 from resco_amd.agents.train_fused import DeviceTrainer                                      # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                                           # noqa: E402
-from resco_amd import checkpoint                                                            # noqa: E402
+from resco_amd import checkpoint, demand                                                    # noqa: E402
 
 
 def delay(env):
@@ -47,12 +53,24 @@ def greedy_evaluation(env, policy, state, actions, steps, seed):
     return round(delay(env)[0], 2)
 
 
+def greedy_on_variants(env, policy, state, actions, steps, seed, variants):
+    """the greedy episode on held-out demand variants -> the mean delay of the environments of every variant"""
+    env.set_demand(variants)
+    greedy_evaluation(env, policy, state, actions, steps, seed)
+    per = demand.per_variant_mean(env.sim.trip_delay(), demand.env_variants(env.n_envs, env.sim.env_base, len(variants)), len(variants))
+    env.set_demand(None)
+    return [round(float(x), 2) for x in per]
+
+
 def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, seed=0, full=False, quiet=False, device_update=False, device_loop=False, chunk=0,
-         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0):
+         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, demand_variants=None, eval_demand=0):
     """device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
     save / save_freq / save_replay / load / eval_only / stop_after: the checkpoint flags of the module docstring; a run that leaves
-    at stop_after returns (rows, None)."""
+    at stop_after returns (rows, None).  demand_variants / eval_demand: the demand flags of the module docstring."""
     device_update = device_update or device_loop
+    n_var, var_kw = demand.parse_spec(demand_variants)
+    n_eval, eval_kw = demand.parse_spec(eval_demand)
+    eval_kw = eval_kw or var_kw
     state = 'mplight_full' if full else 'mplight'
     env = VecMultiSignal(map_name, n, states=(state,), rewards=('pressure',), seed=0, outputs=(state,))
     S, steps = env.n_signals, env.horizon_steps
@@ -77,6 +95,8 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
     if not device_update:
         objects['gen'] = gen
     hyper = dict(episodes=episodes, decay_steps=decay, seed=seed)
+    if n_var:
+        hyper['demand_variants'] = str(demand_variants)     # (a resume under another spec is another run: refused)
     first_ep, rows = 0, []
     if load and eval_only:
         rows = checkpoint.load(load, agent=agent, map_name=map_name, objects=dict(net=net, policy=policy), strict=False)['rows']
@@ -94,6 +114,8 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
 
     for ep in range(first_ep, episodes):
         env.sim.set_seed(1000 + ep + 7919 * seed)
+        if n_var:
+            env.set_demand(demand.episode_set(env.scenario, n_var, seed, ep, **var_kw))
         obs = env.reset()[state]
         ret = torch.zeros(n, S, device='cuda')
         torch.cuda.synchronize()
@@ -130,8 +152,15 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
             return rows, None
     final = dict(map=map_name, agent='MPLightFULL' if full else 'MPLight', envs=n, episodes=episodes, batch=batch, replay_steps=replay.T,
                  seed=seed, best_training_episode_delay_s=min(r['avg_delay_s'] for r in rows), random_avg_delay_s=round(rnd_delay, 2))
-    if eval_only:
+    env.set_demand(None)        # the evaluations below start from the map's own demand
+    if n_var:
+        final['demand_variants'] = str(demand_variants)
+    if eval_only or n_eval > 0:
         final['greedy_avg_delay_s'] = greedy_evaluation(env, policy, state, actions, steps, 12345)
+    if n_eval > 0:              # reported, not judged: held-out variants (the spec of --eval-demand, or the training spec's jitter and keep)
+        held_out = demand.eval_set(env.scenario, n_eval, seed, **eval_kw)
+        final['greedy_variant_delay_s'] = greedy_on_variants(env, policy, state, actions, steps, 12345, held_out)
+        final['greedy_variants_mean_delay_s'] = round(sum(final['greedy_variant_delay_s']) / len(final['greedy_variant_delay_s']), 2)
     if not quiet:
         print(json.dumps(final), flush=True)
     if device_update:
@@ -142,9 +171,10 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
 
 if __name__ == '__main__':
     ckpt, a = checkpoint.tool_flags(sys.argv[1:])
+    dem, a = demand.tool_flags(a)
     device_loop = bool(a) and a[0] == '--device-loop'
     device_update = device_loop or (bool(a) and a[0] == '--device-update')
     a = a[1:] if device_update else a
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 30,
          int(a[3]) if len(a) > 3 else 256, int(a[4]) if len(a) > 4 else 2048, int(a[5]) if len(a) > 5 else 0,
-         full=len(a) > 6 and a[6] == 'full', device_update=device_update, device_loop=device_loop, **ckpt)
+         full=len(a) > 6 and a[6] == 'full', device_update=device_update, device_loop=device_loop, **ckpt, **dem)
