@@ -560,6 +560,16 @@ template <class F> struct LdsScn {
 #define RS_SEC_BEGIN
 #define RS_SEC(id) {}
 #endif
+// what the two long paths of the plan phase did, by kind: a counting build (tests/longpath_host) defines RS_COUNT as a bump of a counter,
+// everybody else compiles it out.  A comparison with the oracle that never took a path has not compared it.
+enum RsCount {
+    RC_WALK, RC_HOP2, RC_HOP3, RC_HOP4, RC_MAX_HOPS, RC_ROUTE_END, RC_DEAD_END, RC_STOP_RED, RC_RED_TOO_CLOSE, RC_MINOR_FAR,
+    RC_FOE_IN, RC_FOE_BLOCKED, RC_FOE_RED, RC_FOE_ARR, RC_FOE_VIA1, RC_FOE_VIA2, RC_NEXT_LEADER, RC_LOOK_DONE,
+    RC_STRATEGIC, RC_SG, RC_SG_LEAD, RC_SG_WANT, RC_URGENT, RC_FOLL_T, RC_CHANGE, RC_LEAD_REQ, RC_COOP_REQ, RC_SWAP, RC_COUNT
+};
+#ifndef RS_COUNT
+#define RS_COUNT(id) {}
+#endif
 template <class LT> RS_DEV int lane_cells(const LT &L, const LaneRec &LR) { return (int)(LR.len * L.cell_inv) + 1; }
 template <class LT> RS_DEV int cell_of(const LT &L, float pos, int ncell) { const int c = (int)(pos * L.cell_inv); return c < ncell ? c : ncell - 1; }
 
@@ -791,10 +801,10 @@ template <class TT> RS_DEV uint16_t cache_link(const TT &T, const LaneRec &LR, i
 template <class TT, class LT> RS_DEV bool foe_blocked(const TT &T, const LT &L, const Grid &grid, const LinkRec &K) {
     for (int i = K.foe_start; i < K.foe_start + K.foe_cnt; ++i) {
         const FoeRec F = rec_load16(T.foes(), i);
-        if (F.tls != 0xFF && tls_state(T, L, F.tls, F.tls_pos) == TLS_R) continue;
-        if (F.arr_idx >= 0 && L.arr[F.arr_idx] < RM_FOE_GAP_Q) return true;
-        if (F.via1_cell0 != 0xFFFF && cells_have_mover(grid, F.via1_cell0, F.via1_nc)) return true;   // a moving vehicle on
-        if (F.via2_cell0 != 0xFFFF && cells_have_mover(grid, F.via2_cell0, F.via2_nc)) return true;   // the foe's junction lanes
+        if (F.tls != 0xFF && tls_state(T, L, F.tls, F.tls_pos) == TLS_R) { RS_COUNT(RC_FOE_RED) continue; }
+        if (F.arr_idx >= 0 && L.arr[F.arr_idx] < RM_FOE_GAP_Q) { RS_COUNT(RC_FOE_ARR) return true; }
+        if (F.via1_cell0 != 0xFFFF && cells_have_mover(grid, F.via1_cell0, F.via1_nc)) { RS_COUNT(RC_FOE_VIA1) return true; }   // a moving vehicle on
+        if (F.via2_cell0 != 0xFFFF && cells_have_mover(grid, F.via2_cell0, F.via2_nc)) { RS_COUNT(RC_FOE_VIA2) return true; }   // the foe's junction lanes
     }
     return false;
 }
@@ -860,17 +870,22 @@ RS_DEV float cont_of(const ContRow &R, int j) {
 // wants the length takes the magnitude, and neither the maximum over the lanes nor the comparisons are evaluated per vehicle and tick.
 RS_DEV bool cont_notbest(float c) { return rs_float_as_int(c) < 0; }
 RS_DEV float cont_len(float c) { return rs_int_as_float(rs_float_as_int(c) & 0x7FFFFFFF); }
-RS_DEV int strategic_dir(const ContRow &R, int kk, int n, float x, float v, int extra, float &rem, const Grid &grid, int cell0, int nc, float occ_unit) {
+// nb: the same signs as ONE word, the not-best mask of the route step (KTab::notbest, bit k = lane k): the distances to the nearest best
+// lane on either side are a find-first-set and a count-leading-zeros on the best lanes' bits, not two loops over the row.
+RS_DEV uint32_t row_notbest(const ContRow &R, int n) { uint32_t nb = 0; for (int j = 0; j < n; ++j) nb |= cont_notbest(cont_of(R, j)) ? 1u << j : 0u; return nb; }
+RS_DEV int strategic_dir(const ContRow &R, uint32_t nb, int kk, int n, float x, float v, int extra, float &rem, const Grid &grid, int cell0, int nc, float occ_unit) {
     const float mine = cont_of(R, kk);
     rem = cont_len(mine) - x;
-#ifdef RS_EMU_CHECK_MAIL      // (host emulation: the sign is what the comparison over the lanes of THIS edge gives)
+#ifdef RS_EMU_CHECK_MAIL      // (host emulation: the sign is what the comparison over the lanes of THIS edge gives, and the mask is the signs)
     { float best = 0.0f; for (int j = 0; j < n; ++j) { const float c = cont_len(cont_of(R, j)); if (c > best) best = c; }
-      for (int j = 0; j < n; ++j) RS_ASSERT(cont_notbest(cont_of(R, j)) == !(cont_len(cont_of(R, j)) >= best - RM_CONT_EPS)) }
+      for (int j = 0; j < n; ++j) RS_ASSERT(cont_notbest(cont_of(R, j)) == !(cont_len(cont_of(R, j)) >= best - RM_CONT_EPS))
+      RS_ASSERT((nb & ((1u << n) - 1u)) == row_notbest(R, n)) }
 #endif
-    if (!cont_notbest(mine)) return 0;
-    int dl = 1000, dr = 1000;
-    for (int j = kk + 1; j < n; ++j) if (!cont_notbest(cont_of(R, j))) { dl = j - kk; break; }
-    for (int j = kk - 1; j >= 0; --j) if (!cont_notbest(cont_of(R, j))) { dr = kk - j; break; }
+    if (!((nb >> kk) & 1u)) return 0;
+    const uint32_t good = ~nb & ((1u << n) - 1u);                   // the best lanes of the edge
+    const uint32_t up = good >> (kk + 1), dn = good & ((1u << kk) - 1u);
+    const int dl = up ? rs_ffs(up) : 1000;                          // lanes to the nearest best one above me / below me
+    const int dr = dn ? kk - (63 - rs_clzll((unsigned long long)dn | 1ull)) : 1000;
     const int dir = (dr <= dl) ? -1 : +1;
     if (grid.c == (uint16_t *)1) return dir;
     const int off = (dr <= dl ? dr : dl) + extra;
@@ -962,10 +977,11 @@ RS_DEV bool may_change_lanes_row(const ContRow &R, const LaneRec &LR, int lane, 
     if ((LR.flags & LF_INTERNAL) || n < 2) return false;
     const int kk = lane - (int)LR.edge_lane0;
     float rem;
-    if (strategic_dir(R, kk, n, x, v, 0, rem, OCC_FULL, 0, 0, 0.0f) != 0) return true;      // any lane that is not a best one
+    const uint32_t nb = row_notbest(R, n);
+    if (strategic_dir(R, nb, kk, n, x, v, 0, rem, OCC_FULL, 0, 0, 0.0f) != 0) return true;      // any lane that is not a best one
     if ((((uint32_t)t >> 1) + (uint32_t)k) & 3u) return false;
     const int tk = kk + ((t & 1) ? -1 : +1);
-    return tk >= 0 && tk < n && strategic_dir(R, tk, n, x, v, RM_SG_EXTRA_LANES, rem, OCC_NONE, 0, 0, 0.0f) == 0;
+    return tk >= 0 && tk < n && strategic_dir(R, nb, tk, n, x, v, RM_SG_EXTRA_LANES, rem, OCC_NONE, 0, 0, 0.0f) == 0;
 }
 // the same from the not-best MASK of the route step (KTab::notbest: bit k = lane k is not one of the step's best lanes -- the signs of the
 // continuation row as one 16-bit word): the move classifies every vehicle every tick, and all it needs of the row is two of these bits.
@@ -981,7 +997,7 @@ template <class TT> RS_DEV bool may_change_lanes(const TT &T, int rq, uint32_t n
         const int tk = kk + ((t & 1) ? -1 : +1);
         if (tk < 0 || tk >= n) r = false;
         else if (!((nb >> tk) & 1u)) r = true;
-        else { float rem; r = strategic_dir(cont_row(T, rq), tk, n, x, v, RM_SG_EXTRA_LANES, rem, OCC_NONE, 0, 0, 0.0f) == 0; }
+        else { float rem; r = strategic_dir(cont_row(T, rq), nb, tk, n, x, v, RM_SG_EXTRA_LANES, rem, OCC_NONE, 0, 0, 0.0f) == 0; }
     }
 #ifdef RS_EMU_CHECK_MAIL      // (host emulation)
     RS_ASSERT(r == may_change_lanes_row(cont_row(T, rq), LR, lane, k, x, v, t))
@@ -1049,52 +1065,73 @@ template <bool LONG, class TT, class LT, class GT> RS_DEV void phase_plan(const 
         int link = (int)(ax.nlink & 0x7FFF);
         int cur_lane = lane;
         const float bgv = d_brake_gap(v, b);        // can I still stop in front of a red / yellow light?
-        for (int hop = 0; hop < RM_MAX_HOPS; ++hop) {
+        RS_COUNT(RC_WALK)
+        // The walk has ONE exit: a lane that is done drops its `go`, and the loop ends when no lane of the wave has it.  Inside a hop the
+        // verdicts are expressions and the results selects -- a wave runs every branch that any of its lanes takes, and the ladder of
+        // `continue` / `break` this replaces was a dozen divergent exits per hop.  What is rare and
+        // costs loads stays behind a branch: the route step of a lane without a link, and the foes.
+        bool go = true;
+        for (int hop = 0; go && hop < RM_MAX_HOPS; ++hop) {
+            if (hop == 1) RS_COUNT(RC_HOP2)
+            if (hop == 2) RS_COUNT(RC_HOP3)
+            if (hop >= 3) RS_COUNT(RC_HOP4)
             const bool cur_int = (LR.flags & LF_INTERNAL) != 0;
             if (hop > 0) link = (int)(cache_link(T, LR, cur_lane, rq, k) & 0x7FFF);
-            bool stop_here = false;
-            LinkRec K;
-            if (link == NLINK_NONE) {
-                // last edge of the route: free run to its end; otherwise a dead end: wait for a lane change
-                if (!cur_int && rs_at(T.rsteps(), rq).next_edge == 0xFFFF) break;
-                stop_here = true;
-            } else {
-                K = link_load(T.links(), link);
-                const int st = tls_state(T, L, K.tls, K.tls_pos);
-                if (K.tls != 0xFF && (st == TLS_R || st == TLS_Y) && seen >= bgv) stop_here = true;
-                if (!stop_here && !(K.flags & KF_CONT) && ((K.flags & KF_MINOR) || (K.tls != 0xFF && st == TLS_g))) {
-                    // a minor link is approached ready to stop until the foe lanes can be seen
-                    if (seen > RM_VIS_DIST) stop_here = true;
-                    else if (K.foe_cnt > 0 && foe_blocked(T, L, grid, K)) stop_here = true;
-                }
+            const bool none = link == NLINK_NONE;
+            // (the record of link 0 for a lane without one: every table holds at least one record, and nothing of it is used)
+            const LinkRec K = link_load(T.links(), none ? 0 : link);
+            const bool sig = !none & (K.tls != 0xFF);
+            const int st0 = L.tstate[sig ? K.tls * T.tls_maxl + K.tls_pos : 0];
+            const int st = sig ? st0 : (int)TLS_G;
+            // no link: the last edge of the route -- free run to its end --, otherwise a dead end: wait for a lane change
+            bool route_end = false;
+            if (none) route_end = !cur_int && rs_at(T.rsteps(), rq).next_edge == 0xFFFF;
+            const bool red = (st == TLS_R) | (st == TLS_Y);
+            const bool red_stop = red & (seen >= bgv);          // (a red / yellow light I can no longer stop at is passed)
+            // a minor link is approached ready to stop until the foe lanes can be seen
+            const bool minor = !none & !red_stop & !(K.flags & KF_CONT) & (((K.flags & KF_MINOR) != 0) | (st == TLS_g));
+            const bool far = minor & (seen > RM_VIS_DIST);
+            bool stop_here = (none & !route_end) | red_stop | far;
+            if (none & route_end) RS_COUNT(RC_ROUTE_END)
+            if (none & !route_end) RS_COUNT(RC_DEAD_END)
+            if (red_stop) RS_COUNT(RC_STOP_RED)
+            if (red & !red_stop) RS_COUNT(RC_RED_TOO_CLOSE)
+            if (far) RS_COUNT(RC_MINOR_FAR)
+            if (minor && !far && K.foe_cnt > 0) {
+                RS_COUNT(RC_FOE_IN)
+                if (foe_blocked(T, L, grid, K)) { RS_COUNT(RC_FOE_BLOCKED) stop_here = true; }
             }
-            if (stop_here) {
+            {   // a stop line = a standing leader of zero length: d_follow_speed(g, 0, b, b) == d_stop_speed(g, b)
                 const float g = seen - RM_STOP_OFFSET;
-                tgap = g > 0.0f ? g : 0.0f; tvl = 0.0f; tbl = b;       // d_follow_speed(g, 0, b, b) == d_stop_speed(g, b)
-                have = true;
-                break;
+                tgap = stop_here ? (g > 0.0f ? g : 0.0f) : tgap; tvl = stop_here ? 0.0f : tvl; tbl = stop_here ? b : tbl;
             }
-            LR = K.dest;
-            cur_lane = K.to_lane;
-            {   // slow down in time for a lower speed limit on the next lane
-                const float vnl = LR.vmax * sf;
-                if (vnl < vfree) {
-                    const float vs = d_free_speed(seen, vnl, b);
-                    if (vs < vsafe) vsafe = vs;
+            const bool cont = !none & !stop_here;
+            bool hit = false;
+            if (cont) {
+                LR = K.dest;
+                cur_lane = K.to_lane;
+                {   // slow down in time for a lower speed limit on the next lane
+                    const float vnl = LR.vmax * sf;
+                    if (vnl < vfree) {
+                        const float vs = d_free_speed(seen, vnl, b);
+                        if (vs < vsafe) vsafe = vs;
+                    }
                 }
+                const Found od = rearmost_within(L, grid, LR.cell0, lane_cells(L, LR), look - seen + T.maxlen);
+                hit = od.slot != NIL;
+                const float *vo = L.vtp + od.vt() * VT_COLS;        // (nobody there: the row of vType 0, selected away)
+                tgap = hit ? seen + od.pos() - vo[VT_LENGTH] - mingap : tgap;
+                tvl = hit ? od.speed() : tvl; tbl = hit ? vo[VT_DECEL] : tbl;
+                // (seen, rq and LR are dead after the walk: a lane that found its leader may update them too)
+                rq += cur_int ? 0 : 1;
+                seen += LR.len;
             }
-            const Found od = rearmost_within(L, grid, LR.cell0, lane_cells(L, LR), look - seen + T.maxlen);
-            if (od.slot != NIL) {
-                const float *vo = L.vtp + od.vt() * VT_COLS;
-                tgap = seen + od.pos() - vo[VT_LENGTH] - mingap;
-                tvl = od.speed(); tbl = vo[VT_DECEL];
-                have = true;
-                break;
-            }
-            if (!cur_int) rq += 1;
-            seen += LR.len;
-            if (!(seen < look)) break;
+            have |= stop_here | hit;
+            if (hit) RS_COUNT(RC_NEXT_LEADER)
+            if (cont & !hit & !(seen < look)) RS_COUNT(RC_LOOK_DONE)
+            go = cont & !hit & (seen < look);
         }
+        if (go) RS_COUNT(RC_MAX_HOPS)
     }
     if (LONG) RS_SEC(10)
     if (have) {
@@ -1268,6 +1305,7 @@ template <class TT, class LT, class GT> RS_DEV int phase_lc_decide(const TT &T, 
     const ContRow R = cont_row(T, ax.rq);
     const LaneRec LR = rec_load16(T.lanes(), lane);     // (after the row: the record's wait covers both, see phase_move)
 #endif
+    const uint32_t nbm = rs_at(T.notbest(), ax.rq);     // (the signs of R as one word: strategic_dir)
     const int my_wait = (int)ax.swait;
     const int n = LR.flags >> 2;
     if ((LR.flags & LF_INTERNAL) || n < 2) return 0;
@@ -1279,36 +1317,40 @@ template <class TT, class LT, class GT> RS_DEV int phase_lc_decide(const TT &T, 
     const int nc = lane_cells(L, LR);
     int want = 0, dir = dir_allowed;
     float rem;
-    const int sdir = strategic_dir(R, kk, n, x, v, 0, rem, grid, LR.cell0, nc, T.occ_unit);
-    if (sdir != 0) { dir = sdir; want = 2; }
+    const int sdir = strategic_dir(R, nbm, kk, n, x, v, 0, rem, grid, LR.cell0, nc, T.occ_unit);
+    if (sdir != 0) { RS_COUNT(RC_STRATEGIC) dir = sdir; want = 2; }
     int code = 0;
     const int tk = kk + dir;
     if (tk >= 0 && tk < n) {
         const int tcell0 = (int)LR.cell0 + dir * nc;        // lanes of an edge own consecutive, equally sized cell blocks
         int lead_t = NIL, foll_t = NIL;
-        bool have_t = false;
+        // speed gain between lanes that are both good: more room ahead on the neighbour.  A vehicle reconsiders only on
+        // one pair of ticks (one left, one right chance) out of four.  sg: a candidate whose neighbour lane is good enough
+        bool sg = false;
         if (!want && !((((uint32_t)t >> 1) + (uint32_t)k) & 3u)) {
-            // speed gain between lanes that are both good: more room ahead on the neighbour.  A vehicle reconsiders only on
-            // one pair of ticks (one left, one right chance) out of four
             float rem_t;
-            if (strategic_dir(R, tk, n, x, v, RM_SG_EXTRA_LANES, rem_t, grid, tcell0, nc, T.occ_unit) == 0) {
-                const int lead_c = leader_within(L, grid, LR.cell0, nc, x, k, s, RM_NB_WINDOW);
-                if (lead_c != NIL) {
-                    lead_t = leader_within(L, grid, tcell0, nc, x, k, s, RM_NB_WINDOW);
-                    have_t = true;
-                    const float gcur = L.node[lead_c].pos - L.vtp[L.node[lead_c].vt * VT_COLS + VT_LENGTH] - x;
-                    float gtgt = RM_BIGF;
-                    if (lead_t != NIL) gtgt = L.node[lead_t].pos - L.vtp[L.node[lead_t].vt * VT_COLS + VT_LENGTH] - x;
-                    if (gcur < v * 3.0f + 15.0f && gtgt > gcur + RM_SG_ADVANTAGE) want = 1;
-                }
-            }
+            sg = strategic_dir(R, nbm, tk, n, x, v, RM_SG_EXTRA_LANES, rem_t, grid, tcell0, nc, T.occ_unit) == 0;
+        }
+        int lead_c = NIL;
+        if (sg) { RS_COUNT(RC_SG) lead_c = leader_within(L, grid, LR.cell0, nc, x, k, s, RM_NB_WINDOW); }
+        // ONE search for the leader on the target lane, reached together by the lanes that want the change and by the speed-gain
+        // candidates that have a leader on their own lane (a wave runs every copy of a search that any of its lanes needs)
+        const bool sgl = sg && lead_c != NIL;
+        if (want || sgl) lead_t = leader_within(L, grid, tcell0, nc, x, k, s, RM_NB_WINDOW);
+        if (sgl) {
+            RS_COUNT(RC_SG_LEAD)
+            const float gcur = L.node[lead_c].pos - L.vtp[L.node[lead_c].vt * VT_COLS + VT_LENGTH] - x;
+            float gtgt = RM_BIGF;
+            if (lead_t != NIL) gtgt = L.node[lead_t].pos - L.vtp[L.node[lead_t].vt * VT_COLS + VT_LENGTH] - x;
+            if (gcur < v * 3.0f + 15.0f && gtgt > gcur + RM_SG_ADVANTAGE) { RS_COUNT(RC_SG_WANT) want = 1; }
         }
         if (want) {
-            if (!have_t) lead_t = leader_within(L, grid, tcell0, nc, x, k, s, RM_NB_WINDOW);
             foll_t = follower_within(L, grid, tcell0, nc, x, k, s, RM_NB_WINDOW);
             // urgent = strategic change close to the end of the drivable lane: accept tighter gaps (followers may have to
             // brake with their emergency deceleration), otherwise dense queues would never let anybody in
             const bool urgent = want == 2 && rem <= RM_URGENT_DIST;
+            if (urgent) RS_COUNT(RC_URGENT)
+            if (foll_t != NIL) RS_COUNT(RC_FOLL_T)
             bool safe = true;
             if (lead_t != NIL) {
                 const Node ld = L.node[lead_t];
@@ -1329,13 +1371,13 @@ template <class TT, class LT, class GT> RS_DEV int phase_lc_decide(const TT &T, 
             if (safe) {
                 // (a vehicle that leaves its lane in this tick changes lanes on the next edge, if at all -- its plan looked at
                 //  the links of the lane it is on: the move phase, which knows the next speed, drops the change then)
-                if (dir == dir_allowed) code = dir > 0 ? LCT_LEFT : LCT_RIGHT;
+                if (dir == dir_allowed) { RS_COUNT(RC_CHANGE) code = dir > 0 ? LCT_LEFT : LCT_RIGHT; }
             } else if (want == 2) {
                 // blocked: fall in behind the target-lane leader, and ask the nearest vehicle completely behind me on the
                 // target lane to let me in
-                if (lead_t != NIL) { G.cooplead(t & 1)[eo + s] = ((uint32_t)L.node[lead_t].trip << 16) | (uint32_t)lead_t; mail_flag_set(L, s, t & 1); }
+                if (lead_t != NIL) { RS_COUNT(RC_LEAD_REQ) G.cooplead(t & 1)[eo + s] = ((uint32_t)L.node[lead_t].trip << 16) | (uint32_t)lead_t; mail_flag_set(L, s, t & 1); }
                 const int R = at_or_behind_within(L, grid, tcell0, nc, x - vt[VT_LENGTH], RM_COOP_RANGE);
-                if (R != NIL) { rs_atomic_min(&G.coop(t & 1)[eo + R], ((uint32_t)k << 16) | (uint32_t)s); mail_flag_set(L, R, t & 1); }
+                if (R != NIL) { RS_COUNT(RC_COOP_REQ) rs_atomic_min(&G.coop(t & 1)[eo + R], ((uint32_t)k << 16) | (uint32_t)s); mail_flag_set(L, R, t & 1); }
             }
         }
     }
@@ -1349,9 +1391,9 @@ template <class TT, class LT, class GT> RS_DEV int phase_lc_decide(const TT &T, 
             const Node nb = L.node[b];
             float rem_b;
             if (nb.speed <= RM_HALT_SPEED && (int)L.aux[b].swait >= RM_SWAP_WAIT &&
-                strategic_dir(cont_row(T, L.aux[b].rq), kk + sdir, n, nb.pos, nb.speed, 0, rem_b, grid, (int)LR.cell0 + sdir * nc, nc, T.occ_unit) == -sdir && rem_b <= RM_URGENT_DIST &&
+                strategic_dir(cont_row(T, L.aux[b].rq), rs_at(T.notbest(), L.aux[b].rq), kk + sdir, n, nb.pos, nb.speed, 0, rem_b, grid, (int)LR.cell0 + sdir * nc, nc, T.occ_unit) == -sdir && rem_b <= RM_URGENT_DIST &&
                 overlapping(L, grid, LR.cell0, nc, nb.pos, nb.trip, b, L.vtp[nb.vt * VT_COLS + VT_LENGTH]) == s)
-                code |= sdir > 0 ? LCT_SWAP_LEFT : LCT_SWAP_RIGHT;
+                { RS_COUNT(RC_SWAP) code |= sdir > 0 ? LCT_SWAP_LEFT : LCT_SWAP_RIGHT; }
         }
     }
         return code;
