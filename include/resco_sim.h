@@ -472,6 +472,24 @@ void rs_ppo_destroy(rs_ppo_handle p);
  * next rs_dqn_update draws with update_key = t; no launch and no synchronisation, what is enqueued afterwards sees it; RS_EINVAL for t < 0.
  * rs_dqn_update: for j < n_updates: rs_dqn_sample with update_key = the step count so far into the handle's own index array,
  * rs_dqn_grad, rs_dqn_step -- the same launches, all enqueued by one call without host synchronisation or copies.
+ * rs_dqn_set_target: the target's options, n_step in 1 .. 32 (n-step returns) and double_q 0 / 1 (Double DQN); a new handle has (1, 0),
+ * PFRL's plain one-step DQN as described above, and at (1, 0) exactly those launches run.  The host-side fields alone, like
+ * rs_dqn_set_steps: no launch, no synchronisation, what is enqueued afterwards sees them; RS_EINVAL with a text and the handle
+ * unchanged for a NULL handle, n_step outside 1 .. 32 or double_q outside 0 / 1.  rs_dqn_get_target: the pair as it stands.
+ * The draw does not depend on the options.  With them rs_dqn_grad's target of row (t, e) of signal s is, with T = capacity and
+ * newest = (head - 1) mod T the one written slot without a successor:
+ *   the walk: u_0 = t; step j = 0, 1, .. takes rew[u_j][e][s] and the walk stops after it where done[u_j] (cut), where j + 1 == n_step,
+ *   or where (u_j + 1) mod T == newest; m = j + 1 rewards were taken, 1 <= m <= n_step, and u_m = (t + m) mod T.  It reads done and rew
+ *   of u_0 .. u_{m-1} only, obs[u_m] only when not cut, nothing of an unwritten slot, neither reward nor action of `newest`, and
+ *   nothing behind a cut (a cut is not a bootstrap multiplied by zero).  It truncates at the newest slot instead of waiting for n
+ *   successors as PFRL's n-step buffer would: a row is a row as soon as it has one successor.
+ *   the arithmetic, fp32, in this order: R = rew_0, g = gamma; for j = 1 .. m - 1: R = R + g rew_j, g = g gamma; tgt = R where cut,
+ *   else R + g boot.
+ *   boot: double_q 0: max_{a < A_s} Q_target(obs[u_m][e][s])[a]; double_q 1: Q_target(obs[u_m][e][s])[a*] with a* = argmax_{a < A_s}
+ *   Q_online(obs[u_m][e][s])[a], the lowest index among equal maxima, the online network being params as they stand when the
+ *   gradient is taken (before that update's Adam step).
+ * rs_dqn_grad takes its rows from the caller: a row at `newest` is the caller's mistake as before; the walk is bounded by n_step and
+ * by mod T, so such a row reads wrong data but never outside the ring.
  * All calls are asynchronous on `stream`; every sum has one fixed order (no float atomics): the same state gives the same bits.
  * Workspace, allocated once by rs_dqn_create for max_batch rows and padded to lmax for every signal.
  * Refusals (RS_EINVAL, text in rs_last_error(NULL), nothing launched): a NULL handle or pointer, batch outside 1 .. max_batch,
@@ -504,6 +522,8 @@ int rs_dqn_update(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t batch, uint3
                   void *stream);
 int64_t rs_dqn_steps(rs_dqn_handle p);
 int rs_dqn_set_steps(rs_dqn_handle p, int64_t t);
+int rs_dqn_set_target(rs_dqn_handle p, int32_t n_step, int32_t double_q);
+int rs_dqn_get_target(rs_dqn_handle p, int32_t *n_step, int32_t *double_q);
 void rs_dqn_destroy(rs_dqn_handle p);
 
 /* ---- MPLight: the shared-DQN update on the device (resco_amd/csrc/resco_frap_train.h) -------------------------------

@@ -86,8 +86,10 @@ class DeviceReplay:
         if not weights_only:
             _state.load_ring_state(self, sd, 'DeviceReplay')
 
-    def sample(self, batch_size, generator=None):
-        """Independent minibatch per signal: returns o [B,S,L,5], a [B,S] long, r [B,S], o2 [B,S,L,5], d [B,S] float."""
+    def sample(self, batch_size, generator=None, n_step=1, gamma=None):
+        """Independent minibatch per signal: returns o [B,S,L,5], a [B,S] long, r [B,S], o2 [B,S,L,5], d [B,S] float.
+        n_step > 1 (needs gamma): the same rows from the same draws, with r the discounted sum of the walk's rewards, o2 the
+        observation the walk ends at, d the cut flag, and a sixth element disc = gamma^m (nstep_walk)."""
         n_ok = self.count - 1                       # slots with a written successor
         assert n_ok >= 1, 'need two pushes before sampling'
         dev = self.obs.device
@@ -96,13 +98,56 @@ class DeviceReplay:
         k = torch.randint(0, n_ok, (B, S), device=dev, generator=generator)
         t = (self.head - self.count + k) % self.T
         e = torch.randint(0, self.N, (B, S), device=dev, generator=generator)
-        t2 = (t + 1) % self.T
-        sig = self._sig
-        return (self.obs[t, e, sig], self.act[t, e, sig].long(), self.rew[t, e, sig], self.obs[t2, e, sig],
-                self.done[t].to(torch.float32))
+        return _rows(self, t, e, self.head, n_step, gamma)
 
 
-def _sample_from_device_position(rp, batch_size):
+def nstep_walk(rp, t, e, head, n_step, gamma):
+    """The n-step walk of rows (t, e) [B, S] of the ring rp, vectorised: n_step masked steps, no data-dependent control flow, `head`
+    a Python int or a device scalar (so it can be captured in a HIP graph).  newest = (head - 1) mod T is the one written slot
+    without a successor.  u_0 = t; step j takes rew[u_j] and the walk stops after it where done[u_j] (cut), where j + 1 == n_step, or
+    where (u_j + 1) mod T == newest; m = j + 1.  In the ring's float32 and in this order: R = rew_0, g = gamma; for j = 1 .. m - 1:
+    R = R + g rew_j, g = g gamma.  -> (R [B, S], u_m = (t + m) mod T [B, S], cut [B, S] bool, g = gamma^m [B, S]).
+    Truncated at the newest slot (PFRL's n-step buffer would wait for n successors); rs_dqn_set_target of include/resco_sim.h is the
+    same definition for the fused update."""
+    T, sig = rp.T, rp._sig
+    newest = (head - 1) % T
+    u = t
+    R = rp.rew[t, e, sig]
+    g = torch.full_like(R, float(gamma))
+    cut = rp.done[t]
+    stopped = cut | ((u + 1) % T == newest)
+    for _ in range(1, int(n_step)):
+        alive = ~stopped
+        u = torch.where(alive, (u + 1) % T, u)
+        R = torch.where(alive, R + g * rp.rew[u, e, sig], R)
+        g = torch.where(alive, g * float(gamma), g)
+        ended = rp.done[u] & alive
+        cut = cut | ended
+        stopped = stopped | ended | ((u + 1) % T == newest)
+    return R, (u + 1) % T, cut, g
+
+
+def _rows(rp, t, e, head, n_step, gamma):
+    """what sample returns for the rows (t, e): five tensors at n_step 1, six beyond"""
+    sig = rp._sig
+    if int(n_step) == 1:
+        return (rp.obs[t, e, sig], rp.act[t, e, sig].long(), rp.rew[t, e, sig], rp.obs[(t + 1) % rp.T, e, sig], rp.done[t].to(torch.float32))
+    assert 1 < int(n_step) <= 32 and gamma is not None, 'n-step rows need 1 <= n_step <= 32 and gamma'
+    R, u_m, cut, disc = nstep_walk(rp, t, e, head, n_step, gamma)
+    return (rp.obs[t, e, sig], rp.act[t, e, sig].long(), R, rp.obs[u_m, e, sig], cut.to(torch.float32), disc)
+
+
+def target_options_signature(fields, n_step, double_q):
+    """the learners' signature rule for the target's options: a key only where it differs from the default, so that a checkpoint
+    written before the options existed loads into a default learner and any other mix is refused by the field comparison"""
+    if int(n_step) != 1:
+        fields['n_step'] = int(n_step)
+    if double_q:
+        fields['double_q'] = True
+    return fields
+
+
+def _sample_from_device_position(rp, batch_size, n_step=1, gamma=None):
     """DeviceReplay.sample with the ring position read from device memory and PyTorch's default generator: every value
     that changes between calls lives on the device, so the call can be captured in a HIP graph and replayed."""
     dev = rp.obs.device
@@ -113,9 +158,7 @@ def _sample_from_device_position(rp, batch_size):
     k = torch.minimum(k, n_ok - 1)
     t = torch.remainder(head - count + k, rp.T)
     e = torch.randint(0, rp.N, (B, S), device=dev)
-    t2 = torch.remainder(t + 1, rp.T)
-    sig = rp._sig
-    return (rp.obs[t, e, sig], rp.act[t, e, sig].long(), rp.rew[t, e, sig], rp.obs[t2, e, sig], rp.done[t].to(torch.float32))
+    return _rows(rp, t, e, head, n_step, gamma)
 
 
 def linear_epsilon(t, start, end, decay_steps):
@@ -128,8 +171,12 @@ def linear_epsilon(t, start, end, decay_steps):
 class BatchedDQNLearner:
     """DQN update for the S stacked per-signal networks of a BatchedIDQN."""
 
-    def __init__(self, qnet, gamma=0.99, lr=1e-3, target_update=500, batch_size=32):
+    def __init__(self, qnet, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, n_step=1, double_q=False):
+        """n_step (1 .. 32): n-step returns (nstep_walk); double_q: Double DQN's bootstrap.  The defaults are PFRL's plain DQN."""
         assert isinstance(qnet, BatchedIDQN)
+        self.n_step, self.double_q = int(n_step), bool(double_q)
+        if not 1 <= self.n_step <= 32:
+            raise ValueError('BatchedDQNLearner: n_step must be in 1 .. 32, got %d' % self.n_step)
         self.q = qnet
         self.target = copy.deepcopy(qnet)
         for p in self.target.parameters():
@@ -142,14 +189,19 @@ class BatchedDQNLearner:
         self._fc1_mask = fc1_row_mask(qnet.lanes, qnet.lmax, qnet.fc1_w.dtype, qnet.fc1_w.device)
         qnet.fc1_w.register_hook(lambda g: g * self._fc1_mask)
 
-    def loss(self, o, a, r, o2, d):
+    def loss(self, o, a, r, o2, d, disc=None):
         """Sum over signals of the mean Huber loss of each signal's minibatch.  Inputs as DeviceReplay.sample()
-        returns them, but signal-major batches ([B,S,...]) are read as 'B independent draws per signal'."""
+        returns them, but signal-major batches ([B,S,...]) are read as 'B independent draws per signal'.
+        disc: the discount of the bootstrap per row (gamma^m of an n-step row); None: gamma."""
         q = self.q(o)                                               # [B, S, Amax]
         y = q.gather(-1, a.unsqueeze(-1)).squeeze(-1)               # [B, S]
         with torch.no_grad():
-            nxt = self.target(o2).max(dim=-1).values                # padded actions are -inf: never the max
-            tgt = r + self.gamma * (1.0 - d) * nxt
+            if self.double_q:                                       # the online network's best action (the first of equal maxima),
+                best = self.q(o2).argmax(dim=-1, keepdim=True)      # valued by the target network
+                nxt = self.target(o2).gather(-1, best).squeeze(-1)
+            else:
+                nxt = self.target(o2).max(dim=-1).values            # padded actions are -inf: never the max
+            tgt = r + (self.gamma if disc is None else disc) * (1.0 - d) * nxt
         per = torch.nn.functional.smooth_l1_loss(y.float(), tgt.float(), reduction='none')   # Huber, delta 1
         return per.mean(dim=0).sum()
 
@@ -175,7 +227,7 @@ class BatchedDQNLearner:
 
         def one():
             self.opt.zero_grad(set_to_none=False)
-            loss = self.loss(*_sample_from_device_position(replay, self.batch_size))
+            loss = self.loss(*_sample_from_device_position(replay, self.batch_size, self.n_step, self.gamma))
             loss.backward()
             self.opt.step()
             return loss.detach()
@@ -208,7 +260,7 @@ class BatchedDQNLearner:
     # ---- checkpoints (resco_amd/checkpoint.py).  Everything is loaded IN PLACE, so a learner whose update has been graph-captured
     # (capture_update) keeps its graph: the graph reads the parameters, the gradients and the optimizer's state tensors by address.
     def signature(self):
-        return {'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}
+        return target_options_signature({'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}, self.n_step, self.double_q)
 
     def state_dict(self):
         return {'weights': {'target': _state.module_tensors(self.target)},
@@ -234,5 +286,5 @@ class BatchedDQNLearner:
                     self.n_updates += 1
                     out = self._graph_loss
                 else:
-                    out = self.update(replay.sample(self.batch_size, generator))
+                    out = self.update(replay.sample(self.batch_size, generator, self.n_step, self.gamma))
         return out

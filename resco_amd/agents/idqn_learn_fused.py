@@ -17,6 +17,7 @@ import torch
 
 from ..sim import DQN_TENSORS, DQNConfig, DQNRing, DQNTensors, torch_stream
 from . import _state
+from .idqn_learn import target_options_signature
 from .idqn_rollout import BatchedIDQN
 from .learn_fused import FusedLearnerBase
 
@@ -24,9 +25,15 @@ from .learn_fused import FusedLearnerBase
 class FusedDQNLearner(FusedLearnerBase):
     NAME, PREFIX, TENSORS, TENSOR_SET = 'FusedDQNLearner', 'rs_dqn', DQN_TENSORS, DQNTensors
 
-    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, seed=0):
+    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, seed=0, n_step=1, double_q=False):
+        """n_step (1 .. 32): n-step returns, truncated at the newest slot of the ring and cut at an episode end; double_q: the
+        bootstrap is the target network's value of the online network's best action (rs_dqn_set_target has the definition).  The
+        defaults are PFRL's plain one-step DQN."""
         assert isinstance(net, BatchedIDQN)
         super().__init__(net)
+        self.n_step, self.double_q = int(n_step), bool(double_q)
+        if not 1 <= self.n_step <= 32:
+            raise ValueError('FusedDQNLearner: n_step must be in 1 .. 32, got %d' % self.n_step)
         self.gamma, self.lr, self.adam_eps = float(gamma), float(lr), 1e-8
         self.batch_size, self.target_update, self.seed = int(batch_size), int(target_update), int(seed) & 0xFFFFFFFF
         self.t = 0              # agent steps seen (PFRL's self.t)
@@ -34,6 +41,12 @@ class FusedDQNLearner(FusedLearnerBase):
         for p in self.target.parameters():
             p.requires_grad_(False)
         self._create(DQNConfig(self.lr, self.adam_eps, 0.9, 0.999, self.gamma), self.batch_size, more_nets=(self.target,))     # (a CPU net raises)
+        if (self.n_step, self.double_q) != (1, False):
+            if not hasattr(self._lib, 'rs_dqn_set_target'):
+                raise RuntimeError('the loaded library has no rs_dqn_set_target: rebuild it (there is no CPU fallback)')
+            rc = self._lib.rs_dqn_set_target(self._h, self.n_step, int(self.double_q))
+            if rc != 0:
+                self._fail('rs_dqn_set_target', rc)
 
     def _ring(self, replay):
         """rs_dqn_ring over a DeviceReplay's own arrays (no copies) at its present position"""
@@ -92,7 +105,7 @@ class FusedDQNLearner(FusedLearnerBase):
     # ---- checkpoints (resco_amd/checkpoint.py): in place, the library has borrowed target, m and v; its step count goes back
     # through rs_dqn_set_steps (the bias correction's t and the key of the next minibatch draw)
     def signature(self):
-        return {'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}
+        return target_options_signature({'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}, self.n_step, self.double_q)
 
     def state_dict(self):
         return {'weights': {'target': _state.module_tensors(self.target)},

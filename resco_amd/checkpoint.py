@@ -143,10 +143,11 @@ def load(path, *, agent, map_name, objects, strict=True, hyper=None):
             if theirs[k] != ours[k]:
                 raise _mismatch(k, theirs[k], ours[k])
         for kind in ('fields', 'tensors'):
-            for k in sorted(set(theirs[kind]) | set(ours[kind])):
-                a, b = theirs[kind].get(k, '(absent)'), ours[kind].get(k, '(absent)')
-                if _plain(a) != _plain(b):
-                    raise _mismatch(k, a, b)
+            differ = lambda k: _plain(theirs[kind].get(k, '(absent)')) != _plain(ours[kind].get(k, '(absent)'))
+            bad = [k for k in sorted(set(theirs[kind]) | set(ours[kind])) if differ(k)]
+            if bad:         # the first in full, the others by name
+                e = _mismatch(bad[0], theirs[kind].get(bad[0], '(absent)'), ours[kind].get(bad[0], '(absent)'))
+                raise e if len(bad) == 1 else ValueError('%s (and in %s)' % (e, ', '.join(bad[1:])))
     else:
         for name, obj in objects.items():
             if name not in theirs['objects']:

@@ -9,7 +9,8 @@
 //
 // The network, its forward and backward, the reduction and the Adam body are resco_train.h's, with NH = 8 head columns (no value
 // head: the tensor sets leave PT_V_W and PT_V_B NULL) and NL = 1 loss term.  This file adds the draw (dqn_sample_index), the per-row
-// loss gradient (dqn_row_loss_grad; both built for the host as well by tests/dqn_train_host), the minibatch and the kernels.
+// loss gradient (dqn_row_loss_grad; both built for the host as well by tests/dqn_train_host), the n-step walk (dqn_nstep_walk; built for
+// the host by tests/dqn_nstep_host), the minibatch and the kernels.
 //
 // Launches of one minibatch gradient (rs_dqn_grad); row i of signal s is ring row idx[i][s] = (slot t, environment e):
 //   1. dqn_target_kernel, one workgroup per (64-row tile, signal): the TARGET network forward on the successor row ((t + 1) mod T, e)
@@ -20,6 +21,23 @@
 //   2. dqn_fwd_bwd_kernel;  3. dqn_fc1_bwd_kernel;  4. dqn_reduce_kernel
 // and of one optimiser step (rs_dqn_step): dqn_adam_kernel (PFRL's DQN does not clip gradients: scale {1, 0}).
 // rs_dqn_sample is dqn_sample_kernel.  A target network may hold anything in its padded fc1_w rows and fc3 columns.
+//
+// The options of rs_dqn_set_target (n-step returns, Double DQN; PFRL's IDQN uses neither).  With either one on, launch 1 is
+// dqn_target_opt_kernel<DOUBLE_Q> instead; launches 2 - 4, the draw and the Adam step are the same, and with both off nothing of this
+// is launched: dqn_target_kernel stays as it is.
+//   n_step: every row lane walks its row forward through the ring (dqn_nstep_walk: at most n_step dependent one-byte loads of done,
+//   then as many four-byte loads of rew, small beside the fc1 MFMA chain), keeps R = sum_j gamma^j rew_j and g = gamma^m, and names
+//   slot (t + m) mod T as the row the tile loads; tgt = R + g boot, or R alone where an episode end cut the walk (nothing is read
+//   behind it).  The walk TRUNCATES at the newest slot: a row less than n_step slots behind it bootstraps from the newest observation
+//   after fewer rewards.  PFRL's n-step buffer instead holds a transition back until its n successors exist; here the ring is read in
+//   place and a row is a row as soon as it has one successor, so the draw is the same whatever the options.
+//   double_q: boot = Q_target[argmax_a Q_online[a]] on the same successor rows, the lowest index among equal maxima; the online network
+//   is T.par as it stands at this launch, before the update's Adam step.  A second load and forward in the SAME workgroup, not a
+//   launch of its own: the successor rows have just been walked to (a launch of its own would walk them again or pass 64-bit row
+//   names through memory), a* stays in LDS, and the argument for two launches above does not apply -- the online forward of the
+//   successor rows must finish before the target's max in any case, so a separate launch would put one more launch gap on the
+//   same dependent chain and run on the same tiles x S workgroups.
+//   The cost is one more tile forward in launch 1, paid only with double_q on.
 #pragma once
 #include "resco_train.h"
 
@@ -56,6 +74,24 @@ RS_DQN_DEV void dqn_sample_index(uint32_t seed, uint32_t u, uint32_t s, uint32_t
     out[1] = (int32_t)e;
 }
 
+// The n-step walk of the row at slot t of a ring of T slots whose next slot to write is head: newest = (head - 1) mod T is the one
+// written slot without a successor.  u_0 = t; step j takes the reward of u_j = (t + j) mod T and the walk stops after it where
+// done[u_j] (*cut = 1: an episode ended, nothing behind it is read), where j + 1 == n_step, or where (u_j + 1) mod T == newest (the
+// bootstrap row may be the newest slot, a reward may not).  *m = j + 1 rewards were taken, 1 <= *m <= max(n_step, 1); the bootstrap
+// row of a walk that was not cut is (t + *m) mod T.  Reads done[u_0 .. u_{m-1}] only.  A t at `newest` is the caller's mistake: the
+// walk then runs its n_step slots round the ring, over wrong data but never outside it.  Needs T >= 1, 0 <= t, head < T.
+RS_PPO_HD void dqn_nstep_walk(const uint8_t *done, int T, int head, int t, int n_step, int *m, int *cut) {
+    const int newest = head == 0 ? T - 1 : head - 1;
+    int u = t, j = 0;
+    for (;;) {
+        const int nxt = u + 1 == T ? 0 : u + 1;
+        const bool d = done[u] != 0;
+        ++j;
+        if (d || j >= n_step || nxt == newest) { *m = j; *cut = d ? 1 : 0; return; }
+        u = nxt;
+    }
+}
+
 #ifdef __HIPCC__
 struct DqnTrainTab : PptTab {
     PptTensors tgt;                         // the target network (borrowed like the parameters, only read)
@@ -71,6 +107,7 @@ struct DqnBatch {
     int32_t T, N;
     const int32_t *idx;                     // [B][S][2]: (t, e)
     int32_t B;
+    int32_t head;                           // the ring's next slot to write (the n-step walk stops before the newest slot, head - 1)
     // slot and environment of row i of signal s, held inside the ring whatever idx says
     __device__ void at(int i, int s, int S, int *t, int *e) const {
         const int32_t *p = idx + ((size_t)i * S + s) * 2;
@@ -119,6 +156,69 @@ __global__ void __launch_bounds__(PPT_T, 2) dqn_target_kernel(DqnTrainTab T, Dqn
                 float mx = L.lg[tid * DQN_NH];
                 for (int a = 1; a < X.A; ++a) mx = L.lg[tid * DQN_NH + a] > mx ? L.lg[tid * DQN_NH + a] : mx;
                 y = y + T.gamma * mx;
+            }
+        }
+        T.y[(size_t)s * T.bpad_max + X.r0 + tid] = y;
+    }
+}
+
+// ---------------------------------------------------------------- 1'. the rows' targets with n-step returns and / or Double DQN
+// (the file's header has the semantics).  Arithmetic in fp32, this order: R = rew_0, g = gamma; for j = 1 .. m - 1: R = R + g rew_j,
+// g = g gamma; tgt = cut ? R : R + g boot -- at n_step 1 what dqn_target_kernel computes.
+template <bool DOUBLE_Q> __global__ void __launch_bounds__(PPT_T, 2) dqn_target_opt_kernel(DqnTrainTab T, DqnBatch D, int n_step) {
+    __shared__ PptTileLds<DQN_NH> L;
+    __shared__ float ret_s[PPT_TM], disc_s[PPT_TM];
+    __shared__ int astar_s[PPT_TM];
+    const PptTile X = ppt_tile(T, D.B);
+    const int tid = X.tid, S = T.S, s = X.s;
+    if (tid < PPT_TM) {
+        long long nxt = -1;
+        float R = 0.0f, g = T.gamma;
+        if (tid < X.nrows) {
+            int t, e, m, cut;
+            D.at(X.r0 + tid, s, S, &t, &e);
+            dqn_nstep_walk(D.done, D.T, min(max(D.head, 0), D.T - 1), t, n_step, &m, &cut);
+            int u = t;
+            R = D.rew[((size_t)u * D.N + e) * S + s];
+            for (int j = 1; j < m; ++j) {
+                u = u + 1 == D.T ? 0 : u + 1;
+                R = R + g * D.rew[((size_t)u * D.N + e) * S + s];
+                g = g * T.gamma;
+            }
+            if (!cut) nxt = (long long)(u + 1 == D.T ? 0 : u + 1) * D.N + e;            // an episode end cuts the bootstrap: nothing is read
+        }
+        ret_s[tid] = R; disc_s[tid] = g; L.src[tid] = nxt; astar_s[tid] = 0;
+    }
+    __syncthreads();
+    if constexpr (DOUBLE_Q) {           // the online network on the successor rows: a* = its best action, the lowest index among equals
+        ppt_tile_load(T.par, T, X, D.obs, L);
+        __syncthreads();
+        ppt_tile_forward(T.par, T, X, L);
+        if (tid < PPT_TM) {
+            int best = 0;
+            float mx = L.lg[tid * DQN_NH];
+            for (int a = 1; a < X.A; ++a)
+                if (L.lg[tid * DQN_NH + a] > mx) { mx = L.lg[tid * DQN_NH + a]; best = a; }
+            astar_s[tid] = best;
+        }
+        __syncthreads();
+    }
+    ppt_tile_load(T.tgt, T, X, D.obs, L);
+    __syncthreads();
+    ppt_tile_forward(T.tgt, T, X, L);
+    if (tid < PPT_TM) {
+        float y = 0.0f;
+        if (tid < X.nrows) {
+            y = ret_s[tid];
+            if (L.src[tid] >= 0) {
+                float boot;
+                if constexpr (DOUBLE_Q) {
+                    boot = L.lg[tid * DQN_NH + astar_s[tid]];
+                } else {
+                    boot = L.lg[tid * DQN_NH];
+                    for (int a = 1; a < X.A; ++a) boot = L.lg[tid * DQN_NH + a] > boot ? L.lg[tid * DQN_NH + a] : boot;
+                }
+                y = y + disc_s[tid] * boot;
             }
         }
         T.y[(size_t)s * T.bpad_max + X.r0 + tid] = y;

@@ -1175,6 +1175,7 @@ struct DqnHandle : TrainHandle {
 struct rs_dqn : DqnHandle {
     static constexpr const char *kCreate = "rs_dqn_create";
     DqnTrainTab T{};
+    int n_step = 1, double_q = 0;       // rs_dqn_set_target: host-side, read when a gradient is enqueued
 };
 
 extern "C" void rs_dqn_destroy(rs_dqn_handle p) { train_destroy(p); }
@@ -1205,7 +1206,7 @@ static bool dqn_on_device(const void *ptr, int device) {
 }
 static const char *dqn_ring_refusal(const rs_dqn *, const rs_dqn_ring *) { return nullptr; }      // (a ring of rs_dqn_ring has no sizes of its own to check)
 static DqnBatch dqn_batch(const rs_dqn_ring *r, const int32_t *idx, int32_t B) {
-    return DqnBatch{(const __half *)r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, idx, B};
+    return DqnBatch{(const __half *)r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, idx, B, r->head};
 }
 
 // the launches; the arguments have been checked
@@ -1216,7 +1217,12 @@ static void dqn_sample_launch(const rs_dqn *p, const rs_dqn_ring *r, int B, uint
 static void dqn_grad_launch(const rs_dqn *p, const DqnBatch &D, float *loss_out, hipStream_t st) {
     const DqnTrainTab &T = p->T;
     const int tiles = (D.B + PPT_TM - 1) / PPT_TM, chunks = (tiles * PPT_TM + PPT_CH - 1) / PPT_CH;
-    hipLaunchKernelGGL(dqn_target_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
+    if (p->n_step == 1 && !p->double_q)         // the options off: the plain one-step target, its own kernel
+        hipLaunchKernelGGL(dqn_target_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
+    else if (p->double_q)
+        hipLaunchKernelGGL(dqn_target_opt_kernel<true>, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D, p->n_step);
+    else
+        hipLaunchKernelGGL(dqn_target_opt_kernel<false>, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D, p->n_step);
     hipLaunchKernelGGL(dqn_fwd_bwd_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
     hipLaunchKernelGGL(dqn_fc1_bwd_kernel, dim3(T.H * 2, chunks, T.S), dim3(PPT_T), 0, st, T, D);
     hipLaunchKernelGGL(dqn_reduce_kernel, dim3(T.S, T.H + (ppt_n_small(DQN_NH) + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, T, D.B, loss_out);
@@ -1766,6 +1772,19 @@ extern "C" int rs_dqn_update(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t b
 extern "C" int rs_dqn_sync_target(rs_dqn_handle p, void *stream) { return dqn_sync_target("rs_dqn_sync_target", p, stream); }
 extern "C" int64_t rs_dqn_steps(rs_dqn_handle p) { return p ? (int64_t)p->t : -1; }
 extern "C" int rs_dqn_set_steps(rs_dqn_handle p, int64_t t) { return train_set_steps("rs_dqn_set_steps", p, t); }
+// the target's options: the host-side fields alone (no launch, no synchronisation): what is enqueued afterwards sees them
+extern "C" int rs_dqn_set_target(rs_dqn_handle p, int32_t n_step, int32_t double_q) {
+    if (!p) { g_create_err = "rs_dqn_set_target: NULL handle"; return RS_EINVAL; }
+    if (n_step < 1 || n_step > 32) { g_create_err = "rs_dqn_set_target: need 1 <= n_step <= 32"; return RS_EINVAL; }
+    if (double_q != 0 && double_q != 1) { g_create_err = "rs_dqn_set_target: double_q is 0 or 1"; return RS_EINVAL; }
+    p->n_step = n_step; p->double_q = double_q;
+    return RS_OK;
+}
+extern "C" int rs_dqn_get_target(rs_dqn_handle p, int32_t *n_step, int32_t *double_q) {
+    if (!p || !n_step || !double_q) { g_create_err = "rs_dqn_get_target: NULL handle or pointer"; return RS_EINVAL; }
+    *n_step = p->n_step; *double_q = p->double_q;
+    return RS_OK;
+}
 
 extern "C" int rs_mplight_dqn_sample(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key,
                                      int32_t *idx_out, void *stream) {

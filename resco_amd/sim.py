@@ -36,7 +36,7 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_ippo_act', 'rs_group_rollout', 'rs_ppo_gae',
                'rs_ppo_create', 'rs_ppo_grad', 'rs_ppo_step', 'rs_ppo_fit', 'rs_ppo_steps', 'rs_ppo_set_steps', 'rs_ppo_destroy',
                'rs_dqn_create', 'rs_dqn_sample', 'rs_dqn_grad', 'rs_dqn_step', 'rs_dqn_update', 'rs_dqn_steps', 'rs_dqn_set_steps',
-               'rs_dqn_destroy',
+               'rs_dqn_set_target', 'rs_dqn_get_target', 'rs_dqn_destroy',
                'rs_mplight_dqn_create', 'rs_mplight_dqn_sample', 'rs_mplight_dqn_grad', 'rs_mplight_dqn_step', 'rs_mplight_dqn_update',
                'rs_mplight_dqn_steps', 'rs_mplight_dqn_set_steps', 'rs_mplight_dqn_destroy',
                'rs_mplight_multi_create', 'rs_mplight_multi_sample', 'rs_mplight_multi_grad', 'rs_mplight_multi_step', 'rs_mplight_multi_update',
@@ -128,6 +128,9 @@ def bind(L):
         L.rs_dqn_steps.restype = C.c_int64
         if hasattr(L, 'rs_dqn_set_steps'):      # (a host emulation may not have it)
             L.rs_dqn_set_steps.argtypes = [vp, C.c_int64]
+        if hasattr(L, 'rs_dqn_set_target'):     # (a host emulation may not have them)
+            L.rs_dqn_set_target.argtypes = [vp, i32, i32]
+            L.rs_dqn_get_target.argtypes = [vp, vp, vp]
         L.rs_dqn_destroy.argtypes = [vp]
         L.rs_dqn_destroy.restype = None
     if hasattr(L, 'rs_mplight_dqn_create'):

@@ -2,11 +2,14 @@
 """IDQN training loop entirely on the GPU: HIP simulator -> fp16 observations -> fused HIP policy kernel
 (rs_idqn_act) -> device replay ring -> batched DQN update (PyTorch, or HIP with --device-update) -> weights re-packed on the device.  Nothing crosses PCIe per step except the launch calls.
 
-    python tools/idqn_train.py [--device-update | --device-loop] [map] [n_envs] [episodes] [batch] [updates_per_step] [graph|nograph] [replay_steps] [eps_end] [seed]
+    python tools/idqn_train.py [--n-step K] [--double-q] [--device-update | --device-loop] [map] [n_envs] [episodes] [batch] [updates_per_step] [graph|nograph] [replay_steps] [eps_end] [seed]
 
 --device-update: the update itself in HIP kernels as well (FusedDQNLearner, rs_dqn_update: sampling, target, backward and Adam of all
 updates of a step in one call; no HIP graph is captured).  --device-loop (implies --device-update): the loop itself in the library
 as well (agents/train_fused.py: DeviceTrainer, rs_group_train), one call per episode; the same rows.  Without either: the batched PyTorch learner, graph-captured unless `nograph`.
+
+--n-step K (1 .. 32) and --double-q, in every mode: n-step returns (truncated at the newest slot of the ring, cut at an episode end) and
+Double DQN's bootstrap; both are part of a checkpoint's signature.  Without them: PFRL's plain one-step DQN.
 
 Prints one JSON line per episode (mean episode return of rewards.wait_norm per signal, average trip delay as
 utils/readXML.py computes it, epsilon, env-steps/s including learning) and a final line comparing with the
@@ -55,8 +58,8 @@ def greedy_evaluation(env, policy, actions, steps, seeds):
 
 
 def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_graph=True, replay_steps=0, eps_end=0.0, evaluate=True, quiet=False, seed=0, tls_expiry=True,
-         device_update=False, device_loop=False, chunk=0, save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0):
-    """device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
+         device_update=False, device_loop=False, chunk=0, save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, n_step=1, double_q=False):
+    """n_step / double_q: the learners' options of the same names.  device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
     save / save_freq / save_replay / load / eval_only / stop_after: the checkpoint flags of the module docstring; a run that leaves
     at stop_after returns (rows, None)."""
     device_update = device_update or device_loop
@@ -66,10 +69,10 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
     net = BatchedIDQN.from_scenario(env.scenario, dtype=torch.float32, device='cuda')
     net.init_like_reference(seed=seed)
     if device_update:
-        learner = FusedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed)
+        learner = FusedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed, n_step=n_step, double_q=double_q)
         use_graph = False                               # one call enqueues the update's few launches: nothing to capture
     else:
-        learner = BatchedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch)
+        learner = BatchedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, n_step=n_step, double_q=double_q)
     policy = FusedIDQN(net, seed=7 + seed)             # acting: one HIP kernel; weights re-packed on the device after each update
     actions = env.tensor('actions')
     # the reference keeps the last 10 000 transitions of its ONE environment = 27.8 episodes of history (pfrl_dqn.py:55); a ring of
@@ -156,8 +159,30 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
     return rows, final
 
 
+def target_flags(argv):
+    """--n-step K and --double-q taken out of an argument list -> (keyword arguments for main(), the remaining arguments)"""
+    kw, rest, i = {}, [], 0
+    while i < len(argv):
+        if argv[i] == '--n-step':
+            if i + 1 >= len(argv):
+                raise SystemExit('--n-step needs a value')
+            kw['n_step'] = int(argv[i + 1])
+            if not 1 <= kw['n_step'] <= 32:
+                raise SystemExit('--n-step: 1 .. 32')
+            i += 2
+            continue
+        if argv[i] == '--double-q':
+            kw['double_q'] = True
+        else:
+            rest.append(argv[i])
+        i += 1
+    return kw, rest
+
+
 if __name__ == '__main__':
     ckpt, a = checkpoint.tool_flags(sys.argv[1:])
+    opts, a = target_flags(a)
+    ckpt.update(opts)
     loop = a[:1] == ['--device-loop']
     dev = loop or a[:1] == ['--device-update']
     a = a[1:] if dev else a
