@@ -550,6 +550,15 @@ void rs_dqn_destroy(rs_dqn_handle p);
  * rs_mplight_dqn_update: for j < n_updates: rs_mplight_dqn_sample with update_key = the step count so far into the handle's own
  * index array, rs_mplight_dqn_grad, rs_mplight_dqn_step -- the same launches, all enqueued by one call without host synchronisation
  * or copies.
+ * rs_mplight_dqn_set_target / rs_mplight_dqn_get_target: the target's options, as rs_dqn_set_target / rs_dqn_get_target (n_step in
+ * 1 .. 32, double_q 0 / 1; a new handle has (1, 0) and at (1, 0) exactly the launches above run; host-side fields alone, what is
+ * enqueued afterwards sees them -- rs_mplight_dqn_grad, rs_mplight_dqn_update and the MPLight branch of rs_group_train; RS_EINVAL with
+ * a text and the handle unchanged for a NULL handle, n_step outside 1 .. 32 or double_q outside 0 / 1).  The draw does not depend on
+ * them.  The walk of row (t, e, s) is rs_dqn_set_target's, on rew[.][e][s] and the ring's done and head; the arithmetic is in
+ * double like the rest of the gradient, in the same order: R = rew_0, g = gamma; for j = 1 .. m - 1: R = R + g rew_j, g = g gamma;
+ * tgt = R where cut, else R + g boot.  boot: double_q 0: the max over ALL n_pairs outputs of Q_target(obs[u_m][e][s]); double_q 1:
+ * Q_target(obs[u_m][e][s])[a*], a* = the argmax over ALL n_pairs outputs of Q_online(obs[u_m][e][s]) (not masked by a signal's valid
+ * pairs either), the lowest index among equal maxima, the online network being params as they stand when the gradient is taken.
  * All calls are asynchronous on `stream`; every sum has one fixed order (no float atomics): the same state gives the same bits.
  * Workspace, allocated once by rs_mplight_dqn_create: 10 KB per 4 rows of max_batch.  The five vectors, the Adam step and every
  * result are fp32; the gradient is evaluated in double and rounded once per element (resco_frap_train.h says why), so the Q-values
@@ -579,6 +588,8 @@ int rs_mplight_dqn_update(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, 
                           void *stream);
 int64_t rs_mplight_dqn_steps(rs_mplight_dqn_handle p);
 int rs_mplight_dqn_set_steps(rs_mplight_dqn_handle p, int64_t t);
+int rs_mplight_dqn_set_target(rs_mplight_dqn_handle p, int32_t n_step, int32_t double_q);
+int rs_mplight_dqn_get_target(rs_mplight_dqn_handle p, int32_t *n_step, int32_t *double_q);
 void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p);
 
 /* ---- MPLight on several maps: ONE shared FRAP trained on M replay rings at once (resco_amd/csrc/resco_frap_multi.h) ------------
@@ -601,6 +612,10 @@ void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p);
  * the mean over all `batch` rows of the Huber terms; loss_out: ONE device float or NULL.  A tile holds rows of one map, tiles run in
  * group order: with n_maps = 1 every bit is rs_mplight_dqn_grad's.
  * rs_mplight_multi_step / _steps / _set_steps / _sync_target: as rs_mplight_dqn_*.
+ * rs_mplight_maps_set_target / rs_mplight_maps_get_target (on an rs_mplight_multi handle; rs_mplight_multi_* stays the nine calls of the
+ * update itself): as rs_mplight_dqn_set_target / _get_target; every row walks its own
+ * map's ring (that ring's done and head) and a* runs over the n_pairs_m outputs of the row's own map.  With n_maps = 1 every bit is
+ * rs_mplight_dqn_grad's with the same options.
  * rs_mplight_multi_update: for j < n_updates: the draw with update_key = the step count so far into the handle's own index array,
  * the gradient, the Adam step: four launches per update whatever n_maps is, all enqueued by one call.
  * All calls are asynchronous on `stream` and create no stream, event or wait and use no asynchronous memcpy; every sum has one fixed
@@ -629,6 +644,8 @@ int rs_mplight_multi_update(rs_mplight_multi_handle p, const rs_mplight_ring *ri
 int rs_mplight_multi_sync_target(rs_mplight_multi_handle p, void *stream);
 int64_t rs_mplight_multi_steps(rs_mplight_multi_handle p);
 int rs_mplight_multi_set_steps(rs_mplight_multi_handle p, int64_t t);
+int rs_mplight_maps_set_target(rs_mplight_multi_handle p, int32_t n_step, int32_t double_q);
+int rs_mplight_maps_get_target(rs_mplight_multi_handle p, int32_t *n_step, int32_t *double_q);
 void rs_mplight_multi_destroy(rs_mplight_multi_handle p);
 
 /* ---- the DQN training loop of IDQN and MPLight in one call (resco_amd/csrc/resco_group_train.h) -------------------------------

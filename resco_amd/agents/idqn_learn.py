@@ -101,15 +101,16 @@ class DeviceReplay:
         return _rows(self, t, e, self.head, n_step, gamma)
 
 
-def nstep_walk(rp, t, e, head, n_step, gamma):
-    """The n-step walk of rows (t, e) [B, S] of the ring rp, vectorised: n_step masked steps, no data-dependent control flow, `head`
+def nstep_walk(rp, t, e, head, n_step, gamma, s=None):
+    """The n-step walk of rows (t, e) [B, S] of the ring rp (s None: column j is signal j, a DeviceReplay's rows), or of rows (t, e, s)
+    of any one shape (an MPLightReplay's [B]), vectorised: n_step masked steps, no data-dependent control flow, `head`
     a Python int or a device scalar (so it can be captured in a HIP graph).  newest = (head - 1) mod T is the one written slot
     without a successor.  u_0 = t; step j takes rew[u_j] and the walk stops after it where done[u_j] (cut), where j + 1 == n_step, or
     where (u_j + 1) mod T == newest; m = j + 1.  In the ring's float32 and in this order: R = rew_0, g = gamma; for j = 1 .. m - 1:
     R = R + g rew_j, g = g gamma.  -> (R [B, S], u_m = (t + m) mod T [B, S], cut [B, S] bool, g = gamma^m [B, S]).
     Truncated at the newest slot (PFRL's n-step buffer would wait for n successors); rs_dqn_set_target of include/resco_sim.h is the
     same definition for the fused update."""
-    T, sig = rp.T, rp._sig
+    T, sig = rp.T, (rp._sig if s is None else s)
     newest = (head - 1) % T
     u = t
     R = rp.rew[t, e, sig]

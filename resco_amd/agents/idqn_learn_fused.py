@@ -31,9 +31,7 @@ class FusedDQNLearner(FusedLearnerBase):
         defaults are PFRL's plain one-step DQN."""
         assert isinstance(net, BatchedIDQN)
         super().__init__(net)
-        self.n_step, self.double_q = int(n_step), bool(double_q)
-        if not 1 <= self.n_step <= 32:
-            raise ValueError('FusedDQNLearner: n_step must be in 1 .. 32, got %d' % self.n_step)
+        self._take_target_options(n_step, double_q)
         self.gamma, self.lr, self.adam_eps = float(gamma), float(lr), 1e-8
         self.batch_size, self.target_update, self.seed = int(batch_size), int(target_update), int(seed) & 0xFFFFFFFF
         self.t = 0              # agent steps seen (PFRL's self.t)
@@ -41,12 +39,7 @@ class FusedDQNLearner(FusedLearnerBase):
         for p in self.target.parameters():
             p.requires_grad_(False)
         self._create(DQNConfig(self.lr, self.adam_eps, 0.9, 0.999, self.gamma), self.batch_size, more_nets=(self.target,))     # (a CPU net raises)
-        if (self.n_step, self.double_q) != (1, False):
-            if not hasattr(self._lib, 'rs_dqn_set_target'):
-                raise RuntimeError('the loaded library has no rs_dqn_set_target: rebuild it (there is no CPU fallback)')
-            rc = self._lib.rs_dqn_set_target(self._h, self.n_step, int(self.double_q))
-            if rc != 0:
-                self._fail('rs_dqn_set_target', rc)
+        self._set_target_options()
 
     def _ring(self, replay):
         """rs_dqn_ring over a DeviceReplay's own arrays (no copies) at its present position"""

@@ -16,6 +16,7 @@ class FusedLearnerBase:
     TENSORS = None          # names of the parameters, in the order of the fields of
     TENSOR_SET = None       # the ctypes struct of one set of device pointers
     LOSS_SHAPE = ()         # .loss_out is float32 [S, *LOSS_SHAPE]
+    SET_TARGET = None       # the DQN learners' setter of the target's options; None: PREFIX_set_target
 
     def __init__(self, net):
         self.net = net
@@ -51,6 +52,23 @@ class FusedLearnerBase:
 
     def _fn(self, name):
         return getattr(self._lib, '%s_%s' % (self.PREFIX, name))
+
+    # ---- the target's options of the DQN learners (SET_TARGET: n-step returns, Double DQN)
+    def _take_target_options(self, n_step, double_q):
+        self.n_step, self.double_q = int(n_step), bool(double_q)
+        if not 1 <= self.n_step <= 32:
+            raise ValueError('%s: n_step must be in 1 .. 32, got %d' % (self.NAME, self.n_step))
+
+    def _set_target_options(self):
+        """on a fresh handle: nothing is called while the options are the defaults"""
+        if (self.n_step, self.double_q) == (1, False):
+            return
+        name = self.SET_TARGET or self.PREFIX + '_set_target'
+        if not hasattr(self._lib, name):
+            raise RuntimeError('the loaded library has no %s: rebuild it (there is no CPU fallback)' % name)
+        rc = getattr(self._lib, name)(self._h, self.n_step, int(self.double_q))
+        if rc != 0:
+            self._fail(name, rc)
 
     def _need_handle(self):
         """what a learner that creates its handle on first use overrides"""

@@ -39,7 +39,7 @@ import torch.nn.functional as F
 
 from ..sim import load_library, maxwave_tables, torch_stream
 from . import _state
-from .idqn_learn import linear_epsilon
+from .idqn_learn import linear_epsilon, nstep_walk, target_options_signature
 
 N_MOVEMENTS = 12
 Q_WIDTH = 16            # the q output of rs_mplight_act: [N][S][16], -inf beyond P
@@ -293,8 +293,10 @@ class MPLightReplay:
         if not weights_only:
             _state.load_ring_state(self, sd, 'MPLightReplay')
 
-    def sample(self, batch_size, generator=None):
-        """B transitions uniform over (slot with a successor, environment, signal): o [B, W], g [B] long, r [B], o2 [B, W], d [B]."""
+    def sample(self, batch_size, generator=None, n_step=1, gamma=None):
+        """B transitions uniform over (slot with a successor, environment, signal): o [B, W], g [B] long, r [B], o2 [B, W], d [B].
+        n_step > 1 (needs gamma): the same rows from the same draws, with r the discounted sum of the walk's rewards, o2 the
+        observation the walk ends at, d the cut flag, and a sixth element disc = gamma^m (idqn_learn.nstep_walk)."""
         n_ok = self.count - 1
         assert n_ok >= 1, 'need two pushes before sampling'
         dev, B = self.obs.device, int(batch_size)
@@ -302,14 +304,22 @@ class MPLightReplay:
         t = (self.head - self.count + k) % self.T
         e = torch.randint(0, self.N, (B,), device=dev, generator=generator)
         s = torch.randint(0, self.S, (B,), device=dev, generator=generator)
-        t2 = (t + 1) % self.T
-        return self.obs[t, e, s], self.act[t, e, s].long(), self.rew[t, e, s], self.obs[t2, e, s], self.done[t].to(torch.float32)
+        if int(n_step) == 1:
+            t2 = (t + 1) % self.T
+            return self.obs[t, e, s], self.act[t, e, s].long(), self.rew[t, e, s], self.obs[t2, e, s], self.done[t].to(torch.float32)
+        assert 1 < int(n_step) <= 32 and gamma is not None, 'n-step rows need 1 <= n_step <= 32 and gamma'
+        R, u_m, cut, disc = nstep_walk(self, t, e, self.head, n_step, gamma, s)
+        return self.obs[t, e, s], self.act[t, e, s].long(), R, self.obs[u_m, e, s], cut.to(torch.float32), disc
 
 
 class MPLightLearner:
     """PFRL's DQN update on the shared FRAP network (see the module docstring for the batching)."""
 
-    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32):
+    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, n_step=1, double_q=False):
+        """n_step (1 .. 32): n-step returns (idqn_learn.nstep_walk); double_q: Double DQN's bootstrap.  The defaults are PFRL's plain DQN."""
+        self.n_step, self.double_q = int(n_step), bool(double_q)
+        if not 1 <= self.n_step <= 32:
+            raise ValueError('MPLightLearner: n_step must be in 1 .. 32, got %d' % self.n_step)
         self.q = net
         self.target = copy.deepcopy(net)
         for p in self.target.parameters():
@@ -319,11 +329,16 @@ class MPLightLearner:
         self.t = 0              # env-steps seen
         self.n_updates = 0
 
-    def loss(self, o, g, r, o2, d):
+    def loss(self, o, g, r, o2, d, disc=None):
+        """disc: the discount of the bootstrap per row (gamma^m of an n-step row); None: gamma"""
         y = self.q(o).gather(-1, g.unsqueeze(-1)).squeeze(-1)
         with torch.no_grad():
-            nxt = self.target(o2).max(dim=-1).values                            # over ALL P outputs: not masked by valid_acts
-            tgt = r + self.gamma * (1.0 - d) * nxt
+            if self.double_q:                                                   # the online network's best of ALL P outputs (the first of
+                best = self.q(o2).argmax(dim=-1, keepdim=True)                  # equal maxima), valued by the target network
+                nxt = self.target(o2).gather(-1, best).squeeze(-1)
+            else:
+                nxt = self.target(o2).max(dim=-1).values                        # over ALL P outputs: not masked by valid_acts
+            tgt = r + (self.gamma if disc is None else disc) * (1.0 - d) * nxt
         return F.smooth_l1_loss(y, tgt, reduction='mean')                      # Huber, delta 1, mean over the minibatch
 
     def update(self, batch):
@@ -339,7 +354,7 @@ class MPLightLearner:
 
     # ---- checkpoints (resco_amd/checkpoint.py): loaded in place
     def signature(self):
-        return {'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}
+        return target_options_signature({'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}, self.n_step, self.double_q)
 
     def state_dict(self):
         return {'weights': {'target': _state.module_tensors(self.target)},
@@ -358,7 +373,7 @@ class MPLightLearner:
         if self.t % self.target_update == 0:
             self.sync_target()
         if len(replay) >= self.batch_size:
-            return self.update(replay.sample(self.batch_size, generator))
+            return self.update(replay.sample(self.batch_size, generator, self.n_step, self.gamma))
         return None
 
 

@@ -20,6 +20,7 @@ import torch
 
 from ..sim import DQNConfig, MPLightRing, load_library, torch_stream
 from . import _state
+from .idqn_learn import target_options_signature
 from .learn_fused import FusedLearnerBase
 from .mplight import FRAP
 
@@ -37,9 +38,13 @@ def _views(flat, net):
 class FusedMPLightLearner(FusedLearnerBase):
     NAME, PREFIX = 'FusedMPLightLearner', 'rs_mplight_dqn'
 
-    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, seed=0, n_signals=None):
+    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, seed=0, n_signals=None, n_step=1, double_q=False):
+        """n_step (1 .. 32): n-step returns, truncated at the newest slot of the ring and cut at an episode end; double_q: the
+        bootstrap is the target network's value of the online network's best of ALL P outputs (rs_mplight_dqn_set_target has the
+        definition).  The defaults are PFRL's plain one-step DQN."""
         assert isinstance(net, FRAP)
         super().__init__(net)
+        self._take_target_options(n_step, double_q)
         self.gamma, self.lr, self.adam_eps = float(gamma), float(lr), 1e-8
         self.batch_size, self.target_update, self.seed = int(batch_size), int(target_update), int(seed) & 0xFFFFFFFF
         self.t = 0              # env-steps seen
@@ -84,6 +89,7 @@ class FusedMPLightLearner(FusedLearnerBase):
         if rc != 0:
             self._fail('rs_mplight_dqn_create', rc)
         self._h, self.n_signals = h, n_signals
+        self._set_target_options()
 
     def _need_handle(self):
         if self._h is None:
@@ -150,7 +156,7 @@ class FusedMPLightLearner(FusedLearnerBase):
     # parameters of net and target are views of them and a policy may share .flat --; the step count goes back through
     # rs_mplight_dqn_set_steps, so the handle has to exist (pass n_signals, or show the learner its ring first)
     def signature(self):
-        return {'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}
+        return target_options_signature({'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}, self.n_step, self.double_q)
 
     def state_dict(self):
         return {'weights': {'flat': self.flat, 'flat_target': self.flat_target},

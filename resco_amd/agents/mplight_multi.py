@@ -18,6 +18,7 @@ import torch
 
 from ..sim import DQNConfig, MPLightMap, MPLightRing, load_library, torch_stream
 from . import _state
+from .idqn_learn import target_options_signature
 from .learn_fused import FusedLearnerBase
 from .mplight import FRAP
 from .mplight_learn_fused import _views
@@ -26,15 +27,17 @@ MAX_MAPS = 8        # FPM_MAPS of resco_frap_multi.h
 
 
 class MultiMapMPLightLearner(FusedLearnerBase):
-    NAME, PREFIX = 'MultiMapMPLightLearner', 'rs_mplight_multi'
+    NAME, PREFIX, SET_TARGET = 'MultiMapMPLightLearner', 'rs_mplight_multi', 'rs_mplight_maps_set_target'
 
-    def __init__(self, nets, n_signals, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, seed=0):
-        """nets: one FRAP per map; n_signals: the maps' signal counts (their rings' S)."""
+    def __init__(self, nets, n_signals, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, seed=0, n_step=1, double_q=False):
+        """nets: one FRAP per map; n_signals: the maps' signal counts (their rings' S); n_step (1 .. 32) and double_q: the target's
+        options, as FusedMPLightLearner's (rs_mplight_maps_set_target): every row walks its own map's ring."""
         nets, n_signals = list(nets), [int(s) for s in n_signals]
         if not 1 <= len(nets) <= MAX_MAPS or len(n_signals) != len(nets):
             raise ValueError('MultiMapMPLightLearner takes 1 .. %d networks and as many signal counts' % MAX_MAPS)
         assert all(isinstance(n, FRAP) for n in nets)
         super().__init__(nets[0])
+        self._take_target_options(n_step, double_q)
         self.nets, self.n_signals = nets, n_signals
         D = nets[0].demand_shape
         if any(n.demand_shape != D for n in nets):
@@ -84,6 +87,7 @@ class MultiMapMPLightLearner(FusedLearnerBase):
         if rc != 0:
             self._fail('rs_mplight_multi_create', rc)
         self._h = h
+        self._set_target_options()
 
     def _rings(self, replays):
         """rs_mplight_ring [n_maps] over the MPLightReplays' own arrays (no copies) at their present positions"""
@@ -150,8 +154,9 @@ class MultiMapMPLightLearner(FusedLearnerBase):
 
     # ---- checkpoints (resco_amd/checkpoint.py): the vectors are loaded in place, the step count through rs_mplight_multi_set_steps
     def signature(self):
-        return {'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma, 'demand_shape': int(self.nets[0].demand_shape),
-                'n_pairs': [int(n.oshape) for n in self.nets], 'n_signals': list(self.n_signals)}
+        fields = {'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma, 'demand_shape': int(self.nets[0].demand_shape),
+                  'n_pairs': [int(n.oshape) for n in self.nets], 'n_signals': list(self.n_signals)}
+        return target_options_signature(fields, self.n_step, self.double_q)
 
     def state_dict(self):
         return {'weights': {'flat': self.flat, 'flat_target': self.flat_target},

@@ -104,6 +104,7 @@ struct FrapMultiRing {
     const int32_t *pairs;               // device [P][2]
     int32_t T, N, S, W, P;
     int32_t tile0, row0, rows;          // the group's first tile, its first row of idx, its row count
+    int32_t head;                       // the ring's next slot to write (the n-step walk of the option kernels stops before head - 1)
 };
 struct FrapMultiBatch {
     FrapMultiRing map[FPM_MAPS];
@@ -152,6 +153,22 @@ RS_HD inline void frap_multi_load(FrapStage &L, const FrapMultiRing &R, const in
         L.g[r] = a < 0 ? 0 : (a >= R.P ? R.P - 1 : a);
         L.rew[r] = ok ? R.rew[cur] : 0.0f;
     }
+}
+
+// the same row under the target's options (rs_mplight_maps_set_target): its own observation, its scalars and its walk
+// (fpt_opt_load_row of resco_frap_train.h); the bootstrap row is loaded a barrier later (fpt_opt_load_next)
+template <int TAG>
+RS_HD inline void frap_multi_opt_load(FrapStage &L, FrapOptRows &O, const FrapMultiRing &R, const int32_t *idx, int b, int r, int j, int n_step, fpt_t gamma) {
+    const int local = (b - R.tile0) * FPT_TM + r;
+    const bool ok = local < R.rows;
+    int t = 0, e = 0, s = 0;
+    if (ok) {
+        const int32_t *p = idx + (size_t)(R.row0 + local) * 4;
+        t = p[1] < 0 ? 0 : (p[1] >= R.T ? R.T - 1 : p[1]);
+        e = p[2] < 0 ? 0 : (p[2] >= R.N ? R.N - 1 : p[2]);
+        s = p[3] < 0 ? 0 : (p[3] >= R.S ? R.S - 1 : p[3]);
+    }
+    fpt_opt_load_row<TAG>(L, O, R.obs, R.act, R.rew, R.done, R.T, R.N, R.S, R.W, R.P, R.head, ok, t, e, s, n_step, gamma, r, j);
 }
 
 #if defined(__HIPCC__)      // ------------------------------------------------------------------------------------------ the kernels
@@ -222,6 +239,20 @@ __global__ void __launch_bounds__(FPT_T) frap_multi_tile_kernel(FrapTrainTab T, 
     __syncthreads();
     fpt_t *part = T.part + (size_t)b * FG_N;
     for (int e = tid; e < FG_N; e += FPT_T) part[e] = frap_tile_entry<FPM_TAG>(L, P, Dm, e);
+}
+
+// frap_dqn_tile_opt_kernel over the groups (launched only when an option is on; instantiations FPM_OPT_TAG + DOUBLE_Q)
+#define FPM_OPT_TAG 4
+template <bool DOUBLE_Q> __global__ void __launch_bounds__(FPT_T) frap_multi_tile_opt_kernel(FrapTrainTab T, FrapMultiBatch D, int n_step) {
+    constexpr int TAG = FPM_OPT_TAG + (DOUBLE_Q ? 1 : 0);
+    __shared__ FrapStage L;
+    __shared__ FrapOptRows O;
+    const int tid = threadIdx.x, r = tid / FPT_G, j = tid % FPT_G, b = blockIdx.x;
+    const FrapMultiRing R = D.map[frap_multi_tile_map(D, b)];
+    for (int k = tid; k < 144; k += FPT_T) fpt_prep<TAG>(L, T.par, T.tgt, T.D, k);
+    frap_multi_opt_load<TAG>(L, O, R, D.idx, b, r, j, n_step, T.gamma);
+    __syncthreads();
+    frap_opt_tile_body<TAG, DOUBLE_Q>(L, O, T, R.obs, R.W, R.P, R.pairs, D.B, T.part + (size_t)b * FG_N, tid, r, j);
 }
 
 // frap_dqn_reduce_kernel with the tile count given

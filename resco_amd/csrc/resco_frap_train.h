@@ -30,6 +30,17 @@
 //
 // Every sum has ONE order, fixed by the shapes alone; no floating-point atomics: the same state gives the same bits.
 //
+// The options of rs_mplight_dqn_set_target (n-step returns, Double DQN; PFRL's MPLight uses neither; the header of resco_dqn_train.h has
+// the semantics, restated here per row (t, e, s)).  With either one on, launch 1 is frap_dqn_tile_opt_kernel<DOUBLE_Q> instead; the
+// draw, the reduction and the Adam step are the same, and with both off nothing of this is launched: frap_dqn_tile_kernel stays as it is.
+//   n_step: lane (r, 0) walks its row forward through the ring (dqn_nstep_walk), keeps R = sum_j gamma^j rew[(t + j) mod T][e][s] and
+//   g = gamma^m in double, and names slot (t + m) mod T as the row all lanes load a barrier later; tgt = R + g boot, or R alone where
+//   an episode end cut the walk (nothing is read behind it).  The walk truncates at the newest slot, as the IDQN learners' does.
+//   double_q: boot = Q_target[a*], a* = argmax over ALL P outputs of Q_online(successor row), the lowest index among equal maxima, not
+//   masked by valid_acts (as the target's max is not).  The online pass runs in the same workgroup before the target's pass, through
+//   the same phases (fpt_target_ab / fpt_target_q with NET 0) and the same stage areas x, h and y; a* and the rows' other new scalars
+//   live in a small block beside the stage (FrapOptRows).  The cost: profiles/r24_mplight_nstep_double.txt.
+//
 // Precision.  y - tgt is a difference of two Q-values several times its size, a row's dy multiplies every gradient the row
 // contributes, and the rows' contributions cancel: an fp32 evaluation of this gradient is about 1e-5 of its largest element away from
 // float64 (torch's own float32 is), and two fp32 evaluations in different operation orders are that far from EACH OTHER -- so how far
@@ -265,8 +276,9 @@ RS_HD inline void fpt_prep(FrapStage &L, const float *w, const float *wt, int D,
     else L.R[net][kk - 32] = v;
 }
 
-// ---- the target: lane (r, j < P) A_j, B_j of the successor row under the target network
-template <int TAG = 0, class WP>
+// ---- the target: lane (r, j < P) A_j, B_j of the successor row under network NET of the stage's tables (1: the target network, wt
+// its weights; 0: the parameters, for Double DQN's a*)
+template <int TAG = 0, int NET = 1, class WP>
 RS_HD inline void fpt_target_ab(FrapStage &L, WP wt, int D, int P, const int32_t *pairs, int r, int j) {
     if (!L.boot[r] || j >= P) return;
     const float *ob = L.nxt[r];
@@ -277,7 +289,7 @@ RS_HD inline void fpt_target_ab(FrapStage &L, WP wt, int D, int P, const int32_t
     for (int side = 0; side < 2; ++side) {
         const int m = pairs[2 * j + side];
         fpt_t sd[4], e[FRAP_E];
-        frap_mv_forward(wt, D, L.PE[1], m, m == p0 || m == p1, [&](int mv, int v) { return ob[1 + mv + v]; }, sd, e);
+        frap_mv_forward(wt, D, L.PE[NET], m, m == p0 || m == p1, [&](int mv, int v) { return ob[1 + mv + v]; }, sd, e);
 #pragma unroll
         for (int u = 0; u < FRAP_E; ++u) pr[u] += e[u];
     }
@@ -286,14 +298,14 @@ RS_HD inline void fpt_target_ab(FrapStage &L, WP wt, int D, int P, const int32_t
     for (int c = 0; c < FRAP_C; ++c) { L.x[r][j][c] = A[c]; L.h[r][j][c] = B[c]; }
 }
 // lane (r, i < P): Q_i = sum_{j != i} y_ij, j ascending
-template <int TAG = 0, class WP>
+template <int TAG = 0, int NET = 1, class WP>
 RS_HD inline void fpt_target_q(FrapStage &L, WP wt, int D, int P, const int32_t *pairs, int r, int i) {
     if (!L.boot[r] || i >= P) return;
     fpt_t q = 0.0;
     for (int j = 0; j < P; ++j) {
         if (j == i) continue;
         fpt_t lc[FRAP_C], x[FRAP_C], h[FRAP_C];
-        q += frap_item_forward(wt, D, L.x[r][i], L.h[r][j], L.R[1] + FRAP_C * frap_comp(pairs, i, j), lc, x, h);
+        q += frap_item_forward(wt, D, L.x[r][i], L.h[r][j], L.R[NET] + FRAP_C * frap_comp(pairs, i, j), lc, x, h);
     }
     L.y[r][i] = q;
 }
@@ -305,6 +317,75 @@ RS_HD inline void fpt_target_value(FrapStage &L, int P, double gamma, int r) {
         fpt_t mx = L.y[r][0];
         for (int i = 1; i < P; ++i) mx = L.y[r][i] > mx ? L.y[r][i] : mx;
         t = t + gamma * mx;
+    }
+    L.tgt[r] = t;
+}
+
+// ---- the target's options (rs_mplight_dqn_set_target: n-step returns, Double DQN; the header of resco_dqn_train.h has the semantics).
+// The rows' new scalars live beside the stage, not in it (the option kernels alone pay for them).
+struct FrapOptRows {
+    fpt_t ret[FPT_TM], disc[FPT_TM];                    // R = sum_j gamma^j rew_j and g = gamma^m of the row's walk
+    long long nxt[FPT_TM];                              // the bootstrap row ((t + m) mod T, e, s) of the ring, -1 where it is not read
+    int32_t astar[FPT_TM];                              // double_q: the online network's best action on that row
+};
+// Row r of a tile from the ring obs [T][N][S][W], act, rew [T][N][S], done [T] whose next slot to write is head; (t, e, s) already held
+// inside the ring.  Lane (r, j) reads its share of the row's own observation; lane (r, 0) the action and walks the row
+// (dqn_nstep_walk): R = rew_0, g = gamma; for j = 1 .. m - 1: R = R + g rew_j, g = g gamma -- nothing behind an episode end and no
+// reward of the newest slot is read.  The successor is loaded by fpt_opt_load_next, a barrier later.
+template <int TAG = 0>
+RS_HD inline void fpt_opt_load_row(FrapStage &L, FrapOptRows &O, const float *obs, const int16_t *act, const float *rew, const uint8_t *done, int T, int N,
+                                   int S, int W, int P, int head, bool ok, int t, int e, int s, int n_step, fpt_t gamma, int r, int j) {
+    const size_t cur = ((size_t)t * N + e) * S + s;
+    for (int q = j; q < FPT_W; q += FPT_G) L.obs[r][q] = ok && q < W ? obs[cur * W + q] : 0.0f;
+    if (j != 0) return;
+    fpt_t R = 0.0, g = gamma;
+    long long nxt = -1;
+    if (ok) {
+        int m, cut, u = t;
+        dqn_nstep_walk(done, T, head < 0 ? 0 : (head >= T ? T - 1 : head), t, n_step, &m, &cut);
+        R = rew[cur];
+        for (int k = 1; k < m; ++k) {
+            u = u + 1 == T ? 0 : u + 1;
+            R = R + g * (fpt_t)rew[((size_t)u * N + e) * S + s];
+            g = g * gamma;
+        }
+        if (!cut) nxt = (long long)(((size_t)(u + 1 == T ? 0 : u + 1) * N + e) * S + s);
+    }
+    const int a = ok ? (int)act[cur] : 0;
+    L.ok[r] = ok; L.boot[r] = nxt >= 0;
+    L.g[r] = a < 0 ? 0 : (a >= P ? P - 1 : a);
+    O.ret[r] = R; O.disc[r] = g; O.nxt[r] = nxt; O.astar[r] = 0;
+}
+// lane (r, j): its share of the bootstrap row, zeros where the walk was cut
+template <int TAG = 0>
+RS_HD inline void fpt_opt_load_next(FrapStage &L, const FrapOptRows &O, const float *obs, int W, int r, int j) {
+    const long long nxt = O.nxt[r];
+    for (int q = j; q < FPT_W; q += FPT_G) L.nxt[r][q] = nxt >= 0 && q < W ? obs[(size_t)nxt * W + q] : 0.0f;
+}
+// lane (r, 0), after the ONLINE network's pass over the successor rows (fpt_target_ab / fpt_target_q with NET 0): a* = its best of ALL
+// P outputs, the lowest index among equal maxima
+template <int TAG = 0>
+RS_HD inline void fpt_opt_astar(const FrapStage &L, FrapOptRows &O, int P, int r) {
+    int best = 0;
+    if (L.boot[r]) {
+        fpt_t mx = L.y[r][0];
+        for (int i = 1; i < P; ++i)
+            if (L.y[r][i] > mx) { mx = L.y[r][i]; best = i; }
+    }
+    O.astar[r] = best;
+}
+// lane (r, 0): tgt = R + g boot, boot = Q_target[a*] or max_i Q_target[i]; R alone where the walk was cut
+template <int TAG, bool DOUBLE_Q>
+RS_HD inline void fpt_opt_target_value(FrapStage &L, const FrapOptRows &O, int P, int r) {
+    fpt_t t = O.ret[r];
+    if (L.boot[r]) {
+        fpt_t boot;
+        if (DOUBLE_Q) boot = L.y[r][O.astar[r]];
+        else {
+            boot = L.y[r][0];
+            for (int i = 1; i < P; ++i) boot = L.y[r][i] > boot ? L.y[r][i] : boot;
+        }
+        t = t + O.disc[r] * boot;
     }
     L.tgt[r] = t;
 }
@@ -571,6 +652,7 @@ struct FrapBatch {
     int32_t T, N, S, W;
     const int32_t *idx;                     // [B][3]: (t, e, s)
     int32_t B;
+    int32_t head;                           // the ring's next slot to write (the n-step walk stops before the newest slot, head - 1)
 };
 
 __global__ void __launch_bounds__(256) frap_dqn_sample_kernel(uint32_t seed, uint32_t u, int T, int N, int S, int head, int count, int B, int32_t *idx) {
@@ -627,6 +709,67 @@ __global__ void __launch_bounds__(FPT_T) frap_dqn_tile_kernel(FrapTrainTab T, Fr
     __syncthreads();
     fpt_t *part = T.part + (size_t)blockIdx.x * FG_N;
     for (int e = tid; e < FG_N; e += FPT_T) part[e] = frap_tile_entry(L, P, Dm, e);
+}
+
+// frap_dqn_tile_kernel with n-step returns and / or Double DQN (launched only when an option is on; its own instantiations of the
+// phases, FPT_OPT_TAG + DOUBLE_Q).  One more barrier than the plain kernel: lane (r, 0) walks the row to its bootstrap slot, then all
+// lanes load that row.  double_q: the online network's pass over the successor rows comes first, through the stage areas the target's
+// pass then overwrites (x, h, y); a* stays in LDS beside the stage.
+#define FPT_OPT_TAG 2
+// the phases from the target to the entries, over a stage whose rows (fpt_opt_load_row) are loaded and fenced by a barrier
+template <int TAG, bool DOUBLE_Q>
+__device__ __forceinline__ void frap_opt_tile_body(FrapStage &L, FrapOptRows &O, const FrapTrainTab &T, const float *nobs, int W, int P, const int32_t *pairs,
+                                                   int B, fpt_t *part, int tid, int r, int j) {
+    const int Dm = T.D;
+    const float *w = T.par, *wt = T.tgt;
+    fpt_opt_load_next<TAG>(L, O, nobs, W, r, j);
+    __syncthreads();
+    if constexpr (DOUBLE_Q) {
+        fpt_target_ab<TAG, 0>(L, w, Dm, P, pairs, r, j);
+        __syncthreads();
+        fpt_target_q<TAG, 0>(L, w, Dm, P, pairs, r, j);
+        __syncthreads();
+        if (j == 0) fpt_opt_astar<TAG>(L, O, P, r);     // (reads y; the target's A, B below go to x and h)
+    }
+    fpt_target_ab<TAG, 1>(L, wt, Dm, P, pairs, r, j);
+    __syncthreads();
+    fpt_target_q<TAG, 1>(L, wt, Dm, P, pairs, r, j);
+    __syncthreads();
+    if (j == 0) fpt_opt_target_value<TAG, DOUBLE_Q>(L, O, P, r);
+    if (j < FRAP_MV) fpt_mv_forward<TAG>(L, w, Dm, P, pairs, r, j);
+    __syncthreads();
+    fpt_pair_forward<TAG>(L, w, Dm, P, pairs, r, j);
+    __syncthreads();
+    fpt_item_forward<TAG>(L, w, Dm, P, pairs, r, j);
+    __syncthreads();
+    if (j == 0) fpt_row_loss<TAG>(L, P, B, r);
+    __syncthreads();
+    fpt_item_backward<TAG>(L, w, Dm, P, r, j);
+    __syncthreads();
+    if (j == L.g[r]) fpt_row_backward<TAG>(L, w, Dm, P, r);
+    __syncthreads();
+    if (j < FRAP_MV) fpt_mv_backward<TAG>(L, w, Dm, P, pairs, r, j);
+    __syncthreads();
+    for (int e = tid; e < FG_N; e += FPT_T) part[e] = frap_tile_entry<TAG>(L, P, Dm, e);
+}
+
+template <bool DOUBLE_Q> __global__ void __launch_bounds__(FPT_T) frap_dqn_tile_opt_kernel(FrapTrainTab T, FrapBatch D, int n_step) {
+    constexpr int TAG = FPT_OPT_TAG + (DOUBLE_Q ? 1 : 0);
+    __shared__ FrapStage L;
+    __shared__ FrapOptRows O;
+    const int tid = threadIdx.x, r = tid / FPT_G, j = tid % FPT_G, row = blockIdx.x * FPT_TM + r;
+    for (int k = tid; k < 144; k += FPT_T) fpt_prep<TAG>(L, T.par, T.tgt, T.D, k);
+    {   // the row, held inside the ring whatever idx says
+        const bool ok = row < D.B;
+        int t = 0, e = 0, s = 0;
+        if (ok) {
+            const int32_t *p = D.idx + (size_t)row * 3;
+            t = min(max(p[0], 0), D.T - 1); e = min(max(p[1], 0), D.N - 1); s = min(max(p[2], 0), D.S - 1);
+        }
+        fpt_opt_load_row<TAG>(L, O, D.obs, D.act, D.rew, D.done, D.T, D.N, D.S, D.W, T.P, D.head, ok, t, e, s, n_step, T.gamma, r, j);
+    }
+    __syncthreads();
+    frap_opt_tile_body<TAG, DOUBLE_Q>(L, O, T, D.obs, D.W, T.P, T.pairs, D.B, T.part + (size_t)blockIdx.x * FG_N, tid, r, j);
 }
 
 // grid ceil(n / 256): every workgroup reduces the 72 chain entries for itself, then a thread its own element of the gradient

@@ -1604,6 +1604,7 @@ extern "C" int rs_fma2c_learn_buffer(rs_fma2c_learn_handle l, int32_t which, voi
 struct rs_mplight_dqn : DqnHandle {
     static constexpr const char *kCreate = "rs_mplight_dqn_create";
     FrapTrainTab T{};
+    int n_step = 1, double_q = 0;       // rs_mplight_dqn_set_target: host-side, read when a gradient is enqueued
 };
 
 extern "C" void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p) { train_destroy(p); }
@@ -1653,7 +1654,7 @@ static const char *dqn_ring_refusal(const rs_mplight_dqn *p, const rs_mplight_ri
     return nullptr;
 }
 static FrapBatch dqn_batch(const rs_mplight_ring *r, const int32_t *idx, int32_t B) {
-    return FrapBatch{r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, r->n_signals, r->width, idx, B};
+    return FrapBatch{r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, r->n_signals, r->width, idx, B, r->head};
 }
 
 // the launches; the arguments have been checked
@@ -1663,7 +1664,13 @@ static void dqn_sample_launch(const rs_mplight_dqn *, const rs_mplight_ring *r, 
 }
 static void dqn_grad_launch(const rs_mplight_dqn *p, const FrapBatch &D, float *loss_out, hipStream_t st) {
     const FrapTrainTab &T = p->T;
-    hipLaunchKernelGGL(frap_dqn_tile_kernel, dim3((D.B + FPT_TM - 1) / FPT_TM), dim3(FPT_T), 0, st, T, D);
+    const dim3 tiles((D.B + FPT_TM - 1) / FPT_TM);
+    if (p->n_step == 1 && !p->double_q)         // the options off: the plain one-step target, its own kernel
+        hipLaunchKernelGGL(frap_dqn_tile_kernel, tiles, dim3(FPT_T), 0, st, T, D);
+    else if (p->double_q)
+        hipLaunchKernelGGL(frap_dqn_tile_opt_kernel<true>, tiles, dim3(FPT_T), 0, st, T, D, p->n_step);
+    else
+        hipLaunchKernelGGL(frap_dqn_tile_opt_kernel<false>, tiles, dim3(FPT_T), 0, st, T, D, p->n_step);
     hipLaunchKernelGGL(frap_dqn_reduce_kernel, dim3((T.n + 255) / 256), dim3(256), 0, st, T, D.B, loss_out);
 }
 // the Adam step and the target copy of a handle that holds a FrapTrainTab T (rs_mplight_dqn, rs_mplight_multi)
@@ -1772,19 +1779,22 @@ extern "C" int rs_dqn_update(rs_dqn_handle p, const rs_dqn_ring *ring, int32_t b
 extern "C" int rs_dqn_sync_target(rs_dqn_handle p, void *stream) { return dqn_sync_target("rs_dqn_sync_target", p, stream); }
 extern "C" int64_t rs_dqn_steps(rs_dqn_handle p) { return p ? (int64_t)p->t : -1; }
 extern "C" int rs_dqn_set_steps(rs_dqn_handle p, int64_t t) { return train_set_steps("rs_dqn_set_steps", p, t); }
-// the target's options: the host-side fields alone (no launch, no synchronisation): what is enqueued afterwards sees them
-extern "C" int rs_dqn_set_target(rs_dqn_handle p, int32_t n_step, int32_t double_q) {
-    if (!p) { g_create_err = "rs_dqn_set_target: NULL handle"; return RS_EINVAL; }
-    if (n_step < 1 || n_step > 32) { g_create_err = "rs_dqn_set_target: need 1 <= n_step <= 32"; return RS_EINVAL; }
-    if (double_q != 0 && double_q != 1) { g_create_err = "rs_dqn_set_target: double_q is 0 or 1"; return RS_EINVAL; }
+// the target's options: the host-side fields alone (no launch, no synchronisation): what is enqueued afterwards sees them.  One
+// implementation for the three DQN handles (rs_dqn, rs_mplight_dqn, rs_mplight_multi)
+template <class H> static int dqn_set_target(const char *name, H *p, int32_t n_step, int32_t double_q) {
+    if (!p) { g_create_err = std::string(name) + ": NULL handle"; return RS_EINVAL; }
+    if (n_step < 1 || n_step > 32) { g_create_err = std::string(name) + ": need 1 <= n_step <= 32"; return RS_EINVAL; }
+    if (double_q != 0 && double_q != 1) { g_create_err = std::string(name) + ": double_q is 0 or 1"; return RS_EINVAL; }
     p->n_step = n_step; p->double_q = double_q;
     return RS_OK;
 }
-extern "C" int rs_dqn_get_target(rs_dqn_handle p, int32_t *n_step, int32_t *double_q) {
-    if (!p || !n_step || !double_q) { g_create_err = "rs_dqn_get_target: NULL handle or pointer"; return RS_EINVAL; }
+template <class H> static int dqn_get_target(const char *name, H *p, int32_t *n_step, int32_t *double_q) {
+    if (!p || !n_step || !double_q) { g_create_err = std::string(name) + ": NULL handle or pointer"; return RS_EINVAL; }
     *n_step = p->n_step; *double_q = p->double_q;
     return RS_OK;
 }
+extern "C" int rs_dqn_set_target(rs_dqn_handle p, int32_t n_step, int32_t double_q) { return dqn_set_target("rs_dqn_set_target", p, n_step, double_q); }
+extern "C" int rs_dqn_get_target(rs_dqn_handle p, int32_t *n_step, int32_t *double_q) { return dqn_get_target("rs_dqn_get_target", p, n_step, double_q); }
 
 extern "C" int rs_mplight_dqn_sample(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key,
                                      int32_t *idx_out, void *stream) {
@@ -1801,6 +1811,12 @@ extern "C" int rs_mplight_dqn_update(rs_mplight_dqn_handle p, const rs_mplight_r
 extern "C" int rs_mplight_dqn_sync_target(rs_mplight_dqn_handle p, void *stream) { return dqn_sync_target("rs_mplight_dqn_sync_target", p, stream); }
 extern "C" int64_t rs_mplight_dqn_steps(rs_mplight_dqn_handle p) { return p ? (int64_t)p->t : -1; }
 extern "C" int rs_mplight_dqn_set_steps(rs_mplight_dqn_handle p, int64_t t) { return train_set_steps("rs_mplight_dqn_set_steps", p, t); }
+extern "C" int rs_mplight_dqn_set_target(rs_mplight_dqn_handle p, int32_t n_step, int32_t double_q) {
+    return dqn_set_target("rs_mplight_dqn_set_target", p, n_step, double_q);
+}
+extern "C" int rs_mplight_dqn_get_target(rs_mplight_dqn_handle p, int32_t *n_step, int32_t *double_q) {
+    return dqn_get_target("rs_mplight_dqn_get_target", p, n_step, double_q);
+}
 
 // ---- MPLight on several maps: the shared-DQN update over M rings (resco_frap_multi.h).  The five flat vectors are the caller's; the
 // library owns the per-tile partials, the maps' pair tables and the index array of rs_mplight_multi_update
@@ -1810,6 +1826,7 @@ struct rs_mplight_multi : DqnHandle {
     int32_t n_maps = 0, P[FPM_MAPS] = {}, S[FPM_MAPS] = {};
     const int32_t *pairs[FPM_MAPS] = {};
     const void *rings_ok[FPM_MAPS][4] = {};     // per map, the ring arrays last found on this handle's device
+    int n_step = 1, double_q = 0;       // rs_mplight_maps_set_target: host-side, read when a gradient is enqueued
 };
 
 extern "C" void rs_mplight_multi_destroy(rs_mplight_multi_handle p) { train_destroy(p); }
@@ -1889,7 +1906,7 @@ static int multi_check(rs_mplight_multi *p, const rs_mplight_ring *rings, int32_
         }
         Q.cum[k + 1] = Q.cum[k] + pool;
         Q.T[k] = r->capacity; Q.N[k] = r->n_envs; Q.S[k] = r->n_signals; Q.head[k] = r->head; Q.count[k] = r->count;
-        D.map[k] = FrapMultiRing{r->obs, r->act, r->rew, r->done, p->pairs[k], r->capacity, r->n_envs, r->n_signals, r->width, p->P[k], 0, 0, 0};
+        D.map[k] = FrapMultiRing{r->obs, r->act, r->rew, r->done, p->pairs[k], r->capacity, r->n_envs, r->n_signals, r->width, p->P[k], 0, 0, 0, r->head};
     }
     if (Q.cum[p->n_maps] == 0) return refuse("total == 0: no ring holds a transition (a slot and its written successor, count >= 2)");
     return RS_OK;
@@ -1903,7 +1920,12 @@ static void multi_grad_launch(const rs_mplight_multi *p, FrapMultiBatch &D, cons
     const FrapTrainTab &T = p->T;
     D.idx = idx;
     const int tiles = frap_multi_layout(D, counts);     // <= tiles_max: sum(counts) <= max_batch has been checked
-    hipLaunchKernelGGL(frap_multi_tile_kernel, dim3(tiles), dim3(FPT_T), 0, st, T, D);
+    if (p->n_step == 1 && !p->double_q)         // the options off: the plain one-step target, its own kernel
+        hipLaunchKernelGGL(frap_multi_tile_kernel, dim3(tiles), dim3(FPT_T), 0, st, T, D);
+    else if (p->double_q)
+        hipLaunchKernelGGL(frap_multi_tile_opt_kernel<true>, dim3(tiles), dim3(FPT_T), 0, st, T, D, p->n_step);
+    else
+        hipLaunchKernelGGL(frap_multi_tile_opt_kernel<false>, dim3(tiles), dim3(FPT_T), 0, st, T, D, p->n_step);
     hipLaunchKernelGGL(frap_multi_reduce_kernel, dim3((T.n + 255) / 256), dim3(256), 0, st, T, tiles, D.B, loss_out);
 }
 static void dqn_step_launch(rs_mplight_multi *p, hipStream_t st) { frap_step_launch(p, st); }
@@ -1953,6 +1975,12 @@ extern "C" int rs_mplight_multi_step(rs_mplight_multi_handle p, void *stream) { 
 extern "C" int rs_mplight_multi_sync_target(rs_mplight_multi_handle p, void *stream) { return dqn_sync_target("rs_mplight_multi_sync_target", p, stream); }
 extern "C" int64_t rs_mplight_multi_steps(rs_mplight_multi_handle p) { return p ? (int64_t)p->t : -1; }
 extern "C" int rs_mplight_multi_set_steps(rs_mplight_multi_handle p, int64_t t) { return train_set_steps("rs_mplight_multi_set_steps", p, t); }
+extern "C" int rs_mplight_maps_set_target(rs_mplight_multi_handle p, int32_t n_step, int32_t double_q) {
+    return dqn_set_target("rs_mplight_maps_set_target", p, n_step, double_q);
+}
+extern "C" int rs_mplight_maps_get_target(rs_mplight_multi_handle p, int32_t *n_step, int32_t *double_q) {
+    return dqn_get_target("rs_mplight_maps_get_target", p, n_step, double_q);
+}
 
 // ---- "does this policy fit this handle?" and "may this handle take part in a loop?": asked by rs_group_step, rs_group_rollout, the
 // three training loops and rs_fma2c_record.  Each returns NULL or the reason; the caller puts its own name in front.

@@ -38,9 +38,10 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_dqn_create', 'rs_dqn_sample', 'rs_dqn_grad', 'rs_dqn_step', 'rs_dqn_update', 'rs_dqn_steps', 'rs_dqn_set_steps',
                'rs_dqn_set_target', 'rs_dqn_get_target', 'rs_dqn_destroy',
                'rs_mplight_dqn_create', 'rs_mplight_dqn_sample', 'rs_mplight_dqn_grad', 'rs_mplight_dqn_step', 'rs_mplight_dqn_update',
-               'rs_mplight_dqn_steps', 'rs_mplight_dqn_set_steps', 'rs_mplight_dqn_destroy',
+               'rs_mplight_dqn_steps', 'rs_mplight_dqn_set_steps', 'rs_mplight_dqn_set_target', 'rs_mplight_dqn_get_target', 'rs_mplight_dqn_destroy',
                'rs_mplight_multi_create', 'rs_mplight_multi_sample', 'rs_mplight_multi_grad', 'rs_mplight_multi_step', 'rs_mplight_multi_update',
-               'rs_mplight_multi_sync_target', 'rs_mplight_multi_steps', 'rs_mplight_multi_set_steps', 'rs_mplight_multi_destroy',
+               'rs_mplight_multi_sync_target', 'rs_mplight_multi_steps', 'rs_mplight_multi_set_steps', 'rs_mplight_maps_set_target',
+               'rs_mplight_maps_get_target', 'rs_mplight_multi_destroy',
                'rs_idqn_pack_weights', 'rs_dqn_sync_target', 'rs_mplight_dqn_sync_target', 'rs_group_train',
                'rs_ppo_perm', 'rs_ippo_pack_weights', 'rs_group_ppo_train', 'rs_info_kernel', 'rs_set_demand', 'rs_demand_info']
 
@@ -143,6 +144,9 @@ def bind(L):
         L.rs_mplight_dqn_steps.restype = C.c_int64
         if hasattr(L, 'rs_mplight_dqn_set_steps'):      # (a host emulation may not have it)
             L.rs_mplight_dqn_set_steps.argtypes = [vp, C.c_int64]
+        if hasattr(L, 'rs_mplight_dqn_set_target'):     # (a host emulation may not have them)
+            L.rs_mplight_dqn_set_target.argtypes = [vp, i32, i32]
+            L.rs_mplight_dqn_get_target.argtypes = [vp, vp, vp]
         L.rs_mplight_dqn_destroy.argtypes = [vp]
         L.rs_mplight_dqn_destroy.restype = None
     if hasattr(L, 'rs_mplight_multi_create'):
@@ -155,6 +159,9 @@ def bind(L):
         L.rs_mplight_multi_steps.argtypes = [vp]
         L.rs_mplight_multi_steps.restype = C.c_int64
         L.rs_mplight_multi_set_steps.argtypes = [vp, C.c_int64]
+        if hasattr(L, 'rs_mplight_maps_set_target'):   # (a host emulation may not have them)
+            L.rs_mplight_maps_set_target.argtypes = [vp, i32, i32]
+            L.rs_mplight_maps_get_target.argtypes = [vp, vp, vp]
         L.rs_mplight_multi_destroy.argtypes = [vp]
         L.rs_mplight_multi_destroy.restype = None
     if hasattr(L, 'rs_group_train'):

@@ -5,14 +5,15 @@ weights do not depend on a map's signals or phase pairs, so one vector serves ev
 afford this, here the maps step in lock-step on one GPU.
 
     python tools/mplight_multimap_train.py maps=cologne3,ingolstadt7 [n_envs per map: comma list or one value] [episodes] [batch]
-                                           [replay_steps] [seed] [full] [--eval-on cologne8,...]
+                                           [replay_steps] [seed] [full] [--eval-on cologne8,...] [--n-step K] [--double-q]
 
 Per env-step and map: policy_m.act -> replay_m.stage -> env_m.step -> replay_m.commit; then ONE learner.observe_step over all rings
 (a Python-driven loop: the library loop and pipes per map are not built for this learner).  Every policy reads learner.flat
 (share_weights); policy m draws with seed 7 + seed + 101 m; epsilon and the step key come from the one learner.t.  The maps must have
 one episode length (horizon_steps).  Prints one JSON line per episode with the average trip delay per map, and a final line that adds,
 for every --eval-on map, the greedy delay of the shared weights (zero-shot) beside that map's on-device random policy on the same demand.
-`full`: MPLightFULL (states.mplight_full, demand_shape 4).
+`full`: MPLightFULL (states.mplight_full, demand_shape 4).  --n-step K (1 .. 32) and --double-q (the flags of tools/idqn_train.py): the
+target's options of the shared update (rs_mplight_maps_set_target), every row walking its own map's ring; part of a checkpoint's signature.
 
 Checkpoints (resco_amd/checkpoint.py, the flags of tools/mplight_train.py): --save PATH [--save-freq K] [--save-replay], --load PATH,
 --stop-after K; the checkpoint's map is '+'.join(maps).  --load PATH --eval loads the weights alone -- from a multi-map checkpoint or
@@ -37,6 +38,7 @@ from resco_amd.agents.mplight import FusedMPLight, MPLightReplay, frap_from_scen
 from resco_amd.agents.mplight_multi import MultiMapMPLightLearner                           # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                                           # noqa: E402
 from resco_amd import checkpoint, demand                                                    # noqa: E402
+from tools.idqn_train import target_flags                                                   # noqa: E402
 from tools.mplight_train import delay, greedy_evaluation, greedy_on_variants                # noqa: E402
 
 
@@ -51,8 +53,8 @@ def random_delay(env, steps):
 
 
 def main(maps=('cologne3', 'ingolstadt7'), n_envs=(256,), episodes=30, batch=256, replay_steps=2048, seed=0, full=False, eval_on=(), quiet=False, made=None,
-         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, demand_variants=None, eval_demand=0):
-    """-> (rows, final); a run that leaves at stop_after returns (rows, None).  made: a dict that receives the learner (closed when
+         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, demand_variants=None, eval_demand=0, n_step=1, double_q=False):
+    """n_step / double_q: the learner's options of the same names.  -> (rows, final); a run that leaves at stop_after returns (rows, None).  made: a dict that receives the learner (closed when
     the call returns; its vectors stay readable).  demand_variants / eval_demand: the demand flags of the module docstring."""
     n_var, var_kw = demand.parse_spec(demand_variants)
     n_eval, eval_kw = demand.parse_spec(eval_demand)
@@ -72,7 +74,8 @@ def main(maps=('cologne3', 'ingolstadt7'), n_envs=(256,), episodes=30, batch=256
         raise ValueError('the maps step in lock-step and must have one horizon_steps, got %s' % {m: e.horizon_steps for m, e in zip(maps, envs)})
     nets = [frap_from_scenario(e.scenario, D).cuda() for e in envs]
     nets[0].init_like_reference(seed)
-    learner = MultiMapMPLightLearner(nets, [e.n_signals for e in envs], gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed)
+    learner = MultiMapMPLightLearner(nets, [e.n_signals for e in envs], gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed, n_step=n_step,
+                                     double_q=double_q)
     if made is not None:
         made['learner'] = learner
     policies = [FusedMPLight(net, e.scenario, seed=7 + seed + 101 * m) for m, (net, e) in enumerate(zip(nets, envs))]
@@ -174,6 +177,8 @@ def main(maps=('cologne3', 'ingolstadt7'), n_envs=(256,), episodes=30, batch=256
 if __name__ == '__main__':
     ckpt, a = checkpoint.tool_flags(sys.argv[1:])
     dem, a = demand.tool_flags(a)
+    opts, a = target_flags(a)
+    ckpt.update(opts)
     eval_on = ()
     if '--eval-on' in a:
         i = a.index('--eval-on')

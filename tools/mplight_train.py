@@ -5,12 +5,16 @@ resco_amd/agents/mplight_learn_fused.py on the policy's own weight vector) -> we
 tools/idqn_train.py for the reference's MPLight (agents/mplight.py, config/agent_config.py:101-113; batching:
 resco_amd/agents/mplight.py).
 
-    python tools/mplight_train.py [--device-update | --device-loop] [map] [n_envs] [episodes] [batch] [replay_steps] [seed] [full]
+    python tools/mplight_train.py [--n-step K] [--double-q] [--device-update | --device-loop] [map] [n_envs] [episodes] [batch] [replay_steps] [seed] [full]
 
 Prints one JSON line per episode (mean episode return of rewards.pressure per signal, average trip delay as utils/readXML.py
 computes it, epsilon, env-steps/s including learning) and a final line with the best training episode and the on-device random
 policy on the same demand.  --device-loop (implies --device-update): the loop itself in the library as well
 (agents/train_fused.py: DeviceTrainer, rs_group_train), one call per episode; the same rows.  `full`: MPLightFULL (states.mplight_full, demand_shape 4).
+
+--n-step K (1 .. 32) and --double-q, in every mode (the flags of tools/idqn_train.py): n-step returns (truncated at the newest slot of
+the ring, cut at an episode end) and Double DQN's bootstrap (the online network's best of ALL pairs, valued by the target network);
+both are part of a checkpoint's signature.  Without them: PFRL's plain one-step DQN.
 
 Checkpoints (resco_amd/checkpoint.py), in every mode: --save PATH [--save-freq K] [--save-replay] (the replay ring only with --save-replay: it is the large part; without it a resumed run is a valid continuation, not the same one) writes the training state after every K-th
 episode and after the last; --load PATH continues at the stored episode (`episodes` stays the planned total, so the schedules and the
@@ -37,6 +41,7 @@ from resco_amd.agents.mplight_learn_fused import FusedMPLightLearner            
 from resco_amd.agents.train_fused import DeviceTrainer                                      # noqa: E402
 from resco_amd.multi_signal import VecMultiSignal                                           # noqa: E402
 from resco_amd import checkpoint, demand                                                    # noqa: E402
+from tools.idqn_train import target_flags                                                   # noqa: E402
 
 
 def delay(env):
@@ -63,8 +68,8 @@ def greedy_on_variants(env, policy, state, actions, steps, seed, variants):
 
 
 def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, seed=0, full=False, quiet=False, device_update=False, device_loop=False, chunk=0,
-         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, demand_variants=None, eval_demand=0):
-    """device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
+         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, demand_variants=None, eval_demand=0, n_step=1, double_q=False):
+    """n_step / double_q: the learners' options of the same names.  device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
     save / save_freq / save_replay / load / eval_only / stop_after: the checkpoint flags of the module docstring; a run that leaves
     at stop_after returns (rows, None).  demand_variants / eval_demand: the demand flags of the module docstring."""
     device_update = device_update or device_loop
@@ -77,9 +82,9 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
     net = frap_from_scenario(env.scenario, 4 if full else 1).cuda()
     net.init_like_reference(seed)
     if device_update:
-        learner = FusedMPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed, n_signals=S)
+        learner = FusedMPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed, n_signals=S, n_step=n_step, double_q=double_q)
     else:
-        learner = MPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch)
+        learner = MPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, n_step=n_step, double_q=double_q)
     policy = FusedMPLight(net, env.scenario, seed=7 + seed)
     if device_update:
         policy.share_weights(learner.flat)      # the policy reads the vector the update writes: no re-pack per step
@@ -172,6 +177,8 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
 if __name__ == '__main__':
     ckpt, a = checkpoint.tool_flags(sys.argv[1:])
     dem, a = demand.tool_flags(a)
+    opts, a = target_flags(a)
+    ckpt.update(opts)
     device_loop = bool(a) and a[0] == '--device-loop'
     device_update = device_loop or (bool(a) and a[0] == '--device-update')
     a = a[1:] if device_update else a
