@@ -491,7 +491,8 @@ void rs_ppo_destroy(rs_ppo_handle p);
  * rs_dqn_grad takes its rows from the caller: a row at `newest` is the caller's mistake as before; the walk is bounded by n_step and
  * by mod T, so such a row reads wrong data but never outside the ring.
  * All calls are asynchronous on `stream`; every sum has one fixed order (no float atomics): the same state gives the same bits.
- * Workspace, allocated once by rs_dqn_create for max_batch rows and padded to lmax for every signal.
+ * Workspace, allocated once by rs_dqn_create for max_batch rows and padded to lmax for every signal (with it, whether or not they are
+ * ever turned on, what prioritised replay needs: the rows' weights and |delta|, 8 B per row and signal, and Z_s).
  * Refusals (RS_EINVAL, text in rs_last_error(NULL), nothing launched): a NULL handle or pointer, batch outside 1 .. max_batch,
  * count < 2, capacity < 2, n_envs < 1, head or count outside the ring, n_updates < 1, a ring array (obs, act, rew, done) or an index
  * array that the runtime does not know as memory of the handle's device (asked once per set of ring pointers, every call for idx);
@@ -525,6 +526,48 @@ int rs_dqn_set_steps(rs_dqn_handle p, int64_t t);
 int rs_dqn_set_target(rs_dqn_handle p, int32_t n_step, int32_t double_q);
 int rs_dqn_get_target(rs_dqn_handle p, int32_t *n_step, int32_t *double_q);
 void rs_dqn_destroy(rs_dqn_handle p);
+
+/* ---- IDQN: prioritised experience replay in that update (resco_amd/csrc/resco_dqn_per.h) ---------------------------------
+ * Off on a new handle; while off exactly the launches described above run.  The state is the caller's and borrowed, like params:
+ *   prio f32 [capacity][n_envs][S] (the layout of rew): a leaf q = (|delta| + eps)^alpha >= 0, already exponentiated;
+ *   ssum f32 [capacity][S]: the sum of a slot's n_envs leaves, ALWAYS re-summed from the leaves in one fixed order (the header of
+ *   resco_dqn_per.h states it), never adjusted by a difference;  pmax f32 [S]: the largest q ever written for the signal (start: 1),
+ *   raised by an integer max on the bit pattern.  No float atomics: the same state gives the same bits.
+ * rs_dqn_set_priorities: the host-side fields alone, like rs_dqn_set_target (no launch; what is enqueued afterwards sees them); NULL:
+ * off.  capacity and n_envs are those of the ring the state belongs to; alpha and beta0 in [0, 1], eps > 0, beta_steps >= 0.
+ * rs_dqn_get_priorities: the struct as it stands (untouched while off) and whether it is on.
+ * rs_dqn_per_rebuild: every ssum from prio (at the start, after a checkpoint load); bit for bit what fill and commit leave.
+ * rs_dqn_per_fill: prio[slot][e][s] = pmax[s] for all e, s, and ssum[slot][s] re-summed: a new transition enters at the maximum
+ * priority.  The newest slot, which has no successor yet, is filled like any other: the draw leaves it out by position, not by value.
+ * rs_dqn_per_commit: for the rows idx of the LAST rs_dqn_grad (same batch): prio <- powf(|delta| + eps, alpha) with the |delta| that
+ * call left in the workspace (an infinite value becomes 0), pmax raised, the touched (slot, s) re-summed.
+ * With priorities on:
+ *   rs_dqn_sample draws by priority.  The valid slots are k = 0 .. count - 2 from the oldest, head - count.  For draw i of signal s
+ *   in update u: r_j = (hash(seed ^ 0x9E3779B9, u, s, i, j) >> 8) 2^-24, j = 0, 1.  With Z_s the total of the valid ssum[.][s], the slot
+ *   is the first valid k of positive weight whose inclusive cumulative ssum exceeds r_0 Z_s; the environment the first e of positive
+ *   weight whose inclusive cumulative prio[slot][.][s] exceeds r_1 ssum[slot][s]; where rounding lets the value fall past the end, the
+ *   last entry of positive weight.  An entry of weight 0 is never drawn (nothing positive at all: entry 0).
+ *   rs_dqn_grad weights the loss: w_i = (M q_i / Z_s)^-beta / max_j (M q_j / Z_s)^-beta, M = (count - 1) n_envs, the max over the batch
+ *   rows of signal s, q and Z_s as they stand when the gradient is taken (a row of priority 0, which no draw gives, has weight 0);
+ *   row i contributes w_i Huber(delta_i) to the loss and w_i clamp(delta_i, -1, 1) / batch to dQ.  beta = min(1, beta0 + (1 - beta0)
+ *   u / beta_steps) with u the step count so far, in double, rounded once; beta_steps 0: beta0.  The target is rs_dqn_set_target's.
+ *   rs_dqn_update is sample, grad, step, commit per update.  rs_group_train (IDQN) fills each step's slot on the learner's stream
+ *   after the pipes' recorders, before the target sync and the update.
+ * Refusals (RS_EINVAL, a text, nothing launched, the handle unchanged): a NULL handle; a NULL array or one that is not memory of the
+ * handle's device; capacity < 2 or n_envs < 1; alpha or beta0 outside [0, 1]; eps <= 0; beta_steps < 0; a ring whose capacity or
+ * n_envs differ from the state's, at any call that takes a ring; slot outside the ring; rebuild, fill or commit while off; a commit
+ * whose batch is not that of the last rs_dqn_grad with priorities on (or without one since rs_dqn_set_priorities). */
+typedef struct rs_dqn_per {
+    float *prio, *ssum, *pmax;
+    int32_t capacity, n_envs;
+    double alpha, beta0, eps;
+    int64_t beta_steps;
+} rs_dqn_per;
+int rs_dqn_set_priorities(rs_dqn_handle p, const rs_dqn_per *per);
+int rs_dqn_get_priorities(rs_dqn_handle p, rs_dqn_per *out, int32_t *on);
+int rs_dqn_per_rebuild(rs_dqn_handle p, void *stream);
+int rs_dqn_per_fill(rs_dqn_handle p, int32_t slot, void *stream);
+int rs_dqn_per_commit(rs_dqn_handle p, const rs_dqn_ring *ring, const int32_t *idx, int32_t batch, void *stream);
 
 /* ---- MPLight: the shared-DQN update on the device (resco_amd/csrc/resco_frap_train.h) -------------------------------
  * What resco_amd/agents/mplight.py does per update -- MPLightReplay.sample, MPLightLearner.loss, its backward through the ONE shared

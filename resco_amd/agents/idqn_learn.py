@@ -148,6 +148,37 @@ def target_options_signature(fields, n_step, double_q):
     return fields
 
 
+PER_DEFAULTS = dict(alpha=0.6, beta0=0.4, beta_steps=0, eps=1e-6)
+
+
+def per_options(per, name):
+    """the options of prioritised replay as a learner takes them: None (off), or a dict of any of PER_DEFAULTS' keys -> the full
+    dict, checked (rs_dqn_set_priorities of include/resco_sim.h refuses the same values)"""
+    if per is None:
+        return None
+    unknown = sorted(set(per) - set(PER_DEFAULTS))
+    if unknown:
+        raise ValueError('%s: unknown prioritised-replay options %s (known: %s)' % (name, unknown, sorted(PER_DEFAULTS)))
+    o = dict(PER_DEFAULTS, **per)
+    o = dict(alpha=float(o['alpha']), beta0=float(o['beta0']), beta_steps=int(o['beta_steps']), eps=float(o['eps']))
+    if not 0.0 <= o['alpha'] <= 1.0:
+        raise ValueError('%s: per alpha must lie in [0, 1], got %r' % (name, o['alpha']))
+    if not 0.0 <= o['beta0'] <= 1.0:
+        raise ValueError('%s: per beta0 must lie in [0, 1], got %r' % (name, o['beta0']))
+    if not o['eps'] > 0.0:
+        raise ValueError('%s: per eps must be positive, got %r' % (name, o['eps']))
+    if o['beta_steps'] < 0:
+        raise ValueError('%s: per beta_steps must not be negative, got %r' % (name, o['beta_steps']))
+    return o
+
+
+def per_options_signature(fields, per):
+    """target_options_signature's rule for prioritised replay: the keys are there only when it is on"""
+    if per is not None:
+        fields.update({'per_' + k: per[k] for k in sorted(per)})
+    return fields
+
+
 def _sample_from_device_position(rp, batch_size, n_step=1, gamma=None):
     """DeviceReplay.sample with the ring position read from device memory and PyTorch's default generator: every value
     that changes between calls lives on the device, so the call can be captured in a HIP graph and replayed."""
@@ -172,9 +203,13 @@ def linear_epsilon(t, start, end, decay_steps):
 class BatchedDQNLearner:
     """DQN update for the S stacked per-signal networks of a BatchedIDQN."""
 
-    def __init__(self, qnet, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, n_step=1, double_q=False):
-        """n_step (1 .. 32): n-step returns (nstep_walk); double_q: Double DQN's bootstrap.  The defaults are PFRL's plain DQN."""
+    def __init__(self, qnet, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, n_step=1, double_q=False, per=None):
+        """n_step (1 .. 32): n-step returns (nstep_walk); double_q: Double DQN's bootstrap.  The defaults are PFRL's plain DQN.
+        per: refused -- prioritised replay exists in the fused learner only."""
         assert isinstance(qnet, BatchedIDQN)
+        if per is not None:
+            raise ValueError('BatchedDQNLearner has no prioritised replay: it is built into the fused update only '
+                             '(FusedDQNLearner(per=...), tools/idqn_train.py --device-update or --device-loop)')
         self.n_step, self.double_q = int(n_step), bool(double_q)
         if not 1 <= self.n_step <= 32:
             raise ValueError('BatchedDQNLearner: n_step must be in 1 .. 32, got %d' % self.n_step)

@@ -38,6 +38,7 @@ class DeviceTrainer:
         self.eps_start, self.eps_end, self.decay_steps = float(eps_start), float(eps_end), int(decay_steps)
         if isinstance(learner, FusedDQNLearner):
             self.agent, self.updates_per_step = 'idqn', int(updates_per_step)
+            learner.attach(replay)              # (prioritised replay: the learner's handle carries the priorities, sized from this ring)
             if not hasattr(policy, '_dev'):
                 policy.refresh_on_device()      # the library re-packs into the policy's own device buffers: they have to exist
         elif isinstance(learner, FusedMPLightLearner):

@@ -38,6 +38,10 @@
 //   successor rows must finish before the target's max in any case, so a separate launch would put one more launch gap on the
 //   same dependent chain and run on the same tiles x S workgroups.
 //   The cost is one more tile forward in launch 1, paid only with double_q on.
+//
+// Prioritised replay (rs_dqn_set_priorities) is resco_dqn_per.h: its own draw, the rows' importance weights, launch 2 with them
+// (dqn_fwd_bwd_per_kernel) and the write-back of the priorities.  Off by default, and then nothing of it is launched: every kernel
+// of this file stays as it is.
 #pragma once
 #include "resco_train.h"
 

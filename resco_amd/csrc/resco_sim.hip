@@ -116,6 +116,7 @@ __device__ unsigned long long *g_sec_prof;
 #include "resco_ppo.h"
 #include "resco_ppo_train.h"
 #include "resco_dqn_train.h"
+#include "resco_dqn_per.h"
 #include "resco_frap_train.h"
 #include "resco_frap_multi.h"
 #include "resco_group_train.h"
@@ -1176,6 +1177,11 @@ struct rs_dqn : DqnHandle {
     static constexpr const char *kCreate = "rs_dqn_create";
     DqnTrainTab T{};
     int n_step = 1, double_q = 0;       // rs_dqn_set_target: host-side, read when a gradient is enqueued
+    // prioritised replay (resco_dqn_per.h).  rs_dqn_set_priorities: host-side, read when a launch is enqueued
+    rs_dqn_per per{};
+    int per_on = 0;
+    int ad_batch = 0;                   // the batch of the last gradient taken with priorities on: its |delta| stands in per_ad (0: none)
+    float *per_z = nullptr, *per_w = nullptr, *per_ad = nullptr;    // Z_s [S]; the rows' weights and |delta| [S][bpad_max]
 };
 
 extern "C" void rs_dqn_destroy(rs_dqn_handle p) { train_destroy(p); }
@@ -1187,7 +1193,10 @@ extern "C" int rs_dqn_create(int32_t device_id, int32_t n_signals, int32_t lmax,
     const int rc = train_create("rs_dqn_create", "a visible device, 1 <= signals, 2 <= lmax <= 17, 1 <= amax <= 8, 1 <= max_batch", device_id, n_signals, lmax,
                                 lanes, n_actions, amax, cfg, {params, target, grads, m, v}, NT, max_batch, ppt_p_size(DQN_NH), out, [&](rs_dqn *p) {
         return p->alloc((void **)&p->T.y, (size_t)n_signals * p->T.bpad_max * sizeof(float)) &&
-               p->alloc((void **)&p->idx, (size_t)max_batch * n_signals * 2 * sizeof(int32_t));
+               p->alloc((void **)&p->idx, (size_t)max_batch * n_signals * 2 * sizeof(int32_t)) &&
+               p->alloc((void **)&p->per_z, (size_t)n_signals * sizeof(float)) &&
+               p->alloc((void **)&p->per_w, (size_t)n_signals * p->T.bpad_max * sizeof(float)) &&
+               p->alloc((void **)&p->per_ad, (size_t)n_signals * p->T.bpad_max * sizeof(float));
     });
     if (rc != RS_OK) return rc;
     rs_dqn *p = *out;
@@ -1204,26 +1213,56 @@ static bool dqn_on_device(const void *ptr, int device) {
     if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }     // (not memory the runtime knows)
     return at.device == device;
 }
-static const char *dqn_ring_refusal(const rs_dqn *, const rs_dqn_ring *) { return nullptr; }      // (a ring of rs_dqn_ring has no sizes of its own to check)
-static DqnBatch dqn_batch(const rs_dqn_ring *r, const int32_t *idx, int32_t B) {
-    return DqnBatch{(const __half *)r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, idx, B, r->head};
+// (a ring of rs_dqn_ring has no sizes of its own to check; the priorities were sized for one ring)
+static const char *dqn_ring_refusal(const rs_dqn *p, const rs_dqn_ring *r) {
+    if (p->per_on && (r->capacity != p->per.capacity || r->n_envs != p->per.n_envs))
+        return "the priorities of rs_dqn_set_priorities belong to a ring of another capacity or n_envs";
+    return nullptr;
+}
+// the minibatch the kernels take, and on the host the ring's count beside it (the prioritised weights' M and Z_s)
+struct DqnBatchAt : DqnBatch { int32_t count; };
+static DqnBatchAt dqn_batch(const rs_dqn_ring *r, const int32_t *idx, int32_t B) {
+    return DqnBatchAt{DqnBatch{(const __half *)r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, idx, B, r->head}, r->count};
 }
 
 // the launches; the arguments have been checked
+// the table of the prioritised-replay kernels as the handle stands: beta from the steps taken so far
+static DqnPer dqn_per_tab(const rs_dqn *p) {
+    const rs_dqn_per &q = p->per;
+    return DqnPer{q.prio, q.ssum, q.pmax, p->per_z, p->per_w, p->per_ad, q.capacity, q.n_envs, p->T.S, p->T.bpad_max, (float)q.alpha, (float)q.eps,
+                  dqn_per_beta(q.beta0, q.beta_steps, p->t)};
+}
+static unsigned per_grid(long long units) { return (unsigned)((units + DQN_PER_WAVES - 1) / DQN_PER_WAVES); }
 static void dqn_sample_launch(const rs_dqn *p, const rs_dqn_ring *r, int B, uint32_t seed, uint32_t key, int32_t *idx, hipStream_t st) {
+    if (p->per_on) {
+        const DqnPer P = dqn_per_tab(p);
+        hipLaunchKernelGGL(dqn_per_z_kernel, dim3(per_grid(P.S)), dim3(PPT_T), 0, st, P, r->head, r->count);
+        hipLaunchKernelGGL(dqn_per_sample_kernel, dim3(per_grid((long long)B * P.S)), dim3(PPT_T), 0, st, P, seed, key, r->head, r->count, B, idx);
+        return;
+    }
     hipLaunchKernelGGL(dqn_sample_kernel, dim3((B * p->T.S + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, seed, key, p->T.S, r->capacity, r->n_envs, r->head,
                        r->count, B, idx);
 }
-static void dqn_grad_launch(const rs_dqn *p, const DqnBatch &D, float *loss_out, hipStream_t st) {
+static void dqn_grad_launch(rs_dqn *p, const DqnBatchAt &At, float *loss_out, hipStream_t st) {
+    const DqnBatch &D = At;
     const DqnTrainTab &T = p->T;
     const int tiles = (D.B + PPT_TM - 1) / PPT_TM, chunks = (tiles * PPT_TM + PPT_CH - 1) / PPT_CH;
+    const DqnPer P = p->per_on ? dqn_per_tab(p) : DqnPer{};
+    if (p->per_on) {
+        hipLaunchKernelGGL(dqn_per_z_kernel, dim3(per_grid(P.S)), dim3(PPT_T), 0, st, P, D.head, At.count);
+        hipLaunchKernelGGL(dqn_per_weight_kernel, dim3(P.S), dim3(PPT_T), 0, st, P, D, At.count);
+        p->ad_batch = D.B;
+    }
     if (p->n_step == 1 && !p->double_q)         // the options off: the plain one-step target, its own kernel
         hipLaunchKernelGGL(dqn_target_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
     else if (p->double_q)
         hipLaunchKernelGGL(dqn_target_opt_kernel<true>, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D, p->n_step);
     else
         hipLaunchKernelGGL(dqn_target_opt_kernel<false>, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D, p->n_step);
-    hipLaunchKernelGGL(dqn_fwd_bwd_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
+    if (p->per_on)
+        hipLaunchKernelGGL(dqn_fwd_bwd_per_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D, (const float *)P.w, P.ad);
+    else
+        hipLaunchKernelGGL(dqn_fwd_bwd_kernel, dim3(tiles, T.S), dim3(PPT_T), 0, st, T, D);
     hipLaunchKernelGGL(dqn_fc1_bwd_kernel, dim3(T.H * 2, chunks, T.S), dim3(PPT_T), 0, st, T, D);
     hipLaunchKernelGGL(dqn_reduce_kernel, dim3(T.S, T.H + (ppt_n_small(DQN_NH) + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, T, D.B, loss_out);
 }
@@ -1231,6 +1270,21 @@ static void dqn_step_launch(rs_dqn *p, hipStream_t st) {
     const PpoStepConsts K = ppo_step_consts(p->cfg.lr, p->cfg.adam_eps, p->cfg.beta1, p->cfg.beta2, 0.0, p->t + 1);
     hipLaunchKernelGGL(dqn_adam_kernel, dim3(p->T.S, p->T.H + 1), dim3(PPT_T), 0, st, p->T, K);
     if (hipPeekAtLastError() == hipSuccess) p->t += 1;      // a step that could not be launched is not counted
+}
+// the priorities of the rows D of the last gradient (rs_dqn_per_commit; the last launches of an update with priorities on)
+static void dqn_per_commit_launch(const rs_dqn *p, const DqnBatch &D, hipStream_t st) {
+    const DqnPer P = dqn_per_tab(p);
+    hipLaunchKernelGGL(dqn_per_leaf_kernel, dim3((D.B * P.S + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, P, D);
+    hipLaunchKernelGGL(dqn_per_resum_kernel, dim3(per_grid((long long)D.B * P.S)), dim3(PPT_T), 0, st, P, D);
+}
+static void dqn_per_fill_launch(const rs_dqn *p, int slot, hipStream_t st) {
+    const DqnPer P = dqn_per_tab(p);
+    const long long blocks = ((long long)P.N * P.S + PPT_T - 1) / PPT_T;
+    const unsigned need = per_grid(P.S), cover = (unsigned)(blocks < 1024 ? blocks : 1024);     // one wave per signal at least; the leaves grid-stride
+    hipLaunchKernelGGL(dqn_per_fill_kernel, dim3(need > cover ? need : cover), dim3(PPT_T), 0, st, P, slot);
+}
+static void dqn_after_step_launch(rs_dqn *p, const rs_dqn_ring *r, int batch, hipStream_t st) {
+    if (p->per_on) dqn_per_commit_launch(p, dqn_batch(r, p->idx, batch), st);
 }
 
 // ------------------------------------------------------------------------------------------------ fused MPLight (FRAP) policy
@@ -1731,12 +1785,15 @@ template <class H> static int dqn_check_idx(const H *p, const void *idx, const c
     g_create_err = std::string(name) + ": " + what + (idx ? " is not device memory of this handle's device" : " is NULL");
     return RS_EINVAL;
 }
+// what an update enqueues behind its Adam step: nothing, but for IDQN with priorities on (the overload on rs_dqn) their commit
+template <class H, class Ring> static void dqn_after_step_launch(H *, const Ring *, int, hipStream_t) {}
 // n_updates x [sample -> gradient -> Adam step] (*_update, rs_group_train); the caller reads hipGetLastError
 template <class H, class Ring> static void dqn_update_launch(H *p, const Ring *ring, int batch, uint32_t seed, int n_updates, float *loss_out, hipStream_t st) {
     for (int j = 0; j < n_updates; ++j) {       // the launches of a stream run in order: update j + 1 may overwrite idx and the workspace
         dqn_sample_launch(p, ring, batch, seed, (uint32_t)p->t, p->idx, st);
         dqn_grad_launch(p, dqn_batch(ring, p->idx, batch), loss_out, st);
         dqn_step_launch(p, st);
+        dqn_after_step_launch(p, ring, batch, st);
         if (hipPeekAtLastError() != hipSuccess) break;      // nothing more is enqueued behind a launch that failed
     }
 }
@@ -1795,6 +1852,52 @@ template <class H> static int dqn_get_target(const char *name, H *p, int32_t *n_
 }
 extern "C" int rs_dqn_set_target(rs_dqn_handle p, int32_t n_step, int32_t double_q) { return dqn_set_target("rs_dqn_set_target", p, n_step, double_q); }
 extern "C" int rs_dqn_get_target(rs_dqn_handle p, int32_t *n_step, int32_t *double_q) { return dqn_get_target("rs_dqn_get_target", p, n_step, double_q); }
+
+// ---- prioritised replay of the IDQN learner (resco_dqn_per.h)
+static int per_refuse(const char *name, const char *why) { g_create_err = std::string(name) + ": " + why; return RS_EINVAL; }
+extern "C" int rs_dqn_set_priorities(rs_dqn_handle p, const rs_dqn_per *per) {
+    const char *name = "rs_dqn_set_priorities";
+    if (!p) return per_refuse(name, "NULL handle");
+    if (!per) { p->per_on = 0; p->ad_batch = 0; return RS_OK; }
+    if (!per->prio || !per->ssum || !per->pmax) return per_refuse(name, "a priority array (prio, ssum, pmax) is NULL");
+    if (per->capacity < 2 || per->n_envs < 1) return per_refuse(name, "need capacity >= 2 and n_envs >= 1");
+    if (!(per->alpha >= 0.0 && per->alpha <= 1.0)) return per_refuse(name, "alpha must lie in [0, 1]");
+    if (!(per->beta0 >= 0.0 && per->beta0 <= 1.0)) return per_refuse(name, "beta0 must lie in [0, 1]");
+    if (!(per->eps > 0.0)) return per_refuse(name, "need eps > 0");
+    if (per->beta_steps < 0) return per_refuse(name, "need beta_steps >= 0");
+    for (const void *a : {(const void *)per->prio, (const void *)per->ssum, (const void *)per->pmax})
+        if (!dqn_on_device(a, p->device)) return per_refuse(name, "a priority array is not device memory of this handle's device (another device, or host memory)");
+    p->per = *per; p->per_on = 1; p->ad_batch = 0;
+    return RS_OK;
+}
+extern "C" int rs_dqn_get_priorities(rs_dqn_handle p, rs_dqn_per *out, int32_t *on) {
+    if (!p || !out || !on) return per_refuse("rs_dqn_get_priorities", "NULL handle or pointer");
+    *on = p->per_on;
+    if (p->per_on) *out = p->per;
+    return RS_OK;
+}
+extern "C" int rs_dqn_per_rebuild(rs_dqn_handle p, void *stream) {
+    if (!p) return per_refuse("rs_dqn_per_rebuild", "NULL handle");
+    if (!p->per_on) return per_refuse("rs_dqn_per_rebuild", "priorities are off (rs_dqn_set_priorities)");
+    return on_device(p->device, [&] {
+        const DqnPer P = dqn_per_tab(p);
+        hipLaunchKernelGGL(dqn_per_rebuild_kernel, dim3(per_grid((long long)P.T * P.S)), dim3(PPT_T), 0, (hipStream_t)stream, P);
+    });
+}
+extern "C" int rs_dqn_per_fill(rs_dqn_handle p, int32_t slot, void *stream) {
+    if (!p) return per_refuse("rs_dqn_per_fill", "NULL handle");
+    if (!p->per_on) return per_refuse("rs_dqn_per_fill", "priorities are off (rs_dqn_set_priorities)");
+    if (slot < 0 || slot >= p->per.capacity) return per_refuse("rs_dqn_per_fill", "slot outside the ring");
+    return on_device(p->device, [&] { dqn_per_fill_launch(p, slot, (hipStream_t)stream); });
+}
+extern "C" int rs_dqn_per_commit(rs_dqn_handle p, const rs_dqn_ring *ring, const int32_t *idx, int32_t batch, void *stream) {
+    const char *name = "rs_dqn_per_commit";
+    if (p && !p->per_on) return per_refuse(name, "priorities are off (rs_dqn_set_priorities)");
+    if (int rc = dqn_check(p, ring, batch, name)) return rc;
+    if (int rc = dqn_check_idx(p, idx, "idx", name)) return rc;
+    if (p->ad_batch != batch) return per_refuse(name, "no preceding rs_dqn_grad of this batch size with priorities on: there is no |delta| to commit");
+    return on_device(p->device, [&] { dqn_per_commit_launch(p, dqn_batch(ring, idx, batch), (hipStream_t)stream); });
+}
 
 extern "C" int rs_mplight_dqn_sample(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, int32_t batch, uint32_t seed, uint32_t update_key,
                                      int32_t *idx_out, void *stream) {
@@ -2240,6 +2343,9 @@ template <class H, class Ring> static int group_train(const rs_handle *hs, int32
             row0 += (size_t)h->n_envs;
         }
         // the learner's observe_step on the legacy stream: it waits for every pipe, and the pipes' next launches wait for it
+        bool filled = false;
+        if constexpr (idqn)         // prioritised replay: the step's slot enters at the maximum priority before anything draws from it
+            if (lq->per_on) { dqn_per_fill_launch(lq, P.slot, hipStreamLegacy); filled = true; }
         if (P.sync) dqn_sync_launch(lq, hipStreamLegacy);
         if (P.update) {
             const Ring r = ring_at(P.head, P.count);
@@ -2247,7 +2353,7 @@ template <class H, class Ring> static int group_train(const rs_handle *hs, int32
             if constexpr (idqn)
                 idqn_pack_launch(pol, lq->T.par.p[PT_FC1_W], lq->T.par.p[PT_FC2_W], lq->T.par.p[PT_FC3_W], lq->T.par.p[PT_FC3_B], hipStreamLegacy);
         }
-        if (P.sync || P.update) HIPCHK(h0, hipGetLastError());
+        if (P.sync || P.update || filled) HIPCHK(h0, hipGetLastError());
     }
     return RS_OK;
 }

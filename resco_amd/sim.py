@@ -37,6 +37,7 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_ppo_create', 'rs_ppo_grad', 'rs_ppo_step', 'rs_ppo_fit', 'rs_ppo_steps', 'rs_ppo_set_steps', 'rs_ppo_destroy',
                'rs_dqn_create', 'rs_dqn_sample', 'rs_dqn_grad', 'rs_dqn_step', 'rs_dqn_update', 'rs_dqn_steps', 'rs_dqn_set_steps',
                'rs_dqn_set_target', 'rs_dqn_get_target', 'rs_dqn_destroy',
+               'rs_dqn_set_priorities', 'rs_dqn_get_priorities', 'rs_dqn_per_rebuild', 'rs_dqn_per_fill', 'rs_dqn_per_commit',
                'rs_mplight_dqn_create', 'rs_mplight_dqn_sample', 'rs_mplight_dqn_grad', 'rs_mplight_dqn_step', 'rs_mplight_dqn_update',
                'rs_mplight_dqn_steps', 'rs_mplight_dqn_set_steps', 'rs_mplight_dqn_set_target', 'rs_mplight_dqn_get_target', 'rs_mplight_dqn_destroy',
                'rs_mplight_multi_create', 'rs_mplight_multi_sample', 'rs_mplight_multi_grad', 'rs_mplight_multi_step', 'rs_mplight_multi_update',
@@ -132,6 +133,12 @@ def bind(L):
         if hasattr(L, 'rs_dqn_set_target'):     # (a host emulation may not have them)
             L.rs_dqn_set_target.argtypes = [vp, i32, i32]
             L.rs_dqn_get_target.argtypes = [vp, vp, vp]
+        if hasattr(L, 'rs_dqn_set_priorities'):     # (a host emulation may not have them)
+            L.rs_dqn_set_priorities.argtypes = [vp, vp]
+            L.rs_dqn_get_priorities.argtypes = [vp, vp, vp]
+            L.rs_dqn_per_rebuild.argtypes = [vp, vp]
+            L.rs_dqn_per_fill.argtypes = [vp, i32, vp]
+            L.rs_dqn_per_commit.argtypes = [vp, vp, vp, i32, vp]
         L.rs_dqn_destroy.argtypes = [vp]
         L.rs_dqn_destroy.restype = None
     if hasattr(L, 'rs_mplight_dqn_create'):
@@ -297,6 +304,12 @@ class DQNConfig(C.Structure):
 class DQNRing(C.Structure):
     """ctypes mirror of rs_dqn_ring (include/resco_sim.h): the device arrays of a DeviceReplay and its position"""
     _fields_ = [(k, C.c_void_p) for k in ('obs', 'act', 'rew', 'done')] + [(k, C.c_int32) for k in ('capacity', 'n_envs', 'head', 'count')]
+
+
+class DQNPer(C.Structure):
+    """ctypes mirror of rs_dqn_per (include/resco_sim.h): the device arrays of the priorities and the options of prioritised replay"""
+    _fields_ = [(k, C.c_void_p) for k in ('prio', 'ssum', 'pmax')] + [(k, C.c_int32) for k in ('capacity', 'n_envs')] + \
+               [(k, C.c_double) for k in ('alpha', 'beta0', 'eps')] + [('beta_steps', C.c_int64)]
 
 
 class MPLightRing(C.Structure):

@@ -2,7 +2,7 @@
 """IDQN training loop entirely on the GPU: HIP simulator -> fp16 observations -> fused HIP policy kernel
 (rs_idqn_act) -> device replay ring -> batched DQN update (PyTorch, or HIP with --device-update) -> weights re-packed on the device.  Nothing crosses PCIe per step except the launch calls.
 
-    python tools/idqn_train.py [--n-step K] [--double-q] [--device-update | --device-loop] [map] [n_envs] [episodes] [batch] [updates_per_step] [graph|nograph] [replay_steps] [eps_end] [seed]
+    python tools/idqn_train.py [--n-step K] [--double-q] [--per [alpha,beta0,beta_steps]] [--device-update | --device-loop] [map] [n_envs] [episodes] [batch] [updates_per_step] [graph|nograph] [replay_steps] [eps_end] [seed]
 
 --device-update: the update itself in HIP kernels as well (FusedDQNLearner, rs_dqn_update: sampling, target, backward and Adam of all
 updates of a step in one call; no HIP graph is captured).  --device-loop (implies --device-update): the loop itself in the library
@@ -10,6 +10,13 @@ as well (agents/train_fused.py: DeviceTrainer, rs_group_train), one call per epi
 
 --n-step K (1 .. 32) and --double-q, in every mode: n-step returns (truncated at the newest slot of the ring, cut at an episode end) and
 Double DQN's bootstrap; both are part of a checkpoint's signature.  Without them: PFRL's plain one-step DQN.
+
+--per [alpha,beta0,beta_steps] (with --device-update or --device-loop only): prioritised experience replay in the fused update -- the
+minibatches are drawn by priority (|TD error| + 1e-6)^alpha, the loss carries importance weights whose exponent goes from beta0 to 1
+over beta_steps updates (0: constant).  Without a value: 0.6,0.4 and the run's planned number of updates.  Part of a checkpoint's
+signature; the priorities are saved with the ring (--save-replay) and start again without it.  The default beta_steps follows the
+planned episodes, which are part of the signature themselves (a --load with another total is refused either way): give beta_steps
+explicitly to pin the schedule to something else than the run's length.
 
 Prints one JSON line per episode (mean episode return of rewards.wait_norm per signal, average trip delay as
 utils/readXML.py computes it, epsilon, env-steps/s including learning) and a final line comparing with the
@@ -58,18 +65,25 @@ def greedy_evaluation(env, policy, actions, steps, seeds):
 
 
 def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_graph=True, replay_steps=0, eps_end=0.0, evaluate=True, quiet=False, seed=0, tls_expiry=True,
-         device_update=False, device_loop=False, chunk=0, save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, n_step=1, double_q=False):
-    """n_step / double_q: the learners' options of the same names.  device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
+         device_update=False, device_loop=False, chunk=0, save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, n_step=1, double_q=False, per=None):
+    """n_step / double_q: the learners' options of the same names.  per: None, True (the defaults) or (alpha, beta0[, beta_steps]):
+    prioritised replay, with the fused learner only.  device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
     save / save_freq / save_replay / load / eval_only / stop_after: the checkpoint flags of the module docstring; a run that leaves
     at stop_after returns (rows, None)."""
     device_update = device_update or device_loop
+    if per is not None and per is not False and not device_update:
+        raise SystemExit('--per needs --device-update or --device-loop: prioritised replay is built into the fused update only')
     rows = []
     env = VecMultiSignal(map_name, n, states=('drq_norm_f16',), rewards=('wait_norm',), seed=0, tls_expiry=tls_expiry)
     S, steps = env.n_signals, env.horizon_steps
     net = BatchedIDQN.from_scenario(env.scenario, dtype=torch.float32, device='cuda')
     net.init_like_reference(seed=seed)
     if device_update:
-        learner = FusedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed, n_step=n_step, double_q=double_q)
+        if per is True:
+            per = (0.6, 0.4)
+        if per:             # beta reaches 1 with the last planned update unless told otherwise
+            per = dict(alpha=per[0], beta0=per[1], beta_steps=int(per[2]) if len(per) > 2 else episodes * steps * updates)
+        learner = FusedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed, n_step=n_step, double_q=double_q, per=per or None)
         use_graph = False                               # one call enqueues the update's few launches: nothing to capture
     else:
         learner = BatchedDQNLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, n_step=n_step, double_q=double_q)
@@ -79,6 +93,8 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
     # `replay_steps` env-steps over all N environments (0: the last four episodes -- a small ring forgets exploratory data within
     # four episodes of epsilon reaching 0)
     replay = DeviceReplay(replay_steps if replay_steps > 0 else min(2048, 4 * steps), n, S, net.lmax, device='cuda')
+    if device_update:
+        learner.attach(replay)                          # (the priorities, if any, are sized from the ring: before a checkpoint is loaded)
     gen = torch.Generator(device='cuda').manual_seed(seed)
     decay = int(0.8 * episodes * steps)                 # the reference decays over config['steps'] agent steps
     trainer = DeviceTrainer(env, learner, policy, replay, 1.0, eps_end, decay, updates) if device_loop else None
@@ -159,10 +175,28 @@ def main(map_name='cologne1', n=256, episodes=12, batch=256, updates=1, use_grap
     return rows, final
 
 
+def _per_value(text):
+    """'alpha,beta0[,beta_steps]' -> the tuple, or None where the text is not one (it is then the next positional argument)"""
+    parts = text.split(',')
+    try:
+        v = (float(parts[0]), float(parts[1])) + ((int(parts[2]),) if len(parts) > 2 else ())
+    except (ValueError, IndexError):
+        return None
+    return v if len(parts) in (2, 3) else None
+
+
 def target_flags(argv):
-    """--n-step K and --double-q taken out of an argument list -> (keyword arguments for main(), the remaining arguments)"""
+    """--n-step K, --double-q and --per [alpha,beta0[,beta_steps]] taken out of an argument list -> (keyword arguments for main(), the
+    remaining arguments)"""
     kw, rest, i = {}, [], 0
     while i < len(argv):
+        if argv[i] == '--per':
+            v = _per_value(argv[i + 1]) if i + 1 < len(argv) else None
+            kw['per'] = True if v is None else v
+            if v is not None and not (0.0 <= v[0] <= 1.0 and 0.0 <= v[1] <= 1.0 and (len(v) < 3 or v[2] >= 0)):
+                raise SystemExit('--per: alpha and beta0 in [0, 1], beta_steps >= 0')
+            i += 1 if v is None else 2
+            continue
         if argv[i] == '--n-step':
             if i + 1 >= len(argv):
                 raise SystemExit('--n-step needs a value')
@@ -186,6 +220,8 @@ if __name__ == '__main__':
     loop = a[:1] == ['--device-loop']
     dev = loop or a[:1] == ['--device-update']
     a = a[1:] if dev else a
+    if 'per' in ckpt and not dev:
+        raise SystemExit('--per needs --device-update or --device-loop: prioritised replay is built into the fused update only')
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 12,
          int(a[3]) if len(a) > 3 else 256, int(a[4]) if len(a) > 4 else 1, (a[5] != 'nograph') if len(a) > 5 else True,
          int(a[6]) if len(a) > 6 else 0, float(a[7]) if len(a) > 7 else 0.0, seed=int(a[8]) if len(a) > 8 else 0, device_update=dev, device_loop=loop, **ckpt)
