@@ -635,6 +635,59 @@ int rs_mplight_dqn_set_target(rs_mplight_dqn_handle p, int32_t n_step, int32_t d
 int rs_mplight_dqn_get_target(rs_mplight_dqn_handle p, int32_t *n_step, int32_t *double_q);
 void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p);
 
+/* ---- MPLight: prioritised experience replay in that update (resco_amd/csrc/resco_frap_per.h) ------------------------------
+ * Off on a new handle; while off exactly the launches described above run and nothing new is allocated.  MPLight draws from ONE pooled
+ * population of rows (t, e, s), so the sums run over three axes.  The state is the caller's and borrowed, like params:
+ *   prio f32 [capacity][n_envs][n_signals] (the layout of rew): a leaf q = (|delta| + eps)^alpha >= 0, already exponentiated;
+ *   esum f32 [capacity][n_envs]: the total of the n_signals leaves of (t, e);  ssum f32 [capacity]: the total of the n_envs values
+ *   esum[t][.];  pmax f32 [1]: the largest q ever written (start: 1), raised by an integer max on the bit pattern.
+ * The order of every sum is the one resco_dqn_per.h defines: the terms in chunks of 64, inside a chunk the inclusive Hillis-Steele scan
+ * (steps 1, 2, 4 .. 32: position l adds the value of position l - d), cumulative values = carry + scan, carry = the cumulative value of
+ * position 63, starting at 0; the total is the last carry.  esum is ALWAYS this total of its leaves as they stand and ssum this total of
+ * its esum values as they stand, re-summed, never adjusted by a difference.  No float atomics: the same state gives the same bits.
+ * rs_mplight_dqn_set_priorities: the host-side fields alone, like rs_mplight_dqn_set_target (no launch; what is enqueued afterwards
+ * sees them); NULL: off.  capacity, n_envs and n_signals are those of the ring the state belongs to; alpha and beta0 in [0, 1],
+ * eps > 0, beta_steps >= 0.  The first call that turns priorities on allocates the workspace (8 bytes per row of max_batch).
+ * rs_mplight_dqn_get_priorities: the struct as it stands (untouched while off) and whether it is on.
+ * rs_mplight_dqn_per_rebuild: every esum from prio, then every ssum from esum (at the start, after a checkpoint load); bit for bit
+ * what fill and commit leave.
+ * rs_mplight_dqn_per_fill: prio[slot][.][.] = pmax, esum[slot][e] = the total of n_signals copies of pmax, ssum[slot] = the total of
+ * n_envs copies of that value: a new transition enters at the maximum priority.  The newest slot, which has no successor yet, is filled
+ * like any other: the draw leaves it out by position, not by value.
+ * rs_mplight_dqn_per_commit: for the rows idx of the LAST rs_mplight_dqn_grad (same batch): prio <- powf(|delta| + eps, alpha) with the
+ * |delta| that call left in the workspace (an infinite value becomes 0), pmax raised, then esum of every touched (t, e) and then ssum
+ * of every touched t re-summed.
+ * With priorities on:
+ *   rs_mplight_dqn_sample draws by priority.  The valid slots are k = 0 .. count - 2 from the oldest, head - count.  For draw i of
+ *   update u: r_j = (hash(seed ^ 0x7B1D5C33, u, i, 1, j) >> 8) 2^-24, j = 0, 1, 2 (the uniform draw's fourth argument is 0).  With Z
+ *   the total of the valid ssum, the slot is the first valid k of positive weight whose inclusive cumulative ssum exceeds r_0 Z; the
+ *   environment the first e of positive weight whose inclusive cumulative esum[t][.] exceeds r_1 ssum[t]; the signal the first s of
+ *   positive weight whose inclusive cumulative prio[t][e][.] exceeds r_2 esum[t][e]; where rounding lets the value fall past the end,
+ *   the last entry of positive weight.  An entry of weight 0 is never drawn (nothing positive at all: entry 0).  idx_out as without.
+ *   rs_mplight_dqn_grad weights the loss: w_i = (M q_i / Z)^-beta / max_j (M q_j / Z)^-beta, M = (count - 1) n_envs n_signals, the max
+ *   over the whole minibatch, q and Z as they stand when the gradient is taken (a row of priority 0, which no draw gives, has weight
+ *   0); row i contributes (double) w_i Huber(delta_i) to the loss and (double) w_i clamp(delta_i, -1, 1) / batch to dy.  beta =
+ *   min(1, beta0 + (1 - beta0) u / beta_steps) with u the step count so far, in double, rounded once; beta_steps 0: beta0.  The target
+ *   is rs_mplight_dqn_set_target's.  |delta| is evaluated in double and rounded once to fp32.
+ *   rs_mplight_dqn_update is sample, grad, step, commit per update.  rs_group_train (MPLight) fills each step's slot on the learner's
+ *   stream after the pipes' recorders, before the target sync and the update.
+ * Refusals (RS_EINVAL, a text, nothing launched, the handle unchanged): a NULL handle; a NULL array or one that is not memory of the
+ * handle's device; capacity < 2, n_envs < 1 or n_signals not the handle's; alpha or beta0 outside [0, 1]; eps <= 0; beta_steps < 0; a
+ * ring whose capacity, n_envs or n_signals differ from the state's, at any call that takes a ring; slot outside the ring; rebuild, fill
+ * or commit while off; a commit whose batch is not that of the last rs_mplight_dqn_grad with priorities on (or without one since
+ * rs_mplight_dqn_set_priorities).  The multi-map learner (rs_mplight_multi_*) has no priorities. */
+typedef struct rs_mplight_per {
+    float *prio, *esum, *ssum, *pmax;
+    int32_t capacity, n_envs, n_signals;
+    double alpha, beta0, eps;
+    int64_t beta_steps;
+} rs_mplight_per;
+int rs_mplight_dqn_set_priorities(rs_mplight_dqn_handle p, const rs_mplight_per *per);
+int rs_mplight_dqn_get_priorities(rs_mplight_dqn_handle p, rs_mplight_per *out, int32_t *on);
+int rs_mplight_dqn_per_rebuild(rs_mplight_dqn_handle p, void *stream);
+int rs_mplight_dqn_per_fill(rs_mplight_dqn_handle p, int32_t slot, void *stream);
+int rs_mplight_dqn_per_commit(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, const int32_t *idx, int32_t batch, void *stream);
+
 /* ---- MPLight on several maps: ONE shared FRAP trained on M replay rings at once (resco_amd/csrc/resco_frap_multi.h) ------------
  * FRAP's parameter vector (1365 + 4 D floats) does not depend on a map's signal count or its number of phase pairs: it sees a map
  * only through pairs [n_pairs][2] and a row's 12 movement demands.  rs_mplight_multi_* is rs_mplight_dqn_* over n_maps = 1 .. 8 maps,

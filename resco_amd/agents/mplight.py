@@ -315,8 +315,12 @@ class MPLightReplay:
 class MPLightLearner:
     """PFRL's DQN update on the shared FRAP network (see the module docstring for the batching)."""
 
-    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, n_step=1, double_q=False):
-        """n_step (1 .. 32): n-step returns (idqn_learn.nstep_walk); double_q: Double DQN's bootstrap.  The defaults are PFRL's plain DQN."""
+    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, n_step=1, double_q=False, per=None):
+        """n_step (1 .. 32): n-step returns (idqn_learn.nstep_walk); double_q: Double DQN's bootstrap.  The defaults are PFRL's plain DQN.
+        per: refused -- prioritised replay exists in the fused learner only."""
+        if per is not None:
+            raise ValueError('MPLightLearner: prioritised replay is implemented in the device update only '
+                             '(FusedMPLightLearner(per=...), tools/mplight_train.py --device-update or --device-loop)')
         self.n_step, self.double_q = int(n_step), bool(double_q)
         if not 1 <= self.n_step <= 32:
             raise ValueError('MPLightLearner: n_step must be in 1 .. 32, got %d' % self.n_step)

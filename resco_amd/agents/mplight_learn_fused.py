@@ -13,14 +13,19 @@ owns only its workspace and the step counter (the handle's life cycle, .n_update
 The handle is created over the ring's signal count: at construction when `n_signals` is given, else at the first call that sees a
 ring.  The minibatches come from the library's counter hash, not from a torch generator: the distribution is MPLightReplay.sample's,
 the draws are not.  There is no CPU fallback.
+
+`per=dict(alpha, beta0, beta_steps, eps)` turns prioritised experience replay on (rs_mplight_dqn_set_priorities;
+resco_amd/csrc/resco_frap_per.h): the draw is by priority over the pooled rows (slot, environment, signal), the loss carries the
+importance weights, and every update writes the rows' new priorities back.  The priorities (`.prio` [T, N, S], `.esum` [T, N], `.ssum`
+[T], `.pmax` [1]) are torch tensors this object owns, sized from the replay ring at first use (`attach`).
 """
 import ctypes as C
 
 import torch
 
-from ..sim import DQNConfig, MPLightRing, load_library, torch_stream
+from ..sim import DQNConfig, MPLightPer, MPLightRing, load_library, torch_stream
 from . import _state
-from .idqn_learn import target_options_signature
+from .idqn_learn import per_options, per_options_signature, target_options_signature
 from .learn_fused import FusedLearnerBase
 from .mplight import FRAP
 
@@ -37,14 +42,18 @@ def _views(flat, net):
 
 class FusedMPLightLearner(FusedLearnerBase):
     NAME, PREFIX = 'FusedMPLightLearner', 'rs_mplight_dqn'
+    STATE_FOLLOWS_REPLAY = True         # resco_amd/checkpoint.py: state_dict(replay=...) -- the priorities are saved with the ring only
 
-    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, seed=0, n_signals=None, n_step=1, double_q=False):
+    def __init__(self, net, gamma=0.99, lr=1e-3, target_update=500, batch_size=32, seed=0, n_signals=None, n_step=1, double_q=False, per=None):
         """n_step (1 .. 32): n-step returns, truncated at the newest slot of the ring and cut at an episode end; double_q: the
         bootstrap is the target network's value of the online network's best of ALL P outputs (rs_mplight_dqn_set_target has the
-        definition).  The defaults are PFRL's plain one-step DQN."""
+        definition).  per: None, or the options of prioritised replay, any of dict(alpha=0.6, beta0=0.4, beta_steps=0, eps=1e-6)
+        (rs_mplight_dqn_set_priorities has the definition).  The defaults are PFRL's plain one-step DQN with uniform replay."""
         assert isinstance(net, FRAP)
         super().__init__(net)
         self._take_target_options(n_step, double_q)
+        self.per = per_options(per, self.NAME)
+        self.prio = self.esum = self.ssum = self.pmax = None
         self.gamma, self.lr, self.adam_eps = float(gamma), float(lr), 1e-8
         self.batch_size, self.target_update, self.seed = int(batch_size), int(target_update), int(seed) & 0xFFFFFFFF
         self.t = 0              # env-steps seen
@@ -109,7 +118,58 @@ class FusedMPLightLearner(FusedLearnerBase):
         ring = MPLightRing(replay.obs.data_ptr(), replay.act.data_ptr(), replay.rew.data_ptr(), replay.done.data_ptr(), replay.T, replay.N, replay.S, W,
                            replay.head, replay.count)
         self._keep = (replay, ring)
+        if self.per is not None:
+            self.attach(replay)
         return ring
+
+    # ---- prioritised replay
+    def attach(self, replay):
+        """The priorities of `replay`, at first use: every leaf at pmax = 1, the sums rebuilt; the handle borrows the four tensors.
+        Every call that takes the replay comes through here; call it yourself before a checkpoint is loaded into a learner that
+        has not seen its replay yet."""
+        if self.per is None:
+            return
+        if self.prio is not None:
+            if tuple(self.prio.shape) != (replay.T, replay.N, replay.S):
+                raise ValueError('FusedMPLightLearner: the priorities were sized for a ring of %s, not %s' % (tuple(self.prio.shape), (replay.T, replay.N, replay.S)))
+            return
+        if self._h is None:
+            self._create(replay.S)
+        if not hasattr(self._lib, 'rs_mplight_dqn_set_priorities'):
+            raise RuntimeError('the loaded library has no rs_mplight_dqn_set_priorities: rebuild it (there is no CPU fallback)')
+        T, N, S = replay.T, replay.N, replay.S
+        self.prio = torch.ones(T, N, S, dtype=torch.float32, device=self.device)
+        self.esum = torch.zeros(T, N, dtype=torch.float32, device=self.device)
+        self.ssum = torch.zeros(T, dtype=torch.float32, device=self.device)
+        self.pmax = torch.ones(1, dtype=torch.float32, device=self.device)
+        o = self.per
+        per = MPLightPer(self.prio.data_ptr(), self.esum.data_ptr(), self.ssum.data_ptr(), self.pmax.data_ptr(), T, N, S, o['alpha'], o['beta0'], o['eps'],
+                         o['beta_steps'])
+        rc = self._lib.rs_mplight_dqn_set_priorities(self._h, C.byref(per))
+        if rc != 0:
+            self.prio = self.esum = self.ssum = self.pmax = None
+            self._fail('rs_mplight_dqn_set_priorities', rc)
+        self.per_rebuild()
+
+    def _per_call(self, name, *args):
+        rc = getattr(self._lib, name)(self._h, *args, torch_stream(self.device.index))
+        if rc != 0:
+            self._fail(name, rc)
+
+    def per_rebuild(self):
+        """esum <- the sums of prio, ssum <- the sums of esum (rs_mplight_dqn_per_rebuild)"""
+        self._per_call('rs_mplight_dqn_per_rebuild')
+
+    def per_fill(self, slot):
+        """the transitions of `slot` enter at the maximum priority (rs_mplight_dqn_per_fill)"""
+        self._per_call('rs_mplight_dqn_per_fill', int(slot))
+
+    def per_commit(self, replay, idx):
+        """the priorities of the rows idx of the last grad() <- their |delta| (rs_mplight_dqn_per_commit)"""
+        idx32 = idx.to(torch.int32).contiguous()
+        ring = self._ring(replay)
+        self._keep += (idx32,)
+        self._per_call('rs_mplight_dqn_per_commit', C.byref(ring), idx32.data_ptr(), idx32.shape[0])
 
     # ---- the pieces (what the tests compare one by one) and the update
     def sample(self, replay, batch_size=None, update_key=None):
@@ -139,7 +199,7 @@ class FusedMPLightLearner(FusedLearnerBase):
         return self.grads
 
     def update(self, replay, updates=1):
-        """`updates` times [sample -> gradient -> Adam step], enqueued by one call.  Returns .loss_out (the last update's)."""
+        """`updates` times [sample -> gradient -> Adam step (-> commit of the priorities)], enqueued by one call.  Returns .loss_out (the last update's)."""
         ring = self._ring(replay)
         rc = self._lib.rs_mplight_dqn_update(self._h, C.byref(ring), self.batch_size, self.seed, int(updates), self.loss_out.data_ptr(),
                                              torch_stream(self.device.index))
@@ -155,12 +215,22 @@ class FusedMPLightLearner(FusedLearnerBase):
     # ---- checkpoints (resco_amd/checkpoint.py): the four flat vectors are loaded in place -- the library has borrowed them, the
     # parameters of net and target are views of them and a policy may share .flat --; the step count goes back through
     # rs_mplight_dqn_set_steps, so the handle has to exist (pass n_signals, or show the learner its ring first)
-    def signature(self):
-        return target_options_signature({'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}, self.n_step, self.double_q)
+    _ATTACH_FIRST = ('FusedMPLightLearner: the priorities are sized from the replay ring at first use: call attach(replay) before '
+                     'a checkpoint with the ring is written or loaded')
 
-    def state_dict(self):
-        return {'weights': {'flat': self.flat, 'flat_target': self.flat_target},
-                'state': {'m': self._m, 'v': self._v, 't': int(self.t), 'steps': _state.fused_counter_state(self), 'seed': int(self.seed)}}
+    def signature(self):
+        fields = target_options_signature({'batch': self.batch_size, 'target_update': self.target_update, 'gamma': self.gamma}, self.n_step, self.double_q)
+        return per_options_signature(fields, self.per)
+
+    def state_dict(self, replay=True):
+        """replay: the checkpoint holds the ring, and with it prio and pmax (the sums are rebuilt from them on load)"""
+        sd = {'weights': {'flat': self.flat, 'flat_target': self.flat_target},
+              'state': {'m': self._m, 'v': self._v, 't': int(self.t), 'steps': _state.fused_counter_state(self), 'seed': int(self.seed)}}
+        if self.per is not None and replay:
+            if self.prio is None:
+                raise RuntimeError(self._ATTACH_FIRST)
+            sd['state']['per'] = {'prio': self.prio, 'pmax': self.pmax}
+        return sd
 
     def load_state_dict(self, sd, weights_only=False):
         _state.copy_into(self.flat, sd['weights']['flat'], 'FusedMPLightLearner.flat')
@@ -171,12 +241,27 @@ class FusedMPLightLearner(FusedLearnerBase):
             _state.copy_into(self._v, st['v'], 'FusedMPLightLearner.v')
             _state.set_fused_counter(self, st['steps'], 'FusedMPLightLearner')
             self.t, self.seed = int(st['t']), int(st['seed']) & 0xFFFFFFFF
+            if self.per is not None and 'per' in st:
+                if self.prio is None:
+                    raise RuntimeError(self._ATTACH_FIRST)
+                _state.copy_into(self.prio, st['per']['prio'], 'FusedMPLightLearner.prio')
+                _state.copy_into(self.pmax, st['per']['pmax'], 'FusedMPLightLearner.pmax')
+                self.per_rebuild()
+            elif self.per is not None:
+                print('FusedMPLightLearner: the checkpoint holds no replay ring, so the priorities start again (every transition at priority 1)')
+                if self.prio is not None:
+                    self.prio.fill_(1.0)
+                    self.pmax.fill_(1.0)
+                    self.per_rebuild()
 
     def observe_step(self, replay, generator=None):
         """One env-step in MPLightLearner.observe_step's order: count it, copy the target every ``target_update`` env-steps, then one
         update once the ring holds a minibatch.  `generator` is ignored: the minibatches are drawn by the library's counter hash from
         (seed, Adam steps so far).  Returns .loss_out after an update, else None."""
         self.t += 1
+        if self.per is not None:
+            self.attach(replay)
+            self.per_fill((replay.head - 1) % replay.T)     # the slot just committed enters at the maximum priority
         if self.t % self.target_update == 0:
             self.sync_target()
         if len(replay) >= self.batch_size:

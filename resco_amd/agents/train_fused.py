@@ -45,7 +45,8 @@ class DeviceTrainer:
             if int(updates_per_step) != 1:
                 raise ValueError('MPLight runs one update per env-step (FusedMPLightLearner.observe_step)')
             self.agent, self.updates_per_step = 'mplight', 1
-            learner._ring(replay)               # (creates the handle over the ring's signal count if it has none yet)
+            learner._ring(replay)               # (creates the handle over the ring's signal count if it has none yet; prioritised
+                                                #  replay: attaches the priorities, sized from this ring)
         else:
             raise TypeError('DeviceTrainer needs a FusedDQNLearner or a FusedMPLightLearner: the loop runs in the library (there is no CPU fallback)')
         if sum(e.n_envs for e in self.envs) != replay.N:

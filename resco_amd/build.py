@@ -30,7 +30,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fn
          '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(HERE, 'csrc'), '-I' + GEN_DIR]
 _HDRS = [os.path.join(HERE, 'csrc', f) for f in ('resco_host.h', 'resco_step.h', 'resco_tables.h')] + \
         [os.path.join(ROOT, 'include', f) for f in ('resco_sim.h', 'resco_model.h')]
-_DEPS = [SRC] + _HDRS + [os.path.join(HERE, 'csrc', f) for f in ('resco_policy.h', 'resco_frap.h', 'resco_fma2c.h', 'resco_fma2c_train.h', 'resco_ppo.h', 'resco_train.h', 'resco_ppo_train.h', 'resco_dqn_train.h', 'resco_dqn_per.h', 'resco_frap_train.h', 'resco_frap_multi.h', 'resco_group_train.h', 'resco_ppo_loop.h', 'resco_fma2c_loop.h')]
+_DEPS = [SRC] + _HDRS + [os.path.join(HERE, 'csrc', f) for f in ('resco_policy.h', 'resco_frap.h', 'resco_fma2c.h', 'resco_fma2c_train.h', 'resco_ppo.h', 'resco_train.h', 'resco_ppo_train.h', 'resco_dqn_train.h', 'resco_dqn_per.h', 'resco_frap_train.h', 'resco_frap_per.h', 'resco_frap_multi.h', 'resco_group_train.h', 'resco_ppo_loop.h', 'resco_fma2c_loop.h')]
 
 
 def _newer(target, deps):

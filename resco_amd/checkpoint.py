@@ -65,7 +65,7 @@ def _state_of(obj, replay):
     if not hasattr(obj, 'state_dict'):
         raise TypeError('%s has no state_dict(): it cannot be part of a checkpoint' % type(obj).__name__)
     fields = dict(obj.signature()) if hasattr(obj, 'signature') else {}
-    # a ring, or a learner whose state beside the ring is saved with it only (FusedDQNLearner's priorities)
+    # a ring, or a learner whose state beside the ring is saved with it only (the priorities of FusedDQNLearner and FusedMPLightLearner)
     with_replay = (hasattr(obj, 'head') and hasattr(obj, 'count')) or getattr(obj, 'STATE_FOLLOWS_REPLAY', False)
     return fields, (obj.state_dict(replay=replay) if with_replay else obj.state_dict())
 

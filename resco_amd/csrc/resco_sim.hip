@@ -118,6 +118,7 @@ __device__ unsigned long long *g_sec_prof;
 #include "resco_dqn_train.h"
 #include "resco_dqn_per.h"
 #include "resco_frap_train.h"
+#include "resco_frap_per.h"
 #include "resco_frap_multi.h"
 #include "resco_group_train.h"
 #include "resco_ppo_loop.h"
@@ -1659,6 +1660,11 @@ struct rs_mplight_dqn : DqnHandle {
     static constexpr const char *kCreate = "rs_mplight_dqn_create";
     FrapTrainTab T{};
     int n_step = 1, double_q = 0;       // rs_mplight_dqn_set_target: host-side, read when a gradient is enqueued
+    // prioritised replay (resco_frap_per.h).  rs_mplight_dqn_set_priorities: host-side, read when a launch is enqueued
+    rs_mplight_per per{};
+    int per_on = 0;
+    int ad_batch = 0;                   // the batch of the last gradient taken with priorities on: its |delta| stands in per_ad (0: none)
+    float *per_z = nullptr, *per_w = nullptr, *per_ad = nullptr;    // Z [1]; the rows' weights and |delta| [max_batch]: allocated at first use
 };
 
 extern "C" void rs_mplight_dqn_destroy(rs_mplight_dqn_handle p) { train_destroy(p); }
@@ -1705,21 +1711,49 @@ extern "C" int rs_mplight_dqn_create(int32_t device_id, int32_t demand_shape, in
 static const char *dqn_ring_refusal(const rs_mplight_dqn *p, const rs_mplight_ring *r) {
     if (r->n_signals != p->T.S) return "the ring's n_signals is not the handle's";
     if (r->width != 1 + FRAP_MV * p->T.D) return "the ring's width is not the handle's 1 + 12 demand_shape";
+    if (p->per_on && (r->capacity != p->per.capacity || r->n_envs != p->per.n_envs || r->n_signals != p->per.n_signals))
+        return "the priorities of rs_mplight_dqn_set_priorities belong to a ring of another capacity, n_envs or n_signals";
     return nullptr;
 }
-static FrapBatch dqn_batch(const rs_mplight_ring *r, const int32_t *idx, int32_t B) {
-    return FrapBatch{r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, r->n_signals, r->width, idx, B, r->head};
+// the minibatch the kernels take, and on the host the ring's count beside it (the prioritised weights' M and Z)
+struct FrapBatchAt : FrapBatch { int32_t count; };
+static FrapBatchAt dqn_batch(const rs_mplight_ring *r, const int32_t *idx, int32_t B) {
+    return FrapBatchAt{FrapBatch{r->obs, r->act, r->rew, r->done, r->capacity, r->n_envs, r->n_signals, r->width, idx, B, r->head}, r->count};
 }
 
 // the launches; the arguments have been checked
-static void dqn_sample_launch(const rs_mplight_dqn *, const rs_mplight_ring *r, int B, uint32_t seed, uint32_t key, int32_t *idx, hipStream_t st) {
+// the table of the prioritised-replay kernels as the handle stands: beta from the steps taken so far
+static FrapPer frap_per_tab(const rs_mplight_dqn *p) {
+    const rs_mplight_per &q = p->per;
+    return FrapPer{q.prio, q.esum, q.ssum, q.pmax, p->per_z, p->per_w, p->per_ad, q.capacity, q.n_envs, q.n_signals, (float)q.alpha, (float)q.eps,
+                   dqn_per_beta(q.beta0, q.beta_steps, p->t)};
+}
+static void dqn_sample_launch(const rs_mplight_dqn *p, const rs_mplight_ring *r, int B, uint32_t seed, uint32_t key, int32_t *idx, hipStream_t st) {
+    if (p->per_on) {
+        const FrapPer P = frap_per_tab(p);
+        hipLaunchKernelGGL(frap_per_z_kernel, dim3(1), dim3(PPT_T), 0, st, P, r->head, r->count);
+        hipLaunchKernelGGL(frap_per_sample_kernel, dim3(per_grid(B)), dim3(PPT_T), 0, st, P, seed, key, r->head, r->count, B, idx);
+        return;
+    }
     hipLaunchKernelGGL(frap_dqn_sample_kernel, dim3((B + 255) / 256), dim3(256), 0, st, seed, key, r->capacity, r->n_envs, r->n_signals, r->head, r->count, B,
                        idx);
 }
-static void dqn_grad_launch(const rs_mplight_dqn *p, const FrapBatch &D, float *loss_out, hipStream_t st) {
+static void dqn_grad_launch(rs_mplight_dqn *p, const FrapBatchAt &At, float *loss_out, hipStream_t st) {
+    const FrapBatch &D = At;
     const FrapTrainTab &T = p->T;
     const dim3 tiles((D.B + FPT_TM - 1) / FPT_TM);
-    if (p->n_step == 1 && !p->double_q)         // the options off: the plain one-step target, its own kernel
+    if (p->per_on) {            // the weighted variant of whichever tile kernel the options select
+        const FrapPer P = frap_per_tab(p);
+        hipLaunchKernelGGL(frap_per_z_kernel, dim3(1), dim3(PPT_T), 0, st, P, D.head, At.count);
+        hipLaunchKernelGGL(frap_per_weight_kernel, dim3(1), dim3(PPT_T), 0, st, P, D.idx, D.B, At.count);
+        p->ad_batch = D.B;
+        if (p->n_step == 1 && !p->double_q)
+            hipLaunchKernelGGL(frap_per_tile_kernel, tiles, dim3(FPT_T), 0, st, T, D, (const float *)P.w, P.ad);
+        else if (p->double_q)
+            hipLaunchKernelGGL(frap_per_tile_opt_kernel<true>, tiles, dim3(FPT_T), 0, st, T, D, p->n_step, (const float *)P.w, P.ad);
+        else
+            hipLaunchKernelGGL(frap_per_tile_opt_kernel<false>, tiles, dim3(FPT_T), 0, st, T, D, p->n_step, (const float *)P.w, P.ad);
+    } else if (p->n_step == 1 && !p->double_q)         // the options off: the plain one-step target, its own kernel
         hipLaunchKernelGGL(frap_dqn_tile_kernel, tiles, dim3(FPT_T), 0, st, T, D);
     else if (p->double_q)
         hipLaunchKernelGGL(frap_dqn_tile_opt_kernel<true>, tiles, dim3(FPT_T), 0, st, T, D, p->n_step);
@@ -1734,6 +1768,21 @@ template <class H> static void frap_step_launch(H *p, hipStream_t st) {
     if (hipPeekAtLastError() == hipSuccess) p->t += 1;      // a step that could not be launched is not counted
 }
 static void dqn_step_launch(rs_mplight_dqn *p, hipStream_t st) { frap_step_launch(p, st); }
+// the priorities of the rows idx of the last gradient (rs_mplight_dqn_per_commit; the last launches of an update with priorities on)
+static void frap_per_commit_launch(const rs_mplight_dqn *p, const int32_t *idx, int B, hipStream_t st) {
+    const FrapPer P = frap_per_tab(p);
+    hipLaunchKernelGGL(frap_per_leaf_kernel, dim3((B + PPT_T - 1) / PPT_T), dim3(PPT_T), 0, st, P, idx, B);
+    hipLaunchKernelGGL(frap_per_esum_kernel, dim3(per_grid(B)), dim3(PPT_T), 0, st, P, idx, B);
+    hipLaunchKernelGGL(frap_per_ssum_kernel, dim3(per_grid(B)), dim3(PPT_T), 0, st, P, idx, B);
+}
+static void frap_per_fill_launch(const rs_mplight_dqn *p, int slot, hipStream_t st) {
+    const FrapPer P = frap_per_tab(p);
+    const long long blocks = ((long long)P.N * P.S + PPT_T - 1) / PPT_T;
+    hipLaunchKernelGGL(frap_per_fill_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(PPT_T), 0, st, P, slot);
+}
+static void dqn_after_step_launch(rs_mplight_dqn *p, const rs_mplight_ring *, int batch, hipStream_t st) {
+    if (p->per_on) frap_per_commit_launch(p, p->idx, batch, st);
+}
 
 // target <- params (resco_group_train.h): one launch, the sources, destinations and element counts listed per learner
 static void sync_launch(const GtSync &Y, hipStream_t st) {
@@ -1785,8 +1834,7 @@ template <class H> static int dqn_check_idx(const H *p, const void *idx, const c
     g_create_err = std::string(name) + ": " + what + (idx ? " is not device memory of this handle's device" : " is NULL");
     return RS_EINVAL;
 }
-// what an update enqueues behind its Adam step: nothing, but for IDQN with priorities on (the overload on rs_dqn) their commit
-template <class H, class Ring> static void dqn_after_step_launch(H *, const Ring *, int, hipStream_t) {}
+// (what an update enqueues behind its Adam step, dqn_after_step_launch, is each learner's overload: with priorities on their commit)
 // n_updates x [sample -> gradient -> Adam step] (*_update, rs_group_train); the caller reads hipGetLastError
 template <class H, class Ring> static void dqn_update_launch(H *p, const Ring *ring, int batch, uint32_t seed, int n_updates, float *loss_out, hipStream_t st) {
     for (int j = 0; j < n_updates; ++j) {       // the launches of a stream run in order: update j + 1 may overwrite idx and the workspace
@@ -1919,6 +1967,62 @@ extern "C" int rs_mplight_dqn_set_target(rs_mplight_dqn_handle p, int32_t n_step
 }
 extern "C" int rs_mplight_dqn_get_target(rs_mplight_dqn_handle p, int32_t *n_step, int32_t *double_q) {
     return dqn_get_target("rs_mplight_dqn_get_target", p, n_step, double_q);
+}
+
+// ---- prioritised replay of the MPLight learner (resco_frap_per.h)
+extern "C" int rs_mplight_dqn_set_priorities(rs_mplight_dqn_handle p, const rs_mplight_per *per) {
+    const char *name = "rs_mplight_dqn_set_priorities";
+    if (!p) return per_refuse(name, "NULL handle");
+    if (!per) { p->per_on = 0; p->ad_batch = 0; return RS_OK; }
+    if (!per->prio || !per->esum || !per->ssum || !per->pmax) return per_refuse(name, "a priority array (prio, esum, ssum, pmax) is NULL");
+    if (per->capacity < 2 || per->n_envs < 1) return per_refuse(name, "need capacity >= 2 and n_envs >= 1");
+    if (per->n_signals != p->T.S) return per_refuse(name, "n_signals is not the handle's");
+    if (!(per->alpha >= 0.0 && per->alpha <= 1.0)) return per_refuse(name, "alpha must lie in [0, 1]");
+    if (!(per->beta0 >= 0.0 && per->beta0 <= 1.0)) return per_refuse(name, "beta0 must lie in [0, 1]");
+    if (!(per->eps > 0.0)) return per_refuse(name, "need eps > 0");
+    if (per->beta_steps < 0) return per_refuse(name, "need beta_steps >= 0");
+    for (const void *a : {(const void *)per->prio, (const void *)per->esum, (const void *)per->ssum, (const void *)per->pmax})
+        if (!dqn_on_device(a, p->device)) return per_refuse(name, "a priority array is not device memory of this handle's device (another device, or host memory)");
+    if (!p->per_z) {            // the workspace of the weights, at first use: a handle that never turns priorities on allocates nothing
+        int rc = on_device(p->device, [&] {
+            const size_t nb = (size_t)p->T.tiles_max * FPT_TM * sizeof(float);
+            float *z = nullptr, *w = nullptr, *ad = nullptr;
+            if (p->alloc((void **)&z, sizeof(float)) && p->alloc((void **)&w, nb) && p->alloc((void **)&ad, nb)) { p->per_w = w; p->per_ad = ad; p->per_z = z; }
+            else (void)hipGetLastError();
+        });
+        if (rc != RS_OK || !p->per_z) { g_create_err = std::string(name) + ": device allocation failed"; return RS_ENOMEM; }
+    }
+    p->per = *per; p->per_on = 1; p->ad_batch = 0;
+    return RS_OK;
+}
+extern "C" int rs_mplight_dqn_get_priorities(rs_mplight_dqn_handle p, rs_mplight_per *out, int32_t *on) {
+    if (!p || !out || !on) return per_refuse("rs_mplight_dqn_get_priorities", "NULL handle or pointer");
+    *on = p->per_on;
+    if (p->per_on) *out = p->per;
+    return RS_OK;
+}
+extern "C" int rs_mplight_dqn_per_rebuild(rs_mplight_dqn_handle p, void *stream) {
+    if (!p) return per_refuse("rs_mplight_dqn_per_rebuild", "NULL handle");
+    if (!p->per_on) return per_refuse("rs_mplight_dqn_per_rebuild", "priorities are off (rs_mplight_dqn_set_priorities)");
+    return on_device(p->device, [&] {
+        const FrapPer P = frap_per_tab(p);
+        hipLaunchKernelGGL(frap_per_esum_kernel, dim3(per_grid((long long)P.T * P.N)), dim3(PPT_T), 0, (hipStream_t)stream, P, (const int32_t *)nullptr, P.T * P.N);
+        hipLaunchKernelGGL(frap_per_ssum_kernel, dim3(per_grid(P.T)), dim3(PPT_T), 0, (hipStream_t)stream, P, (const int32_t *)nullptr, P.T);
+    });
+}
+extern "C" int rs_mplight_dqn_per_fill(rs_mplight_dqn_handle p, int32_t slot, void *stream) {
+    if (!p) return per_refuse("rs_mplight_dqn_per_fill", "NULL handle");
+    if (!p->per_on) return per_refuse("rs_mplight_dqn_per_fill", "priorities are off (rs_mplight_dqn_set_priorities)");
+    if (slot < 0 || slot >= p->per.capacity) return per_refuse("rs_mplight_dqn_per_fill", "slot outside the ring");
+    return on_device(p->device, [&] { frap_per_fill_launch(p, slot, (hipStream_t)stream); });
+}
+extern "C" int rs_mplight_dqn_per_commit(rs_mplight_dqn_handle p, const rs_mplight_ring *ring, const int32_t *idx, int32_t batch, void *stream) {
+    const char *name = "rs_mplight_dqn_per_commit";
+    if (p && !p->per_on) return per_refuse(name, "priorities are off (rs_mplight_dqn_set_priorities)");
+    if (int rc = dqn_check(p, ring, batch, name)) return rc;
+    if (int rc = dqn_check_idx(p, idx, "idx", name)) return rc;
+    if (p->ad_batch != batch) return per_refuse(name, "no preceding rs_mplight_dqn_grad of this batch size with priorities on: there is no |delta| to commit");
+    return on_device(p->device, [&] { frap_per_commit_launch(p, idx, batch, (hipStream_t)stream); });
 }
 
 // ---- MPLight on several maps: the shared-DQN update over M rings (resco_frap_multi.h).  The five flat vectors are the caller's; the
@@ -2344,8 +2448,11 @@ template <class H, class Ring> static int group_train(const rs_handle *hs, int32
         }
         // the learner's observe_step on the legacy stream: it waits for every pipe, and the pipes' next launches wait for it
         bool filled = false;
-        if constexpr (idqn)         // prioritised replay: the step's slot enters at the maximum priority before anything draws from it
-            if (lq->per_on) { dqn_per_fill_launch(lq, P.slot, hipStreamLegacy); filled = true; }
+        if (lq->per_on) {           // prioritised replay: the step's slot enters at the maximum priority before anything draws from it
+            if constexpr (idqn) dqn_per_fill_launch(lq, P.slot, hipStreamLegacy);
+            else frap_per_fill_launch(lq, P.slot, hipStreamLegacy);
+            filled = true;
+        }
         if (P.sync) dqn_sync_launch(lq, hipStreamLegacy);
         if (P.update) {
             const Ring r = ring_at(P.head, P.count);

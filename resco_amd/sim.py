@@ -40,6 +40,8 @@ ABI_SYMBOLS = ['rs_create', 'rs_destroy', 'rs_last_error', 'rs_reset', 'rs_step'
                'rs_dqn_set_priorities', 'rs_dqn_get_priorities', 'rs_dqn_per_rebuild', 'rs_dqn_per_fill', 'rs_dqn_per_commit',
                'rs_mplight_dqn_create', 'rs_mplight_dqn_sample', 'rs_mplight_dqn_grad', 'rs_mplight_dqn_step', 'rs_mplight_dqn_update',
                'rs_mplight_dqn_steps', 'rs_mplight_dqn_set_steps', 'rs_mplight_dqn_set_target', 'rs_mplight_dqn_get_target', 'rs_mplight_dqn_destroy',
+               'rs_mplight_dqn_set_priorities', 'rs_mplight_dqn_get_priorities', 'rs_mplight_dqn_per_rebuild', 'rs_mplight_dqn_per_fill',
+               'rs_mplight_dqn_per_commit',
                'rs_mplight_multi_create', 'rs_mplight_multi_sample', 'rs_mplight_multi_grad', 'rs_mplight_multi_step', 'rs_mplight_multi_update',
                'rs_mplight_multi_sync_target', 'rs_mplight_multi_steps', 'rs_mplight_multi_set_steps', 'rs_mplight_maps_set_target',
                'rs_mplight_maps_get_target', 'rs_mplight_multi_destroy',
@@ -154,6 +156,12 @@ def bind(L):
         if hasattr(L, 'rs_mplight_dqn_set_target'):     # (a host emulation may not have them)
             L.rs_mplight_dqn_set_target.argtypes = [vp, i32, i32]
             L.rs_mplight_dqn_get_target.argtypes = [vp, vp, vp]
+        if hasattr(L, 'rs_mplight_dqn_set_priorities'):     # (a host emulation may not have them)
+            L.rs_mplight_dqn_set_priorities.argtypes = [vp, vp]
+            L.rs_mplight_dqn_get_priorities.argtypes = [vp, vp, vp]
+            L.rs_mplight_dqn_per_rebuild.argtypes = [vp, vp]
+            L.rs_mplight_dqn_per_fill.argtypes = [vp, i32, vp]
+            L.rs_mplight_dqn_per_commit.argtypes = [vp, vp, vp, i32, vp]
         L.rs_mplight_dqn_destroy.argtypes = [vp]
         L.rs_mplight_dqn_destroy.restype = None
     if hasattr(L, 'rs_mplight_multi_create'):
@@ -316,6 +324,12 @@ class MPLightRing(C.Structure):
     """ctypes mirror of rs_mplight_ring (include/resco_sim.h): the device arrays of an MPLightReplay and its position"""
     _fields_ = [(k, C.c_void_p) for k in ('obs', 'act', 'rew', 'done')] + \
                [(k, C.c_int32) for k in ('capacity', 'n_envs', 'n_signals', 'width', 'head', 'count')]
+
+
+class MPLightPer(C.Structure):
+    """ctypes mirror of rs_mplight_per (include/resco_sim.h): the device arrays of the priorities and the options of prioritised replay"""
+    _fields_ = [(k, C.c_void_p) for k in ('prio', 'esum', 'ssum', 'pmax')] + [(k, C.c_int32) for k in ('capacity', 'n_envs', 'n_signals')] + \
+               [(k, C.c_double) for k in ('alpha', 'beta0', 'eps')] + [('beta_steps', C.c_int64)]
 
 
 class MPLightMap(C.Structure):

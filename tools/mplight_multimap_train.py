@@ -53,9 +53,11 @@ def random_delay(env, steps):
 
 
 def main(maps=('cologne3', 'ingolstadt7'), n_envs=(256,), episodes=30, batch=256, replay_steps=2048, seed=0, full=False, eval_on=(), quiet=False, made=None,
-         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, demand_variants=None, eval_demand=0, n_step=1, double_q=False):
-    """n_step / double_q: the learner's options of the same names.  -> (rows, final); a run that leaves at stop_after returns (rows, None).  made: a dict that receives the learner (closed when
+         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, demand_variants=None, eval_demand=0, n_step=1, double_q=False, per=None):
+    """n_step / double_q: the learner's options of the same names.  per: refused (--per; prioritised replay is the single-map learner's).  -> (rows, final); a run that leaves at stop_after returns (rows, None).  made: a dict that receives the learner (closed when
     the call returns; its vectors stay readable).  demand_variants / eval_demand: the demand flags of the module docstring."""
+    if per is not None and per is not False:
+        raise SystemExit('--per is not available on several maps: prioritised replay is built into the single-map fused update only (tools/mplight_train.py)')
     n_var, var_kw = demand.parse_spec(demand_variants)
     n_eval, eval_kw = demand.parse_spec(eval_demand)
     eval_kw = eval_kw or var_kw

@@ -5,7 +5,7 @@ resco_amd/agents/mplight_learn_fused.py on the policy's own weight vector) -> we
 tools/idqn_train.py for the reference's MPLight (agents/mplight.py, config/agent_config.py:101-113; batching:
 resco_amd/agents/mplight.py).
 
-    python tools/mplight_train.py [--n-step K] [--double-q] [--device-update | --device-loop] [map] [n_envs] [episodes] [batch] [replay_steps] [seed] [full]
+    python tools/mplight_train.py [--n-step K] [--double-q] [--per [alpha,beta0,beta_steps]] [--device-update | --device-loop] [map] [n_envs] [episodes] [batch] [replay_steps] [seed] [full]
 
 Prints one JSON line per episode (mean episode return of rewards.pressure per signal, average trip delay as utils/readXML.py
 computes it, epsilon, env-steps/s including learning) and a final line with the best training episode and the on-device random
@@ -15,6 +15,11 @@ policy on the same demand.  --device-loop (implies --device-update): the loop it
 --n-step K (1 .. 32) and --double-q, in every mode (the flags of tools/idqn_train.py): n-step returns (truncated at the newest slot of
 the ring, cut at an episode end) and Double DQN's bootstrap (the online network's best of ALL pairs, valued by the target network);
 both are part of a checkpoint's signature.  Without them: PFRL's plain one-step DQN.
+
+--per [alpha,beta0,beta_steps] (with --device-update or --device-loop only): prioritised experience replay in the fused update -- the
+minibatch is drawn by priority over the pooled rows (slot, environment, signal), the loss carries the importance weights and every
+update writes the rows' new priorities back (FusedMPLightLearner(per=...), rs_mplight_dqn_set_priorities).  Defaults 0.6, 0.4 and a
+beta that reaches 1 with the last planned update.  Part of a checkpoint's signature; --save-replay saves the priorities with the ring.
 
 Checkpoints (resco_amd/checkpoint.py), in every mode: --save PATH [--save-freq K] [--save-replay] (the replay ring only with --save-replay: it is the large part; without it a resumed run is a valid continuation, not the same one) writes the training state after every K-th
 episode and after the last; --load PATH continues at the stored episode (`episodes` stays the planned total, so the schedules and the
@@ -68,11 +73,14 @@ def greedy_on_variants(env, policy, state, actions, steps, seed, variants):
 
 
 def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, seed=0, full=False, quiet=False, device_update=False, device_loop=False, chunk=0,
-         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, demand_variants=None, eval_demand=0, n_step=1, double_q=False):
-    """n_step / double_q: the learners' options of the same names.  device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
+         save=None, save_freq=0, save_replay=False, load=None, eval_only=False, stop_after=0, demand_variants=None, eval_demand=0, n_step=1, double_q=False, per=None):
+    """n_step / double_q: the learners' options of the same names.  per: None, True (the defaults) or (alpha, beta0[, beta_steps]):
+    prioritised replay, with the fused learner only.  device_loop: the episodes' steps through DeviceTrainer.run, `chunk` steps per call (0: the whole episode in one).
     save / save_freq / save_replay / load / eval_only / stop_after: the checkpoint flags of the module docstring; a run that leaves
     at stop_after returns (rows, None).  demand_variants / eval_demand: the demand flags of the module docstring."""
     device_update = device_update or device_loop
+    if per is not None and per is not False and not device_update:
+        raise SystemExit('--per needs --device-update or --device-loop: prioritised replay is built into the fused update only')
     n_var, var_kw = demand.parse_spec(demand_variants)
     n_eval, eval_kw = demand.parse_spec(eval_demand)
     eval_kw = eval_kw or var_kw
@@ -82,7 +90,12 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
     net = frap_from_scenario(env.scenario, 4 if full else 1).cuda()
     net.init_like_reference(seed)
     if device_update:
-        learner = FusedMPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed, n_signals=S, n_step=n_step, double_q=double_q)
+        if per is True:
+            per = (0.6, 0.4)
+        if per:             # beta reaches 1 with the last planned update unless told otherwise (one update per env-step)
+            per = dict(alpha=per[0], beta0=per[1], beta_steps=int(per[2]) if len(per) > 2 else episodes * steps)
+        learner = FusedMPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, seed=seed, n_signals=S, n_step=n_step, double_q=double_q,
+                                      per=per or None)
     else:
         learner = MPLightLearner(net, gamma=0.99, lr=1e-3, target_update=500, batch_size=batch, n_step=n_step, double_q=double_q)
     policy = FusedMPLight(net, env.scenario, seed=7 + seed)
@@ -94,6 +107,8 @@ def main(map_name='cologne1', n=256, episodes=30, batch=256, replay_steps=2048, 
     gen = torch.Generator(device='cuda').manual_seed(seed)
     decay = int(0.8 * episodes * steps)     # the reference decays over config['steps'] env-steps
     trainer = DeviceTrainer(env, learner, policy, replay, 1.0, 0.0, decay) if device_loop else None
+    if device_update:
+        learner.attach(replay)      # (prioritised replay: the priorities are sized from this ring, before a checkpoint is loaded)
     # what a checkpoint holds (the network before the learner and the policy that read it) and what else shapes the trajectory
     agent = 'MPLightFULL' if full else 'MPLight'
     objects = dict(env=env, net=net, learner=learner, policy=policy, replay=replay)
@@ -182,6 +197,8 @@ if __name__ == '__main__':
     device_loop = bool(a) and a[0] == '--device-loop'
     device_update = device_loop or (bool(a) and a[0] == '--device-update')
     a = a[1:] if device_update else a
+    if 'per' in ckpt and not device_update:
+        raise SystemExit('--per needs --device-update or --device-loop: prioritised replay is built into the fused update only')
     main(a[0] if len(a) > 0 else 'cologne1', int(a[1]) if len(a) > 1 else 256, int(a[2]) if len(a) > 2 else 30,
          int(a[3]) if len(a) > 3 else 256, int(a[4]) if len(a) > 4 else 2048, int(a[5]) if len(a) > 5 else 0,
          full=len(a) > 6 and a[6] == 'full', device_update=device_update, device_loop=device_loop, **ckpt, **dem)
