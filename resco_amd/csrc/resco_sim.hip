@@ -53,14 +53,28 @@ __device__ __forceinline__ int32_t rs_wave_ticket(int32_t *p) {
     return __builtin_amdgcn_readlane(base, __ffsll((long long)m) - 1) + below;
 }
 // one atomic per wave instead of one per lane (64 lanes adding to ONE LDS address are served one after the other): called
-// where the whole wave is converged
+// where the whole wave is converged.  The reduction over the 64 lanes is six DPP steps in the VALU (no LDS access, where a
+// __shfl_xor is a ds_bpermute_b32 and a wait each): a running sum inside every row of 16 lanes (row_shr:1/2/4/8), the last lane of
+// rows 0 and 2 added to rows 1 and 3 (row_bcast:15, row mask 0xa), the last lane of row 1 to rows 2 and 3 (row_bcast:31, row mask
+// 0xc).  Lane 63 ends up with the result of the wave.  A lane that a step gives no source keeps its value: `old` is the identity of
+// the operation (0, INT32_MIN -- right for any int32_t), which also lets the compiler fold every step into ONE v_add_u32_dpp /
+// v_max_i32_dpp.
+#define RS_DPP_REDUCE(v, ident, OP)                                                                                                   \
+    OP(v, __builtin_amdgcn_update_dpp((int)(ident), (int)v, 0x111, 0xf, 0xf, false))     /* row_shr:1 */                               \
+    OP(v, __builtin_amdgcn_update_dpp((int)(ident), (int)v, 0x112, 0xf, 0xf, false))     /* row_shr:2 */                               \
+    OP(v, __builtin_amdgcn_update_dpp((int)(ident), (int)v, 0x114, 0xf, 0xf, false))     /* row_shr:4 */                               \
+    OP(v, __builtin_amdgcn_update_dpp((int)(ident), (int)v, 0x118, 0xf, 0xf, false))     /* row_shr:8 */                               \
+    OP(v, __builtin_amdgcn_update_dpp((int)(ident), (int)v, 0x142, 0xa, 0xf, false))     /* row_bcast:15 */                            \
+    OP(v, __builtin_amdgcn_update_dpp((int)(ident), (int)v, 0x143, 0xc, 0xf, false))     /* row_bcast:31 */
+#define RS_DPP_ADD(v, o) v += (o);
+#define RS_DPP_MAX(v, o) { const int32_t o_ = (o); v = o_ > v ? o_ : v; }
 __device__ __forceinline__ void rs_wave_add(int32_t *p, int32_t v) {
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(p, v);
+    RS_DPP_REDUCE(v, 0, RS_DPP_ADD)
+    if ((threadIdx.x & 63) == 63 && v) atomicAdd(p, v);
 }
 __device__ __forceinline__ void rs_wave_max(int32_t *p, int32_t v) {
-    for (int m = 32; m > 0; m >>= 1) { const int32_t o = __shfl_xor(v, m); v = o > v ? o : v; }
-    if ((threadIdx.x & 63) == 0) atomicMax(p, v);
+    RS_DPP_REDUCE(v, INT32_MIN, RS_DPP_MAX)
+    if ((threadIdx.x & 63) == 63) atomicMax(p, v);
 }
 __device__ __forceinline__ void rs_atomic_or(uint32_t *p, uint32_t v) { atomicOr(p, v); }
 __device__ __forceinline__ uint32_t rs_atomic_fetch_or(uint32_t *p, uint32_t v) { return atomicOr(p, v); }
@@ -161,11 +175,14 @@ template <bool PROF> struct DevExec {
     }
     // tid / 64 as a wave-uniform value: what is derived from it (the roles of the waves inside a phase) stays in scalar registers
     __device__ __forceinline__ int wave_of(int) const { return wave; }
-    // the next work chunk of this wave: one LDS atomic per wave (called with the wave converged), broadcast from its first lane
-    __device__ __forceinline__ int next_chunk(int32_t *ctr, int, int, int) const {
+    // the next work chunk of this wave (called with the wave converged).  The first chunk of wave w is chunk w, known without a memory
+    // access; every later one is a ticket: one LDS atomic per wave, broadcast from its first lane.  The counter starts at 0 in every
+    // phase and counts the tickets only, so the chunks are still handed out in ascending order (longest code path first).
+    __device__ __forceinline__ int next_chunk(int32_t *ctr, int w, int it, int nwv) const {
+        if (it == 0) return w;
         int c = 0;
         if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0) c = atomicAdd(ctr, 1);
-        return __builtin_amdgcn_readfirstlane(c);
+        return __builtin_amdgcn_readfirstlane(c) + nwv;
     }
     // time a wave spends in one role of a phase: sum of the 100 MHz ticks in the low 40 bits, number of waves above
     __device__ __forceinline__ unsigned long long role_begin() const { return (PROF && prof) ? wall_clock64() : 0ull; }

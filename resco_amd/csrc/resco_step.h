@@ -7,9 +7,10 @@
 //   ex.role_begin/role_end  optional timers of what one WAVE does inside a phase (ids 3, 7-10, 15)
 //   ex.B                    threads per workgroup (a multiple of 64)
 //   ex.wave_of(tid)         tid / 64, known to be the same for the 64 threads of a wave (a scalar on the GPU)
-//   ex.next_chunk(c, w, i, n)  the next work chunk of wave w (its i-th call in this phase, n waves): on the GPU ONE atomic on the LDS
-//                           counter c per wave (dynamic: whichever wave is free takes the next chunk), on the host i * n + w --
-//                           any assignment of chunks to waves gives the same result, a phase being order independent
+//   ex.next_chunk(c, w, i, n)  the next work chunk of wave w (its i-th call in this phase, n waves): on the GPU chunk w for i = 0 (no
+//                           memory access) and then n + ONE atomic on the LDS counter c per wave (dynamic: whichever wave is free
+//                           takes the next chunk), on the host i * n + w -- any assignment of chunks to waves gives the same
+//                           result, a phase being order independent
 // On the GPU (resco_sim.hip) one workgroup = one environment; the state lives in LDS for the whole env-step and phase() is
 // `f(threadIdx.x); __syncthreads()`.  The CPU tests compile the very same source for the host (tests/hostemu), where
 // phase() calls f for tid = 0 .. B-1 in turn (in any order: a phase never reads what another thread writes in the same
@@ -241,7 +242,8 @@ template <class Tp> struct LPtr {
 struct Lds {
     LPtr<Node> node;
     LPtr<Aux> aux;
-    LPtr<float> vnx, vtp;
+    LPtr<float> vnx, vtp;       // vnx, per slot: from the plan to the move of a tick the next speed; from classify() (L1, insertion, end of
+                                // the move) to the plan of the coming tick that plan's look-ahead distance (see plan_look)
     LPtr<uint16_t> grid;        // ONE grid of cells (resco_tables.h: a cell carries the parity of the tick it is valid for): a tick
                                 // reads the cells of its parity and pushes the moved vehicles with the other one
     uint32_t gstride;           // cells of the grid (padded to a multiple of 8)
@@ -960,15 +962,17 @@ RS_DEV float plan_vfree(const float *vt, float v, float lane_vmax, float sf) {
     if (vt[VT_MAXSPEED] < vfree) vfree = vt[VT_MAXSPEED];
     return vfree;
 }
-// (classify() and phase_plan() both evaluate plan_vfree / plan_look, at different inline sites; the short paths of the plan and the move
-// rely on the two giving the SAME bits -- a vehicle without FL_H never has `seen < look` in its plan.  That holds because the library is
-// built with -ffp-contract=off (resco_amd/build.py): no site-dependent FMA fusion.  The host emulation asserts it (RS_ASSERT), and
-// every HIP == oracle test would see a missed stop line as a position difference.)
+// (The look-ahead distance of a tick is computed ONCE, by classify(), which leaves it in L.vnx[s]; the plan of that tick reads it there
+// instead of evaluating plan_look again -- one division, a float-int-float conversion and four reads of the vType row less per vehicle
+// and tick, in every inlined copy of the plan.  INVARIANT: no plan runs for a slot without a classify() of the same slot on the same
+// state before it: classify() runs in L1 for every vehicle of the slab (n_ticks > 0), at every insertion and at the end of every move
+// that has a tick after it (`more`) -- and L.vnx[s] has no other writer between that classify() and the plan (the plan itself writes
+// the next speed there, for C and M of its tick; the move reads it at its top, before it calls classify()).  The short paths of the
+// plan and the move rely on the plan seeing the SAME bits classify() tested -- a vehicle without FL_H never has `seen < look` in its
+// plan -- which the carried value gives by construction.  The plan still asserts that the carried value is what it would compute
+// itself (RS_ASSERT: the host emulation aborts, the checking build counts); that equality rests on -ffp-contract=off
+// (resco_amd/build.py): no site-dependent FMA fusion.)
 RS_DEV float plan_look(const float *vt, float vfree) { return d_brake_gap(vfree, vt[VT_DECEL]) + vfree * vt[VT_TAU] + vt[VT_MINGAP] + 1.0f; }
-// FL_H for a vehicle at x on a lane of length len: the end of the lane is inside its look-ahead
-RS_DEV bool looks_beyond(const float *vt, float v, float x, float lane_len, float lane_vmax, float sf) {
-    return lane_len - x < plan_look(vt, plan_vfree(vt, v, lane_vmax, sf));
-}
 // can the lane-change decision of tick t have an effect for a vehicle in this state?  (a superset, computed before the
 // grid of tick t is complete: it is on a lane that is not a best one -- whether the need has arisen depends on the queue
 // beside it --, or it is its turn to look for speed gain on a neighbour lane that may be good enough)
@@ -1007,7 +1011,10 @@ template <class TT> RS_DEV bool may_change_lanes(const TT &T, int rq, uint32_t n
 // The work of tick t for the vehicle in slot s (state as of the beginning of that tick): its flags, and it is queued
 template <class TT, class LT> RS_DEV int classify(const TT &T, const LT &L, int s, const float *vt, float v, float x, const LaneRec &LR, int lane, int rq, uint32_t nb, int k, float sf, int t) {
     int fl = 0;
-    if (looks_beyond(vt, v, x, LR.len, LR.vmax, sf)) { fl |= FL_H; list_push(L, L.ls_h, SC_NH, s); }
+    // how far the plan of tick t looks: kept for it (see plan_look).  FL_H: the end of the lane is inside the look-ahead
+    const float look = plan_look(vt, plan_vfree(vt, v, LR.vmax, sf));
+    L.vnx[s] = look;
+    if (LR.len - x < look) { fl |= FL_H; list_push(L, L.ls_h, SC_NH, s); }
     if (may_change_lanes(T, rq, nb, LR, lane, k, x, v, t)) { fl |= FL_LC; list_push(L, L.ls_lc, SC_NLC, s); }
     return fl;
 }
@@ -1036,7 +1043,8 @@ template <bool LONG, class TT, class LT, class GT> RS_DEV void phase_plan(const 
     bool have = false;
     if (LONG) RS_SEC(7)
     const float vfree = plan_vfree(vt, v, LR.vmax, sf);
-    const float look = plan_look(vt, vfree);
+    const float look = L.vnx[s];        // (what classify() computed on this very state and tested for FL_H: see plan_look)
+    RS_ASSERT(look == plan_look(vt, vfree))
     const Found ld = leader_found(L, grid, LR.cell0, lane_cells(L, LR), x, k, s, look + T.maxlen);
     const int lead = ld.slot;
     if (LONG) RS_SEC(8)
